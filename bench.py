@@ -36,7 +36,7 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-PEAK_BF16_TFLOPS = 2500.0   # dense MFMA bf16 peak, /opt/skills/guides/MI355X_MICROARCH.md
+PEAK_BF16_TFLOPS = 2500.0   # dense MFMA bf16 peak of the MI355X (nominal 2.4 GHz)
 S_TEXT, N_AUDIO_TOK, NEW_TOKENS = 288, 88, 10
 SPEECH_AT = 280             # the <SpeechHere> slot sits near the end of the VOXCELEB prompt ("...\nOutput:")
 
@@ -111,7 +111,41 @@ def parse():
     ap.add_argument("--workload", default="c2", choices=["c2", "c2s", "c4", "c5"],
                     help="BASELINE.md §4: c2 = headline (default); c2s = 5 speech exemplars; c4 = Qwen2-Audio HVB; "
                          "c5 = Llama2-13B VOXCELEB+HVB+VOXPOPULI round-robin")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (utterance indices, generated ids, "
+                         "first-step logits) as DIR/<name>.npy in float32, at most 64 MB in all, for output-by-output A/B "
+                         "of two builds on the same arguments")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64_000_000 - 64 * 1024     # 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir: str, arrays) -> dict:
+    """`arrays` (name -> tensor / array, all with the same leading row count) -> out_dir/<name>.npy in float32 (token ids
+    and utterance indices are exact in float32).  Past DUMP_BUDGET_BYTES in all, the same fixed seeded sample of rows is
+    kept in every array and its row numbers are written as rows.npy."""
+    host = {k: (v.detach().float().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float32))
+            for k, v in arrays.items()}
+    n_rows = {a.shape[0] for a in host.values()}
+    assert len(n_rows) == 1, f"dump arrays disagree on the row count: { {k: a.shape for k, a in host.items()} }"
+    n = n_rows.pop()
+    row_bytes = sum(a[0].nbytes for a in host.values()) if n else 0
+    if n and row_bytes * n > DUMP_BUDGET_BYTES:
+        keep = max(1, (DUMP_BUDGET_BYTES - 4 * n) // row_bytes)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        host = {k: a[rows] for k, a in host.items()}
+        host["rows"] = rows.astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return {"dir": out_dir, "files": {f"{k}.npy": list(a.shape) for k, a in host.items()}, "dtype": "float32",
+            "sampled_rows": "rows" in host}
 
 
 def launch_ranks(args) -> None:
@@ -758,6 +792,8 @@ def main():
     idx_dev = torch.arange(Bm, dtype=torch.int64, device=cdev)
     len_dev = torch.full((Bm,), NEW_TOKENS, dtype=torch.int32, device=cdev)
 
+    last = {}
+
     def step(s, gather=True):
         if is_qwen:
             speech, _ = rt.encode_audio(raw_wav=wavs[s], wav_lens=lens)
@@ -768,6 +804,7 @@ def main():
             packer.pack(row_local, index=idx_dev + firsts[s], gen_ids=rt.ws.get("gen_tokens", (Bm, NEW_TOKENS), torch.int32),
                         gen_len=len_dev, first_logits=res.first_logits)
             dp.all_gather_rows(dist, row_local, out=row_all)
+        last["res"] = res
         return res.tokens
 
     def barrier():
@@ -816,6 +853,18 @@ def main():
                        "last_step_indices_ok": bool(torch.equal(got["index"].cpu(), want_idx)),
                        "own_rows_roundtrip_ok": bool(torch.equal(got["gen_ids"][:Bm].cpu(), mine)),
                        "backend": dist.get_backend()}
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, copied off the workspace before anything below reuses it; at N > 1 the rows
+        # every rank gathered in that step
+        if world > 1:
+            dumped = dump_outputs(args.dump_outputs, {"utterance_index": got["index"], "tokens": got["gen_ids"],
+                                                      "first_logits": got["first_logits"]})
+        else:
+            res = last["res"]
+            dumped = dump_outputs(args.dump_outputs, {"utterance_index": torch.arange(Bm) + firsts[-1], "tokens": res.tokens,
+                                                      "first_logits": res.first_logits})
+        log(f"outputs of the last timed step written: {dumped}")
 
     # ---- roofline of the dominant kernel, from live HIP-event timings -------------------------------
     roof = None
@@ -923,6 +972,8 @@ def main():
                      "dataloader_workers_per_rank": plugin_workers},
         }
         out["hbm_peak_gib_timed_loop"] = round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1) if rt is not None else hbm_peak
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if plugin_block is not None:
             out["through_plugin"] = plugin_block
             log(f"through-plugin (all ranks): {json.dumps({k: v for k, v in plugin_block.items() if k not in ('per_rank', 'note')})}")

@@ -157,16 +157,26 @@ if int(os.environ["RANK"]) == 0:
 """
 
 
+# the DP plumbing tests run on the CPU whatever the machine has: with a GPU visible the CLI would put rank r on cuda:r over
+# nccl, which a one-GPU machine cannot host for two ranks
+_NO_GPU = {"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"}
+
+
+def _run_checked(cmd, env):
+    p = subprocess.run(cmd, env=env, timeout=300, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
+    assert p.returncode == 0, f"{' '.join(cmd)} exited {p.returncode}:\n{p.stderr[-4000:]}"
+
+
 def _run_dp(script, out_dir, world, port, extra_env=None):
     if world == 1:
-        env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", **(extra_env or {}))
+        env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", **_NO_GPU, **(extra_env or {}))
         cmd = [sys.executable, str(script), ROOT, str(out_dir)]
     else:
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-        env.update(extra_env or {})
+        env.update(_NO_GPU, **(extra_env or {}))
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
                "127.0.0.1", "--master-port", str(port), str(script), ROOT, str(out_dir)]
-    subprocess.run(cmd, check=True, env=env, timeout=300, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    _run_checked(cmd, env)
     return json.load(open(os.path.join(out_dir, "summary.json")))
 
 
@@ -249,9 +259,10 @@ def test_bench_through_plugin_leg_runs_on_every_rank_gloo_world2(tmp_path):
     script = tmp_path / "bench_dp.py"
     script.write_text(_BENCH_DP_SCRIPT)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    env.update(_NO_GPU)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29631", str(script), ROOT, str(tmp_path)]
-    subprocess.run(cmd, check=True, env=env, timeout=300, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    _run_checked(cmd, env)
     b = json.load(open(tmp_path / "plugin.json"))
     assert b["n_ranks"] == 2 and b["batch_size_per_rank"] == 3 and b["batches_timed_per_rank"] == 2
     assert b["last_batch_indices_ok"] is True and "all_gather_into_tensor" in b["collective"]
