@@ -14,6 +14,7 @@
 // Tiles: 128x128 (2x2 waves, 4x4 MFMA tiles per wave) for prefill/encoder shapes,
 //        64x64   (2x2 waves, 2x2 MFMA tiles per wave) for skinny / decode shapes (+ split-K).
 #include "gemm_common.h"
+#include <vector>
 
 using namespace iclg;
 
@@ -661,6 +662,199 @@ __global__ __launch_bounds__(256) void pack_decode_w_kernel(const unsigned short
   }
 }
 
+// =================================================================================================================
+// FP8 weight mode (icl_pack_fp8_weights / icl_gemm_fp8w): the decoder's GEMM weights W are replaced by W' = q * 2^e_n, where
+// e_n is the smallest integer with max_k |W[n][k]| <= 448 * 2^e_n (0 for an all-zero row) and q[n][k] = RNE_e4m3fn(W[n][k] / 2^e_n)
+// (OCP e4m3fn; the division is exact and never saturates).  W' is exact in bf16 (4 significant bits, power-of-two scale).
+// The decode kernel streams q (1 byte per weight) and rebuilds W' in registers: fp8 -> f32 (exact), * 2^e_n (exact: every lane
+// of an MFMA weight fragment holds ONE output row, so the scale is per lane), -> bf16 (exact).  It then issues the MFMA sequence
+// of the bf16 skinny kernel on those fragments, so its output is the bits tile 6 produces on the decode-packed copy of W'.
+// =================================================================================================================
+__device__ __forceinline__ int fp8_row_exponent(float m) {
+  if (m == 0.f) return 0;
+  int k;
+  const float f = frexpf(m, &k);            // m = f * 2^k, f in [0.5, 1);  448 = 0.875 * 2^9
+  return f <= 0.875f ? k - 9 : k - 8;
+}
+// |x| <= 448: round to nearest even into e4m3fn, integer arithmetic on the f32 bits (sign kept, -0 -> 0x80 as torch does)
+__device__ __forceinline__ unsigned f32_to_e4m3fn(float x) {
+  const unsigned u = __float_as_uint(x), a = u & 0x7fffffffu;
+  unsigned c;
+  if (a < 0x3c800000u) c = (unsigned)rintf(__uint_as_float(a) * 512.f);   // |x| < 2^-6: the subnormal grid 2^-9 (8 -> 0x08 = 2^-6)
+  else c = ((a + 0x7ffffu + ((a >> 20) & 1u)) >> 20) - (120u << 3);      // 3 mantissa bits, exponent bias 127 -> 7
+  return ((u >> 24) & 0x80u) | c;
+}
+// q * 2^e as bf16 bits (exact whenever the result is a bf16 normal)
+__device__ __forceinline__ unsigned short e4m3fn_scaled_to_bf16(unsigned c, int e) {
+  const int E = (c >> 3) & 15, M = c & 7;
+  const float v = ldexpf((float)(E ? 8 + M : M), (E ? E - 1 : 0) - 9 + e);
+  return f32_to_bf16_bits((c & 0x80u) ? -v : v);
+}
+
+// One block per 16-row n-tile.  Phase 1: row maxima (and a finiteness check) -> e_n, scales[n] = 2^e_n (NaN marks a row with a
+// non-finite value; the host rejects the matrix).  Phase 2: the fp8 decode-packed pieces — piece (n-tile, k-pair j, lane = fq*16 + fr)
+// is 16 B: q[16*nt + fr][64j + 8fq .. +8] then q[16*nt + fr][64j + 32 + 8fq .. +8] (two 32-wide k-steps; a wave-load is 1 KB
+// contiguous, as in pack_decode_w_kernel) — and W' over the row-major matrix Wd (may be W itself: each thread rewrites only what
+// it has read, after the block's maxima are known).
+__global__ __launch_bounds__(256) void pack_fp8_w_kernel(const unsigned short* W, int64_t ldw, int N, int K, u32x4* q, float* scales,
+                                                         unsigned short* Wd, int64_t ldd) {
+  __shared__ int e_s[16];
+  __shared__ int bad_s[16];
+  const int nt = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int r = wave; r < 16; r += 4) {
+    const int64_t row = (int64_t)nt * 16 + r;
+    float m = 0.f, bad = 0.f;
+    if (row < N) {
+      for (int k = lane * 8; k < K; k += 512) {
+        const u32x4 v = *(const u32x4*)(W + row * ldw + k);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float x0 = fabsf(__uint_as_float(v[j] << 16)), x1 = fabsf(__uint_as_float(v[j] & 0xffff0000u));
+          if (!(x0 <= 3.4028235e38f) || !(x1 <= 3.4028235e38f)) bad = 1.f;
+          m = fmaxf(m, fmaxf(x0, x1));
+        }
+      }
+    }
+    m = wave_reduce_max(m);
+    bad = wave_reduce_max(bad);
+    if (lane == 0) {
+      const int e = fp8_row_exponent(m);
+      e_s[r] = e;
+      bad_s[r] = bad != 0.f;
+      if (row < N) scales[row] = bad != 0.f ? __uint_as_float(0x7fc00000u) : ldexpf(1.f, e);
+    }
+  }
+  __syncthreads();
+  const int kp = K >> 6;
+  for (int pi = tid; pi < kp * 64; pi += 256) {
+    const int l = pi & 63, j = pi >> 6, fr = l & 15, fq = l >> 4;
+    const int64_t row = (int64_t)nt * 16 + fr;
+    u32x4 out = {0u, 0u, 0u, 0u};
+    if (row < N && !bad_s[fr]) {
+      const int e = e_s[fr];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int64_t k = (int64_t)j * 64 + h * 32 + fq * 8;
+        const u32x4 v = *(const u32x4*)(W + row * ldw + k);
+        u32x4 wd;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const unsigned c0 = f32_to_e4m3fn(ldexpf(__uint_as_float(v[i] << 16), -e));
+          const unsigned c1 = f32_to_e4m3fn(ldexpf(__uint_as_float(v[i] & 0xffff0000u), -e));
+          out[h * 2 + (i >> 1)] |= (c0 | (c1 << 8)) << ((i & 1) * 16);
+          wd[i] = (unsigned)e4m3fn_scaled_to_bf16(c0, e) | ((unsigned)e4m3fn_scaled_to_bf16(c1, e) << 16);
+        }
+        *(u32x4*)(Wd + row * ldd + k) = wd;
+      }
+    }
+    q[((int64_t)nt * kp + j) * 64 + l] = out;
+  }
+}
+
+// 8 e4m3fn codes (two dwords, element k in byte k) -> bf16 fragment of q * sc (sc = 2^e_n of this lane's row: every step exact)
+__device__ __forceinline__ bf16x8 fp8x8_scaled_bf16(unsigned lo, unsigned hi, float sc) {
+  const f32x2 s = {sc, sc};
+  const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8(lo, false) * s, b = __builtin_amdgcn_cvt_pk_f32_fp8(lo, true) * s;
+  const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8(hi, false) * s, d = __builtin_amdgcn_cvt_pk_f32_fp8(hi, true) * s;
+  return bf16x8{(__bf16)a[0], (__bf16)a[1], (__bf16)b[0], (__bf16)b[1], (__bf16)c[0], (__bf16)c[1], (__bf16)d[0], (__bf16)d[1]};
+}
+
+// gemm_skinny_kernel<MB, NT, U, true> on the fp8 decode-packed copy: same block shape, same per-wave K split (k-steps s0 .. s1 - 1
+// of 32), same MFMA order per accumulator (k-step ascending), same wave-0..7 combine and epilogues.  A wave-load is 16 B per lane =
+// two k-steps, so a wave walks the k-PAIRS that overlap its range and skips the half-pair outside it at either end (wave-uniform
+// branches).  U k-pairs are loaded per batch; the batch past the end re-reads the wave's last pair (in bounds, never used).
+template <int MB, int NT, int U>
+__global__ __launch_bounds__(512) void gemm_skinny_fp8w_kernel(GemmParams p, const float* __restrict__ wscale) {
+  __shared__ float red[8][NT][MB][256];   // [wave][n-tile][m-block][lane*4 + r]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int fr = lane & 15, fq = lane >> 4;
+  const int n0 = blockIdx.x * (16 * NT);
+  const int steps = p.K >> 5;
+  const int s0 = (int)(((int64_t)wave * steps) >> 3), s1 = (int)(((int64_t)(wave + 1) * steps) >> 3);
+  const int j0 = s0 >> 1, j1 = (s1 + 1) >> 1;
+
+  const unsigned char* wp[NT];
+  float sc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    wp[t] = (const unsigned char*)p.W + (int64_t)min((n0 >> 4) + t, ((p.N + 15) >> 4) - 1) * (p.K >> 6) * 1024 + lane * 16;
+    sc[t] = wscale[min(n0 + t * 16 + fr, p.N - 1)];
+  }
+  const __bf16* ap[MB];
+#pragma unroll
+  for (int b = 0; b < MB; ++b) ap[b] = p.A + (int64_t)min(b * 16 + fr, p.M - 1) * p.lda + fq * 8;
+
+  f32x4 acc[NT][MB];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int b = 0; b < MB; ++b) acc[t][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int j = j0; j < j1; j += U) {
+    u32x4 wq[U][NT];
+    bf16x8 af[U][2][MB];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int jj = min(j + u, j1 - 1);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) wq[u][t] = *(const u32x4*)(wp[t] + (int64_t)jj * 1024);
+#pragma unroll
+      for (int b = 0; b < MB; ++b) {
+        af[u][0][b] = *(const bf16x8*)(ap[b] + (int64_t)jj * 64);
+        af[u][1][b] = *(const bf16x8*)(ap[b] + (int64_t)jj * 64 + 32);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (j + u >= j1) break;
+      const int s = 2 * (j + u);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (h == 0 ? s < s0 : s + 1 >= s1) continue;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const bf16x8 wf = fp8x8_scaled_bf16(wq[u][t][2 * h], wq[u][t][2 * h + 1], sc[t]);
+#pragma unroll
+          for (int b = 0; b < MB; ++b) acc[t][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, af[u][h][b], acc[t][b], 0, 0, 0);
+        }
+      }
+    }
+  }
+  // ---- in-block split-K combine and epilogue: gemm_skinny_kernel's, unchanged --------------------------------------
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int b = 0; b < MB; ++b) *(f32x4*)&red[wave][t][b][lane * 4] = acc[t][b];
+  __syncthreads();
+  for (int f = wave; f < NT * MB; f += 8) {
+    const int t = f / MB, b = f - t * MB;
+    f32x4 v = *(const f32x4*)&red[0][t][b][lane * 4];
+#pragma unroll
+    for (int w = 1; w < 8; ++w) v = v + *(const f32x4*)&red[w][t][b][lane * 4];
+    if (!(p.epi & ICL_EPI_SWIGLU)) epi_store4(p, 0, b * 16 + fr, n0 + t * 16 + fq * 4, v);
+    else *(f32x4*)&red[0][t][b][lane * 4] = v;
+  }
+  if (p.epi & ICL_EPI_SWIGLU) {
+    if constexpr (NT == 2) {
+      __syncthreads();
+      for (int b = wave; b < MB; b += 8) {
+        const f32x4 g = *(const f32x4*)&red[0][0][b][lane * 4], u = *(const f32x4*)&red[0][1][b][lane * 4];
+        epi_store_swiglu(p, 0, b * 16 + fr, n0, fq * 4, g, u);
+      }
+    }
+  }
+}
+
+template <int MB, int NT, int U>
+int launch_skinny_fp8w(GemmParams& p, const float* wscale, hipStream_t stream) {
+  const int blocks = (p.N + 16 * NT - 1) / (16 * NT);
+  hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<MB, NT, U>), dim3(blocks), dim3(512), 0, stream, p, wscale);
+  ICL_CHECK_LAUNCH("icl_gemm_fp8w");
+  return ICL_OK;
+}
+
+
 template <int DEPTH, int MT>
 int launch_m128(GemmParams& p, hipStream_t stream) {
   constexpr int BN = 128, SMEM = (DEPTH + 1) * MT * 16 * 128;
@@ -753,7 +947,9 @@ struct NormFuse {
   int64_t ldx;
 };
 
-static int gemm_impl(const icl_gemm_args* a, void* stream_, const RopeFuse* rope, const NormFuse* norm = nullptr) {
+// wscale != NULL: W is the fp8 decode-packed copy made by icl_pack_fp8_weights and wscale its row scales (icl_gemm_fp8w)
+static int gemm_impl(const icl_gemm_args* a, void* stream_, const RopeFuse* rope, const NormFuse* norm = nullptr,
+                     const float* wscale = nullptr) {
   hipStream_t stream = (hipStream_t)stream_;
   ICL_CHECK_ARG(a != nullptr, "icl_gemm_bf16: args is NULL");
   ICL_CHECK_ARG(a->A && a->W && a->C, "icl_gemm_bf16: A/W/C must be non-NULL");
@@ -812,6 +1008,16 @@ static int gemm_impl(const icl_gemm_args* a, void* stream_, const RopeFuse* rope
   p.tiles_m = p.tiles_n = 0;
   p.group_m = p.xcd_sync = 0;   // the 128x128 / 64x64 tiles keep GROUP_M; the 256x256 launcher picks per shape
 
+  if (wscale) {     // the fp8-weight skinny kernel (tile 6's shape and arithmetic on W' = q * 2^e)
+    ICL_CHECK_ARG(a->M <= 64 && a->batch == 1 && !rope, "icl_gemm_fp8w: needs M <= 64 and batch == 1 (M=%d batch=%d)", a->M, a->batch);
+    p.split_k = 1;   // K is split inside the block
+    const bool sw = a->epilogue & ICL_EPI_SWIGLU;
+    const int mb = (a->M + 15) / 16;
+    if (sw) return mb <= 1 ? launch_skinny_fp8w<1, 2, 4>(p, wscale, stream) : mb == 2 ? launch_skinny_fp8w<2, 2, 2>(p, wscale, stream)
+                           : launch_skinny_fp8w<4, 2, 1>(p, wscale, stream);
+    return mb <= 1 ? launch_skinny_fp8w<1, 1, 8>(p, wscale, stream) : mb == 2 ? launch_skinny_fp8w<2, 1, 4>(p, wscale, stream)
+                   : launch_skinny_fp8w<4, 1, 2>(p, wscale, stream);
+  }
   int tile = a->tile;
   if (tile == 0) tile = icl_gemm_select_tile(a->M, a->N, a->K, a->batch, a->split_k);
   if (tile == 3 && a->K < 128) tile = 1;   // the 256x256 pipeline peels two K-tiles; same arithmetic on the 128x128 tile
@@ -868,7 +1074,8 @@ static int gemm_impl(const icl_gemm_args* a, void* stream_, const RopeFuse* rope
 extern "C" int icl_rmsnorm(const void* x, int64_t ldx, const float* gamma, void* y, int64_t ldy, int32_t M, int32_t N, float eps,
                            int32_t in_dtype, int32_t out_dtype, void* stream);
 
-extern "C" int icl_gemm_rmsnorm_bf16(const icl_gemm_args* a, const float* gamma, float eps, void* xn, int64_t ld_xn, void* stream) {
+static int gemm_rmsnorm_impl(const icl_gemm_args* a, const float* wscale, const float* gamma, float eps, void* xn, int64_t ld_xn,
+                             void* stream) {
   ICL_CHECK_ARG(a != nullptr && gamma && xn, "icl_gemm_rmsnorm_bf16: NULL pointer");
   ICL_CHECK_ARG(a->batch == 1 && a->out_dtype == ICL_F32 && (a->epilogue & ~ICL_EPI_RESIDUAL) == 0 &&
                     (!(a->epilogue & ICL_EPI_RESIDUAL) || a->res_dtype == ICL_F32),
@@ -879,14 +1086,14 @@ extern "C" int icl_gemm_rmsnorm_bf16(const icl_gemm_args* a, const float* gamma,
                     (!a->R || ((uintptr_t)a->R & 15) == 0), "icl_gemm_rmsnorm_bf16: misaligned pointer");
   // the skinny kernels (tiles 4 / 6) split K inside the block and write the finished row themselves whatever split_k says:
   // only a launch that really leaves split-K slabs behind takes the fused reduce + RMSNorm
-  if (a->split_k > 1 && a->tile != 4 && a->tile != 6) {
+  if (a->split_k > 1 && a->tile != 4 && a->tile != 6 && !wscale) {
     const NormFuse nf{gamma, eps, (unsigned short*)xn, ld_xn};
     return gemm_impl(a, stream, nullptr, &nf);
   }
   // (Round 4 tried running this norm inside the skinny launch, in the block that draws the last of one ticket per block — correct,
   // and 6-8 us SLOWER per call than the second launch inside a HIP graph: the device-scope release fence in front of the ticket
   // is an L2 write-back; tools/skinny_tail_time.py)
-  const int rc = gemm_impl(a, stream, nullptr);            // no slabs to reduce: the GEMM's own epilogue, then the plain norm
+  const int rc = gemm_impl(a, stream, nullptr, nullptr, wscale);   // no slabs to reduce: the GEMM's own epilogue, then the plain norm
   if (rc != ICL_OK) return rc;
 #ifndef ICL_SMALL_M_BLOCKNORM
 #define ICL_SMALL_M_BLOCKNORM 1   // round 4: 58.7 -> 56.7 ms per utterance at one sequence (tools/ab_bench_b1.sh, profiles/r04_skinny_tail_ab.txt)
@@ -904,7 +1111,22 @@ extern "C" int icl_gemm_rmsnorm_bf16(const icl_gemm_args* a, const float* gamma,
   return icl_rmsnorm(a->C, a->ldc, gamma, xn, ld_xn, a->M, a->N, eps, ICL_F32, ICL_BF16, stream);
 }
 
+extern "C" int icl_gemm_rmsnorm_bf16(const icl_gemm_args* a, const float* gamma, float eps, void* xn, int64_t ld_xn, void* stream) {
+  return gemm_rmsnorm_impl(a, nullptr, gamma, eps, xn, ld_xn, stream);
+}
+
 extern "C" int icl_gemm_bf16(const icl_gemm_args* a, void* stream) { return gemm_impl(a, stream, nullptr); }
+
+extern "C" int icl_gemm_fp8w(const icl_gemm_args* a, const float* w_scale, void* stream) {
+  ICL_CHECK_ARG(w_scale, "icl_gemm_fp8w: w_scale is NULL");
+  return gemm_impl(a, stream, nullptr, nullptr, w_scale);
+}
+
+extern "C" int icl_gemm_rmsnorm_fp8w(const icl_gemm_args* a, const float* w_scale, const float* gamma, float eps, void* xn,
+                                     int64_t ld_xn, void* stream) {
+  ICL_CHECK_ARG(w_scale, "icl_gemm_rmsnorm_fp8w: w_scale is NULL");
+  return gemm_rmsnorm_impl(a, w_scale, gamma, eps, xn, ld_xn, stream);
+}
 
 extern "C" int icl_gemm_rope_kv_bf16(const icl_gemm_args* a, int64_t k_off, int64_t v_off, const float* cosT,
                                      const float* sinT, const int32_t* pos, const int32_t* seq_ids, void* kcache,
@@ -942,5 +1164,31 @@ extern "C" int icl_pack_decode_weights(const void* W, int64_t ldw, int32_t N, in
   const int blocks = (int)std::min<int64_t>((pieces + 255) / 256, 65535);
   hipLaunchKernelGGL(pack_decode_w_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)W, ldw, N, K, (u32x4*)out);
   ICL_CHECK_LAUNCH("icl_pack_decode_weights");
+  return ICL_OK;
+}
+
+extern "C" int icl_pack_fp8_weights(const void* W, int64_t ldw, int32_t N, int32_t K, void* q, float* scales, void* w_deq,
+                                    int64_t ld_deq, void* stream) {
+  ICL_CHECK_ARG(W && q && scales && w_deq && N > 0 && K > 0, "icl_pack_fp8_weights: bad arguments");
+  ICL_CHECK_ARG(K % 64 == 0 && ldw % 8 == 0 && ldw >= K && ld_deq % 8 == 0 && ld_deq >= K,
+                "icl_pack_fp8_weights: K=%d must be a multiple of 64, ldw=%lld / ld_deq=%lld multiples of 8 and >= K", K, (long long)ldw,
+                (long long)ld_deq);
+  ICL_CHECK_ARG((((uintptr_t)W | (uintptr_t)q | (uintptr_t)w_deq) & 15) == 0, "icl_pack_fp8_weights: misaligned pointer");
+  ICL_CHECK_ARG(w_deq == W ? ld_deq == ldw : true, "icl_pack_fp8_weights: in place needs ld_deq == ldw");
+  const int tiles = (N + 15) >> 4;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(pack_fp8_w_kernel, dim3(tiles), dim3(256), 0, s, (const unsigned short*)W, ldw, N, K, (u32x4*)q, scales,
+                     (unsigned short*)w_deq, ld_deq);
+  ICL_CHECK_LAUNCH("icl_pack_fp8_weights");
+  // a load-time call: it waits for its scales to report a non-finite weight (a NaN scale marks the row) as ICL_EINVAL
+  std::vector<float> sc_host(N);
+  hipError_t e = hipMemcpyAsync(sc_host.data(), scales, sizeof(float) * (size_t)N, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    icl_set_error("icl_pack_fp8_weights: %s", hipGetErrorString(e));
+    return ICL_ELAUNCH;
+  }
+  for (int n = 0; n < N; ++n)
+    ICL_CHECK_ARG(sc_host[n] == sc_host[n], "icl_pack_fp8_weights: row %d holds a non-finite value", n);
   return ICL_OK;
 }

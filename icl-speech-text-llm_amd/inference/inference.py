@@ -98,6 +98,9 @@ def parse_args(argv=None):
     p.add_argument("--synthetic_items", type=int, default=64, help="items per task of the synthetic dataset")
     p.add_argument("--arch", type=str, default=None, help="7b | 13b | tiny (default: inferred from llama_path)")
     p.add_argument("--max_new_tokens", type=int, default=10)
+    p.add_argument("--llm_weights", type=str, default="bf16", choices=["bf16", "fp8"],
+                   help="decoder GEMM weights: bf16, or fp8 = the opt-in FP8 weight mode (each weight replaced by its FP8 rounding; "
+                        "decode at <= 8 rows streams half the bytes)")
     return p.parse_args(argv)
 
 
@@ -208,6 +211,8 @@ def run_inference(args) -> Dict[str, Any]:
         model_args = dict(config.get("model_args", {}))
         if args.arch:
             model_args["arch"] = args.arch
+        if getattr(args, "llm_weights", "bf16") != "bf16":
+            model_args["llm_weight_dtype"] = args.llm_weights
         model = ModelFactory.create_model(model_type=args.model_type, multi_task=False, device=args.device,
                                           low_resource=True, **model_args)
         if args.peft_model_path and args.peft_model_path.strip():

@@ -57,6 +57,8 @@ def setup_model(args):
     model_args = dict(config.get("model_args", {}))
     if getattr(args, "arch", None):
         model_args["arch"] = args.arch
+    if getattr(args, "llm_weights", "bf16") != "bf16":      # a caller's namespace may ask for the FP8 weight mode (no flag: the
+        model_args["llm_weight_dtype"] = args.llm_weights   # interactive CLI's flag set mirrors the reference's plus three)
     if str(args.device).startswith("cuda"):
         idx = int(str(args.device).split(":")[1]) if ":" in str(args.device) else 0
         args.device = f"cuda:{idx}"

@@ -23,7 +23,7 @@ from ..runtime import synth
 from ..runtime.config import QwenAudioCfg
 from ..utils.tokenization import ByteTokenizer, Encoding
 from .base_model import BaseModel
-from .custom_salmon import PackedTreeModule
+from .custom_salmon import PackedTreeModule, check_llm_weight_dtype
 
 logger = logging.getLogger(__name__)
 
@@ -53,9 +53,10 @@ def _read_generation_config(model_path) -> Dict[str, Any]:
 class QwenModule(PackedTreeModule):
     """Parameter tree under HF Qwen2-Audio key names + the packed HIP runtime built from it on first use."""
 
-    def __init__(self, cfg: QwenAudioCfg, device, seed: int = 0):
+    def __init__(self, cfg: QwenAudioCfg, device, seed: int = 0, llm_weight_dtype: str = "bf16"):
         super().__init__()
         self.cfg = cfg
+        self.llm_weight_dtype = check_llm_weight_dtype(llm_weight_dtype)
         self._init_tree(device, synth.qwen_audio_state(cfg, seed=seed, device=torch.device(device), dtype=torch.bfloat16))
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
@@ -69,7 +70,7 @@ class QwenModule(PackedTreeModule):
 
     def _build_runtime(self):
         from ..runtime.qwen import QwenAudioRuntime
-        return QwenAudioRuntime(self.cfg, self.state_dict(), device=self._device)
+        return QwenAudioRuntime(self.cfg, self.state_dict(), device=self._device, llm_weight_dtype=self.llm_weight_dtype)
 
 
 class QwenSpecialTokenizer(ByteTokenizer):
@@ -183,15 +184,18 @@ class CustomQwen(BaseModel):
     def __init__(self, model_path: str = "Qwen/Qwen2-Audio-7B-Instruct", lora: bool = True, low_resource: bool = True,
                  lora_rank: int = 8, lora_alpha: int = 32, lora_dropout: float = 0.05, prompt_template: str = "",
                  max_txt_len: int = 512, ckpt_path: Optional[str] = None, device=None, use_fp16: bool = True,
-                 arch=None, tokenizer=None, seed: int = 0, generation_config: Optional[Dict[str, Any]] = None, **ignored):
+                 arch=None, tokenizer=None, seed: int = 0, generation_config: Optional[Dict[str, Any]] = None,
+                 llm_weight_dtype: str = "bf16", **ignored):
         super().__init__(device=device, use_fp16=use_fp16)
+        check_llm_weight_dtype(llm_weight_dtype)      # "fp8": the opt-in FP8 weight mode of the decoder (never implied by low_resource)
         if ignored:
             logger.info("CustomQwen: ignoring unknown kwargs %s", sorted(ignored))
         from dataclasses import replace
         cfg = arch if isinstance(arch, QwenAudioCfg) else (QwenAudioCfg.tiny(lora=lora) if arch == "tiny" else QwenAudioCfg())
         cfg = replace(cfg, llm=replace(cfg.llm, lora_rank=lora_rank if lora else 0, lora_alpha=float(lora_alpha)))
         self.cfg = cfg
-        self.model = QwenModule(cfg, self.device, seed=seed)
+        self.llm_weight_dtype = llm_weight_dtype
+        self.model = QwenModule(cfg, self.device, seed=seed, llm_weight_dtype=llm_weight_dtype)
         if ckpt_path and os.path.isfile(ckpt_path):
             ckpt = torch.load(ckpt_path, map_location="cpu")
             self.model.load_state_dict(ckpt.get("model", ckpt), strict=False)

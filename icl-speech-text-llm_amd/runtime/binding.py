@@ -18,7 +18,7 @@ LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libicl_hip.so"))
 
 ICL_BF16, ICL_F32 = 0, 1
 EPI_BIAS, EPI_GELU, EPI_RESIDUAL, EPI_SWIGLU = 1, 2, 4, 8
-ABI_VERSION = 5
+ABI_VERSION = 6
 SAMPLE_TOP_K_MAX = 1024      # SAMPLE_CAP of csrc/sampling.hip: candidate-list size of icl_sample_eos
 
 
@@ -76,6 +76,9 @@ _SIGNATURES = {
     "icl_gemm_rope_kv_bf16": (c_int, [POINTER(GemmArgs), c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "icl_pack_decode_weights": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "icl_pack_fp8_weights": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "icl_gemm_fp8w": (c_int, [POINTER(GemmArgs), c_void_p, c_void_p]),
+    "icl_gemm_rmsnorm_fp8w": (c_int, [POINTER(GemmArgs), c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p]),
     "icl_embed_gather_interleave": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                             c_int32, c_int32, c_void_p]),
     "icl_argmax_eos": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
@@ -178,19 +181,23 @@ def _require_gpu(*tensors):
 # ------------------------------------------------------------------------------------------------
 def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, residual=None, gelu=False,
          swiglu=False, split_k: int = 1, workspace=None, tile: int = 0, M=None, K=None, lda=None,
-         batch: int = 1, stride_a: int = 0, stride_c: int = 0, stride_r: int = 0, rope=None, N=None) -> torch.Tensor:
+         batch: int = 1, stride_a: int = 0, stride_c: int = 0, stride_r: int = 0, rope=None, N=None, w_scale=None) -> torch.Tensor:
     """out = epilogue(a @ w.T).  a: bf16 [M,K] (row stride lda), w: bf16 [N,K], out: bf16|f32 [M,N'].
+
+    ``w_scale`` (f32 [N]): ``w`` is the fp8 decode-packed copy of ``pack_fp8_weights`` and the product is taken with
+    W' = q * w_scale on the fp8-weight skinny kernel (icl_gemm_fp8w: M <= 64; ``tile`` is ignored, ``N`` and ``K`` are required).
 
     ``rope`` = (k_off, v_off, cos, sin, pos, seq_ids, kcache, vcache, n_heads, head_dim, max_len[, kv_rows_to_c]) runs the QKV projection
     with RoPE + KV-cache append fused into its epilogue (icl_gemm_rope_kv_bf16; see ``rope_fusable``)."""
     _require_gpu(a, w, out, bias, residual, workspace)
     lib = load_library()
     g = GemmArgs()
+    _require_gpu(w_scale)
     N = w.shape[0] if N is None else N      # tile 5 takes the decode-packed copy (rows padded to 16): pass the true N
     g.A, g.W, g.C = a.data_ptr(), w.data_ptr(), out.data_ptr()
     g.bias, g.R, g.workspace = _ptr(bias), _ptr(residual), _ptr(workspace)
     g.lda = a.stride(-2) if lda is None else lda
-    g.ldw = w.stride(0)
+    g.ldw = w.stride(0) if w_scale is None else w.shape[1]
     g.ldc = out.stride(-2)
     g.ldr = residual.stride(-2) if residual is not None else 0
     g.strideA, g.strideC, g.strideR = stride_a, stride_c, stride_r
@@ -212,9 +219,12 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, resi
     g.out_dtype = _dt(out)
     g.res_dtype = _dt(residual) if residual is not None else ICL_F32
     g.split_k = split_k
-    if tile == 0:  # resolve the library's auto choice here so a profiler hook knows which kernel ran
+    if w_scale is not None:
+        assert w.dtype == torch.uint8 and w_scale.dtype == torch.float32 and rope is None
+        tile = "fp8w"                # the profiler hook's label; the library ignores args.tile here
+    elif tile == 0:  # resolve the library's auto choice here so a profiler hook knows which kernel ran
         tile = lib.icl_gemm_select_tile(g.M, N, g.K, batch, split_k)
-    g.tile = tile
+    g.tile = tile if w_scale is None else 0
     if split_k > 1 and workspace is not None:
         assert workspace.dtype == torch.float32 and workspace.numel() >= split_k * g.M * N
     if rope is not None:
@@ -226,6 +236,9 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, resi
             _check(lib.icl_gemm_rope_kv_bf16(ctypes.byref(g), k_off, v_off, cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
                                              _ptr(seq_ids), _ptr(kcache), _ptr(vcache), n_heads, head_dim, max_len,
                                              kv_rows_to_c, _stream()), "icl_gemm_rope_kv_bf16")
+    elif w_scale is not None:
+        def launch():
+            _check(lib.icl_gemm_fp8w(ctypes.byref(g), w_scale.data_ptr(), _stream()), "icl_gemm_fp8w")
     else:
         def launch():
             _check(lib.icl_gemm_bf16(ctypes.byref(g), _stream()), "icl_gemm_bf16")
@@ -241,24 +254,30 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, resi
 
 
 def gemm_rmsnorm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, gamma: torch.Tensor, eps: float, xn: torch.Tensor, *,
-                 residual=None, split_k: int = 1, workspace=None, tile: int = 0, N=None, K=None) -> torch.Tensor:
+                 residual=None, split_k: int = 1, workspace=None, tile: int = 0, N=None, K=None, w_scale=None) -> torch.Tensor:
     """out = residual + a @ w.T (f32) and xn[:, :N] = bf16(rmsnorm(out) * gamma): the decode form of a projection back into the
     residual stream followed by the next RMSNorm (icl_gemm_rmsnorm_bf16: with split_k > 1 one kernel reduces, adds, stores and
-    normalises)."""
-    _require_gpu(a, w, out, gamma, xn, residual, workspace)
+    normalises).  ``w_scale``: ``w`` is an fp8 decode-packed copy, as in ``gemm`` (icl_gemm_rmsnorm_fp8w)."""
+    _require_gpu(a, w, out, gamma, xn, residual, workspace, w_scale)
     lib = load_library()
     g = GemmArgs()
     N = w.shape[0] if N is None else N
     g.A, g.W, g.C = a.data_ptr(), w.data_ptr(), out.data_ptr()
     g.bias, g.R, g.workspace = 0, _ptr(residual), _ptr(workspace)
-    g.lda, g.ldw, g.ldc = a.stride(-2), w.stride(0), out.stride(-2)
+    g.lda, g.ldw, g.ldc = a.stride(-2), (w.stride(0) if w_scale is None else w.shape[1]), out.stride(-2)
     g.ldr = residual.stride(-2) if residual is not None else 0
     g.strideA = g.strideC = g.strideR = 0
     g.M, g.N, g.K, g.batch = a.shape[-2], N, (w.shape[1] if K is None else K), 1
     g.epilogue = EPI_RESIDUAL if residual is not None else 0
     g.out_dtype, g.res_dtype, g.split_k = _dt(out), ICL_F32, split_k
-    g.tile = tile if tile else lib.icl_gemm_select_tile(g.M, N, g.K, 1, split_k)
     assert out.dtype == torch.float32 and xn.dtype == torch.bfloat16 and gamma.dtype == torch.float32
+    if w_scale is not None:
+        assert w.dtype == torch.uint8 and w_scale.dtype == torch.float32
+        g.tile = 0
+        _check(lib.icl_gemm_rmsnorm_fp8w(ctypes.byref(g), w_scale.data_ptr(), gamma.data_ptr(), eps, xn.data_ptr(), xn.stride(0),
+                                         _stream()), "icl_gemm_rmsnorm_fp8w")
+        return out
+    g.tile = tile if tile else lib.icl_gemm_select_tile(g.M, N, g.K, 1, split_k)
     if split_k > 1 and workspace is not None:
         assert workspace.dtype == torch.float32 and workspace.numel() >= split_k * g.M * N
     _check(lib.icl_gemm_rmsnorm_bf16(ctypes.byref(g), gamma.data_ptr(), eps, xn.data_ptr(), xn.stride(0), _stream()),
@@ -275,6 +294,24 @@ def pack_decode_weights(w: torch.Tensor, K=None) -> torch.Tensor:
     _check(load_library().icl_pack_decode_weights(w.data_ptr(), w.stride(0), N, K, out.data_ptr(), _stream()),
            "icl_pack_decode_weights")
     return out
+
+
+def pack_fp8_weights(w: torch.Tensor, K=None, out=None):
+    """FP8 weight mode (icl_pack_fp8_weights): row-major bf16 w [N, >=K] -> (q, scales, w_deq).  q: uint8 [ceil(N/16)*16, K], the
+    fp8 decode-packed copy for ``gemm(..., w_scale=scales, N=N, K=K)``; scales: f32 [N] = 2^e_n; w_deq: bf16 W' = q * 2^e_n written
+    into ``out`` (``out=w`` rewrites w in place; default: a new [N, K] tensor).  Waits for the GPU: raises IclError on a NaN or an
+    infinity in w."""
+    _require_gpu(w, out)
+    assert w.dtype == torch.bfloat16 and w.dim() == 2
+    N, K = w.shape[0], (w.shape[1] if K is None else K)
+    q = torch.empty((N + 15) // 16 * 16, K, dtype=torch.uint8, device=w.device)
+    scales = torch.empty(N, dtype=torch.float32, device=w.device)
+    if out is None:
+        out = torch.empty(N, K, dtype=torch.bfloat16, device=w.device)
+    assert out.dtype == torch.bfloat16 and out.shape[0] == N and out.shape[1] >= K and out.stride(1) == 1
+    _check(load_library().icl_pack_fp8_weights(w.data_ptr(), w.stride(0), N, K, q.data_ptr(), scales.data_ptr(), out.data_ptr(),
+                                               out.stride(0), _stream()), "icl_pack_fp8_weights")
+    return q, scales, out
 
 
 def rope_fusable(M: int, n_heads: int, head_dim: int, K: int) -> bool:

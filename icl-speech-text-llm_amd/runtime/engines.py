@@ -409,17 +409,41 @@ class LlamaHIP:
         split = min(K // 512, int(0.8 * self.n_cu) // tiles)
         return split if split >= 2 and tiles * split >= 0.45 * self.n_cu else 0
 
-    def __init__(self, w: PackedLlama, device, decode_packed: Optional[bool] = None, pack_now: bool = True):
+    def __init__(self, w: PackedLlama, device, decode_packed: Optional[bool] = None, pack_now: bool = True,
+                 weight_dtype: str = "bf16"):
         """``decode_packed`` (default: the class attribute): keep a second, decode-packed layout of the layer weights (+12.9 GB
         at 7B, +25 GB at 13B).  ``pack_now=False`` defers the copy to the first decode step — forward-only users
-        (``forward_logits`` / loss) then never pay for it; the default packs at load time, not inside a caller's first batch."""
+        (``forward_logits`` / loss) then never pay for it; the default packs at load time, not inside a caller's first batch.
+
+        ``weight_dtype="fp8"``: the opt-in FP8 weight mode (include/icl_hip.h, icl_pack_fp8_weights).  Every packed decoder GEMM
+        weight (wqkv with its LoRA columns, wo, wgu, wdown) is replaced by its FP8 rounding W' (bf16) and gets an fp8 decode-packed
+        copy + row scales, made here on the GPU; prefill, ``forward_logits`` and decode above 8 rows run the bf16 kernels on W'
+        (the bf16 decode-packed copy is then made on first use), decode at <= 8 rows streams the fp8 copy (icl_gemm_fp8w: the
+        same bits as tile 6 on W', half the bytes)."""
+        if weight_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', not {weight_dtype!r}")
         self.w = w
         self.device = torch.device(device)
         self.n_cu = max(B.device_cu_count(), 1)
+        self.weight_dtype = weight_dtype
         if decode_packed is not None:
             self.decode_packed_weights = bool(decode_packed)
-        if self.decode_packed_weights and pack_now:
+        if weight_dtype == "fp8":
+            self._quantize_fp8()
+        elif self.decode_packed_weights and pack_now:
             self.ensure_decode_packed()
+
+    def _quantize_fp8(self):
+        """W -> W' (new bf16 tensors: wo / wdown may share storage with the caller's checkpoint image) + L.fp8 = ((q, scales) x 4)."""
+        c = self.w.cfg
+        for L in self.w.layers:
+            packs = []
+            for name, K in (("wqkv", self.w.k_aug), ("wo", c.hidden), ("wgu", c.hidden), ("wdown", c.ffn)):
+                q, s, wd = B.pack_fp8_weights(getattr(L, name), K=K)
+                setattr(L, name, wd)
+                packs.append((q, s))
+            L.fp8 = tuple(packs)
+            L.decode_packed = None
 
     def ensure_decode_packed(self):
         """Decode-packed copies of the layer weights (second layout of the same bytes: +12.9 GB at 7B, +25 GB at 13B)."""
@@ -455,7 +479,13 @@ class LlamaHIP:
             return sk.get("tile_" + name, sk.get("tile", 0))
 
         def weight_of(name, idx, row_major):       # the decode tiles (5 / 6) stream the decode-packed copy, every other tile the original
-            return L.decode_packed[idx] if tile_of(name) in (5, 6) else row_major
+            t = tile_of(name)
+            if t == "fp8w":                        # FP8 weight mode, <= 8 rows: the fp8 decode-packed copy (+ its scales, scale_of)
+                return L.fp8[idx][0]
+            return L.decode_packed[idx] if t in (5, 6) else row_major
+
+        def scale_of(name, idx):
+            return L.fp8[idx][1] if tile_of(name) == "fp8w" else None
         nsplit = max([v for k, v in sk.items() if not k.startswith("tile")], default=1)
         wsk = ws.get(tag + "splitk", (nsplit * M * max(3 * hd, 2 * I),), F32) if nsplit > 1 else None
         if not xn_ready:
@@ -475,26 +505,26 @@ class LlamaHIP:
                    rope=(hd, 2 * hd, w.rope_cos, w.rope_sin, pos, seq_ids, kc, vc, H, D, max_len, kv_rows_to_c))
         else:
             B.gemm(xn, weight_of("qkv", 0, L.wqkv), qkv, bias=L.bqkv, split_k=sk.get("qkv", 1),
-                   workspace=wsk, tile=tile_of("qkv"), N=3 * hd, K=w.k_aug)
+                   workspace=wsk, tile=tile_of("qkv"), N=3 * hd, K=w.k_aug, w_scale=scale_of("qkv", 0))
             if not attn_does_rope:      # decode: RoPE + cache append run inside the attention launch (icl_attn_decode_rope_bf16)
                 B.rope_kv(qkv, hd, 2 * hd, w.rope_cos, w.rope_sin, pos, seq_ids, kc, vc, H, D, max_len, M=M)
         attn_fn(qkv, att)
         fuse = split is not None and self.fuse_decode_norms
         if fuse:     # decode: h += att Wo^T and the post-attention RMSNorm in one call (one kernel when the GEMM is split-K)
             B.gemm_rmsnorm(att, weight_of("o", 1, L.wo), h, L.rms2, c.rms_eps, xn, residual=h, split_k=sk.get("o", 1),
-                           workspace=wsk, tile=tile_of("o"), N=hd, K=hd)
+                           workspace=wsk, tile=tile_of("o"), N=hd, K=hd, w_scale=scale_of("o", 1))
         else:
             B.gemm(att, weight_of("o", 1, L.wo), h, residual=h, split_k=sk.get("o", 1), workspace=wsk, tile=tile_of("o"),
-                   N=hd, K=hd)
+                   N=hd, K=hd, w_scale=scale_of("o", 1))
             B.rmsnorm(h, L.rms2, xn, c.rms_eps, N=hd)
         B.gemm(xn, weight_of("gu", 2, L.wgu), act, swiglu=True, K=hd, split_k=sk.get("gu", 1), workspace=wsk,
-               tile=tile_of("gu"), N=2 * I)
+               tile=tile_of("gu"), N=2 * I, w_scale=scale_of("gu", 2))
         if fuse and next_norm is not None:
             B.gemm_rmsnorm(act, weight_of("down", 3, L.wdown), h, next_norm[0], c.rms_eps, next_norm[1], residual=h,
-                           split_k=sk.get("down", 1), workspace=wsk, tile=tile_of("down"), N=hd, K=I)
+                           split_k=sk.get("down", 1), workspace=wsk, tile=tile_of("down"), N=hd, K=I, w_scale=scale_of("down", 3))
             return True
         B.gemm(act, weight_of("down", 3, L.wdown), h, residual=h, split_k=sk.get("down", 1), workspace=wsk,
-               tile=tile_of("down"), N=hd, K=I)
+               tile=tile_of("down"), N=hd, K=I, w_scale=scale_of("down", 3))
         return False
 
     # ---- K10: prefill over ragged packed sequences ------------------------------------------------
@@ -564,7 +594,9 @@ class LlamaHIP:
 
         def sk5(N, K):
             return max(1, min(self.n_cu // ((N + 127) // 128), K // 512))
-        if Bn <= 256 and self.decode_packed_weights:
+        if Bn <= 8 and self.weight_dtype == "fp8":
+            split = dict(tile="fp8w")    # FP8 weight mode: the fp8-weight skinny kernel (tile 6's arithmetic on W', half the bytes)
+        elif Bn <= 256 and self.decode_packed_weights:
             self.ensure_decode_packed()
             if Bn <= 8:
                 split = dict(tile=6)

@@ -264,6 +264,7 @@ class LlamaLayer:
     wgu: torch.Tensor            # [2*ffn, h] interleaved in blocks of 16
     wdown: torch.Tensor
     decode_packed: Optional[tuple] = None   # (wqkv, wo, wgu, wdown) in the M <= 128 decode tile's layout, made on first use
+    fp8: Optional[tuple] = None             # FP8 weight mode: ((q, scales) of wqkv, wo, wgu, wdown), LlamaHIP(weight_dtype="fp8")
 
 
 @dataclass

@@ -39,7 +39,8 @@ def normalize_qwen_keys(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
 
 
 class QwenAudioRuntime(CausalLMRuntimeMixin):
-    def __init__(self, cfg: QwenAudioCfg, state_dict: Dict[str, torch.Tensor], device="cuda", consume: bool = False):
+    def __init__(self, cfg: QwenAudioCfg, state_dict: Dict[str, torch.Tensor], device="cuda", consume: bool = False,
+                 llm_weight_dtype: str = "bf16"):
         if not torch.cuda.is_available():
             raise B.IclError("QwenAudioRuntime needs a GPU: the HIP path has no CPU fallback")
         B.load_library()
@@ -51,7 +52,8 @@ class QwenAudioRuntime(CausalLMRuntimeMixin):
         enc = WhisperEncoderHIP(pack_whisper(sd, cfg.audio, self.device, prefix="audio_tower.", consume=consume))
         self.tower = QwenAudioTowerHIP(enc, _bf(_take(sd, "multi_modal_projector.linear.weight", consume), self.device),
                                        _f32(_take(sd, "multi_modal_projector.linear.bias", consume), self.device), cfg.llm.hidden)
-        self.llama = LlamaHIP(pack_llama(sd, cfg.llm, self.device, prefix="language_model.", consume=consume), self.device)
+        self.llama = LlamaHIP(pack_llama(sd, cfg.llm, self.device, prefix="language_model.", consume=consume), self.device,
+                              weight_dtype=llm_weight_dtype)
         self._graphs, self._graph_warm, self._graph_gen = {}, set(), 0
 
     # ---- K13 ---------------------------------------------------------------------------------------

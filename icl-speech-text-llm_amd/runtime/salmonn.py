@@ -408,7 +408,7 @@ class CausalLMRuntimeMixin:
 
 class SalmonnRuntime(CausalLMRuntimeMixin):
     def __init__(self, cfg: SalmonnCfg, state_dict: Dict[str, torch.Tensor], device="cuda", consume: bool = False,
-                 parts: Sequence[str] = ("whisper", "beats", "qformer", "llama")):
+                 parts: Sequence[str] = ("whisper", "beats", "qformer", "llama"), llm_weight_dtype: str = "bf16"):
         if not torch.cuda.is_available():
             raise B.IclError("SalmonnRuntime needs a GPU: the HIP path has no CPU fallback")
         B.load_library()
@@ -428,7 +428,8 @@ class SalmonnRuntime(CausalLMRuntimeMixin):
                                             cfg.whisper.d_model, cfg.beats.d_model if self.beats is not None else 0,
                                             cfg.llama.hidden)
         if "llama" in parts:
-            self.llama = LlamaHIP(pack_llama(sd, cfg.llama, self.device, consume=consume), self.device)
+            self.llama = LlamaHIP(pack_llama(sd, cfg.llama, self.device, consume=consume), self.device,
+                                  weight_dtype=llm_weight_dtype)
         self._graphs, self._graph_warm, self._graph_gen = {}, set(), 0
 
     # --------------------------------------------------------------------------------------------

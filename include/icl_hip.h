@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ICL_ABI_VERSION 5
+#define ICL_ABI_VERSION 6
 
 /* error codes */
 #define ICL_OK 0
@@ -109,6 +109,30 @@ int icl_gemm_rmsnorm_bf16(const icl_gemm_args* args, const float* gamma, float e
  * decode kernel's wave-loads are 1 KB contiguous (rows >= N are zero).  A layout copy made once at load time (the
  * prefill kernels keep reading the row-major original: HBM is sized for both); no reference counterpart. */
 int icl_pack_decode_weights(const void* W, int64_t ldw, int32_t N, int32_t K, void* out, void* stream);
+/* ---- K11 (opt-in FP8 weight mode): fp8-weight decode GEMM ---------------------------------
+ * The decoder's GEMM weights replaced by their FP8 rounding W' = q * 2^e_n (row n): e_n is the smallest integer with
+ * max_k |W[n][k]| <= 448 * 2^e_n (0 for an all-zero row), q[n][k] = W[n][k] / 2^e_n rounded to nearest even in OCP e4m3fn (exact
+ * division, never saturated).  W' is exactly representable in bf16.  An MI355X-native option, not a restatement: the reference
+ * loads its Llama in 8 bits (bitsandbytes LLM.int8, low_resource=True: inference/inference.py:151, models/custom_salmon.py:49,82)
+ * for its batch-1 CLI runs; this mode has its own, exactly defined numerics above.
+ *
+ * icl_pack_fp8_weights: row-major bf16 W [N][ldw] -> q (ceil(N/16)*16 * K bytes, fp8 decode-packed: per 16-row block a K-long
+ * stream of 1-KB pieces, piece (block, k-pair j, lane = fq*16 + fr) = q[16*block + fr][64j + 8fq .. +8] ++ q[..][64j + 32 + 8fq .. +8];
+ * rows >= N are zero), scales f32 [N] = 2^e_n, and W' written as bf16 into w_deq [N][ld_deq] (w_deq == W with ld_deq == ldw
+ * rewrites W in place).  K % 64 == 0; W, q, w_deq 16-byte aligned.  A load-time call and the one exception to "nothing
+ * synchronises": it waits for its stream to return ICL_EINVAL when W holds a NaN or an infinity (q / w_deq are then undefined).
+ *
+ * icl_gemm_fp8w / icl_gemm_rmsnorm_fp8w: icl_gemm_bf16 / icl_gemm_rmsnorm_bf16 with args->W = the q of icl_pack_fp8_weights
+ * (ldw and tile are ignored) and w_scale = its scales, for M <= 64, batch 1.  The skinny decode kernel (tile 6's block shape,
+ * per-wave K split, MFMA order and wave-ordered combine) rebuilds W' in registers (fp8 -> f32 -> * 2^e_n -> bf16, all exact) and
+ * returns the same bits as tile 6 on the decode-packed copy of W' — every epilogue (bias, SwiGLU, residual) and the RMSNorm
+ * pairing included — while reading half the weight bytes.  No reference counterpart (the reference's 8-bit layers are
+ * bitsandbytes matmuls behind HF LlamaForCausalLM, reached from models/custom_salmon.py:704-720). */
+int icl_pack_fp8_weights(const void* W, int64_t ldw, int32_t N, int32_t K, void* q, float* scales, void* w_deq, int64_t ld_deq,
+                         void* stream);
+int icl_gemm_fp8w(const icl_gemm_args* args, const float* w_scale, void* stream);
+int icl_gemm_rmsnorm_fp8w(const icl_gemm_args* args, const float* w_scale, const float* gamma, float eps, void* xn, int64_t ld_xn,
+                          void* stream);
 /* The tile id (1|2|3) that tile == 0 resolves to for this problem (pure host function). */
 int icl_gemm_select_tile(int32_t M, int32_t N, int32_t K, int32_t batch, int32_t split_k);
 
