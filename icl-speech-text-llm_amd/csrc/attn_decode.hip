@@ -12,31 +12,70 @@ constexpr float NEG_BIG = -1.0e30f;
 constexpr float LOG2E = 1.4426950408889634f;
 
 // UNR = key rounds (4 * KPW keys each) whose K and V loads are issued before the first of them is consumed.  A stream's keys and
-// their order do not depend on it, so the result is bit-identical for any UNR: few workgroups (a small decode batch: one block
-// per (sequence, head), nothing else on the CU to hide a 2-3 us round trip per loop iteration) take 16, a full chip takes 4.
+// their order do not depend on it: few workgroups (a small decode batch: one block per (sequence, head), nothing else on the CU to
+// hide a 2-3 us round trip per loop iteration) take the deep unroll, a full chip 4.  (The instruction selection, and so FMA
+// contraction, can differ between unrolls; instantiations compared bit for bit below use the same UNR.)
 // FUSE (icl_attn_decode_rope_bf16): the step's RoPE + cache append run HERE instead of in a launch of their own (rope_kv_kernel:
 // ~5 us per layer at any decode batch, one of the nine launches of a one-sequence decode layer).  Q holds the projection's raw
 // q | k | v row of sequence b; every lane rotates the q chunk it needs (and the new key's chunk) with rope_rot8 — the function and
 // the bf16 rounding points of rope_kv_kernel, so the result is bit-identical to the two launches — the first LPR lanes append the
 // rotated key and the value to the cache at position pos[b], and in the key loop position pos[b] is served from registers, never
 // from the cache line that is being written.
+// EPL = elements of a key row per lane (LPR = D / EPL lanes per row).  The bf16 kernel takes 8 (one 16-B load).
+// F8 (icl_attn_decode_fp8 / icl_attn_decode_rope_fp8): the cache holds e4m3fn bytes and one f32 scale 2^e per row (include/icl_hip.h,
+// "FP8 KV cache").  A lane takes EPL = 16 elements — one 16-B load, so 8 lanes cover a 128-B row and a wave-instruction still
+// reads 1 KiB — plus the row's scale, and rebuilds x' = q * 2^e as the bf16 words a bf16 cache holding x' would hold (exact) before
+// the arithmetic (kv_words): fed f32 directly, the compiler contracts the dot products into FMAs differently than for bf16 words.
+// So the output is bit-identical to the bf16 instantiation with EPL = 16 (icl_attn_decode_bf16_epl16, a reference entry point) on
+// a bf16 cache of x'; against the production EPL = 8 kernel only the order of the d-chunk partial sums of each score differs.
+// FUSE rounds the appended key and value to x' in registers (kv_fp8_quant: the row maximum is a shuffle over the row's LPR lanes)
+// and serves the rounded row.
 struct DecodeRope {
   const float* cosT;
   const float* sinT;
   const int* pos;
   const int* seq_ids;     // cache row of sequence b (NULL: b)
-  unsigned short* kc;     // the caches, writable (Kc / Vc of the kernel are these)
-  unsigned short* vc;
+  void* kc;               // the caches, writable (Kc / Vc of the kernel are these)
+  void* vc;
+  float* ks;              // F8: the row scales of kc / vc (Ks / Vs of the kernel)
+  float* vs;
   int64_t k_off, v_off;   // column offsets of k / v in the qkv row
 };
 
-template <int D, int UNR, bool FUSE>
-__global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* Q, int64_t ldq,
-                                                           const unsigned short* Kc, const unsigned short* Vc,
-                                                           unsigned short* O, int64_t ldo, const int* lens,
-                                                           int n_heads, int max_len, float scale_log2e, DecodeRope rp) {
-  constexpr int LPR = D / 8;     // lanes per key row
-  constexpr int KPW = 64 / LPR;  // keys per wave-instruction
+template <int EPL> struct KvWords;                       // EPL bf16 of a lane: EPL / 2 dwords
+template <> struct KvWords<8> { typedef u32x4 T; };
+template <> struct KvWords<16> { typedef u32x8 T; };
+template <bool F8, int EPL> struct KvRaw { typedef typename KvWords<EPL>::T T; };   // a lane's cache bytes: bf16 words ...
+template <> struct KvRaw<true, 16> { typedef u32x4 T; };                              // ... or 16 e4m3fn codes
+
+// a lane's EPL cache elements as bf16 words (F8: x' = q * sc, exact in bf16)
+template <bool F8, int EPL>
+__device__ __forceinline__ typename KvWords<EPL>::T kv_words(typename KvRaw<F8, EPL>::T r, float sc) {
+  if constexpr (F8) {
+    const unsigned qs[4] = {r[0], r[1], r[2], r[3]};
+    float f[16];
+    kv_fp8_deq<4>(qs, sc, f);
+    typename KvWords<EPL>::T w;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) w[t] = pack_bf16x2(f[2 * t], f[2 * t + 1]);
+    return w;
+  } else {
+    return r;
+  }
+}
+
+template <int D, int UNR, bool FUSE, bool F8, int EPL>
+__global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* Q, int64_t ldq, const void* Kc, const void* Vc,
+                                                           const float* Ks, const float* Vs, unsigned short* O, int64_t ldo,
+                                                           const int* lens, int n_heads, int max_len, float scale_log2e,
+                                                           DecodeRope rp) {
+  typedef typename KvRaw<F8, EPL>::T Raw;
+  typedef typename KvWords<EPL>::T Wd;
+  static_assert(!F8 || EPL == 16, "the fp8 cache is read 16 elements per lane");
+  constexpr int NW = EPL / 2;      // bf16 words per lane
+  constexpr int EB = F8 ? 1 : 2;   // bytes per cache element
+  constexpr int LPR = D / EPL;     // lanes per key row
+  constexpr int KPW = 64 / LPR;    // keys per wave-instruction
   constexpr int NSTREAM = 4 * KPW;
   __shared__ float sm[NSTREAM][D + 2];  // per stream: o[D], m, l
   const int h = blockIdx.x, b = blockIdx.y;
@@ -45,61 +84,105 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
   const int len = min(lens[b], max_len);
   const int crow = FUSE && rp.seq_ids ? rp.seq_ids[b] : b;
   const int64_t base = ((int64_t)crow * n_heads + h) * (int64_t)max_len * D;
-  const unsigned short* kp = Kc + base + dc * 8;
-  const unsigned short* vp = Vc + base + dc * 8;
+  const int64_t sbase = base / D;     // F8: the scale of row (crow, h, key) is Ks[sbase + key]
+  const char* kp = (const char*)Kc + (base + dc * EPL) * EB;
+  const char* vp = (const char*)Vc + (base + dc * EPL) * EB;
 
-  u32x4 q_raw, k_new = {0u, 0u, 0u, 0u}, v_new = {0u, 0u, 0u, 0u};
+  Wd q_raw;
+  Raw k_new = {}, v_new = {};
+  float ks_new = 1.f, vs_new = 1.f;
   int pos_new = -1;
   if constexpr (FUSE) {
     constexpr int HALF = D / 2;
     pos_new = rp.pos[b];
-    const int i0 = (dc % (LPR / 2)) * 8;                 // this lane's 8 elements of the low half (its partner chunk: + HALF)
+    const int i0 = (dc % (LPR / 2)) * EPL;               // this lane's elements of the low half (its partner chunk: + HALF)
     const bool is_hi = dc >= LPR / 2;
     const unsigned short* row = Q + (int64_t)b * ldq + h * D;
-    const u32x4 qlo = *(const u32x4*)(row + i0), qhi = *(const u32x4*)(row + i0 + HALF);
-    const u32x4 klo = *(const u32x4*)(row + rp.k_off + i0), khi = *(const u32x4*)(row + rp.k_off + i0 + HALF);
-    v_new = *(const u32x4*)(row + rp.v_off + dc * 8);
-    const float* cp = rp.cosT + (int64_t)pos_new * HALF + i0;
-    const float* sp = rp.sinT + (int64_t)pos_new * HALF + i0;
-    const f32x4 c0 = *(const f32x4*)cp, c1 = *(const f32x4*)(cp + 4), s0 = *(const f32x4*)sp, s1 = *(const f32x4*)(sp + 4);
-    u32x4 olo, ohi;
-    rope_rot8(qlo, qhi, c0, c1, s0, s1, olo, ohi);
-    q_raw = is_hi ? ohi : olo;
-    rope_rot8(klo, khi, c0, c1, s0, s1, olo, ohi);
-    k_new = is_hi ? ohi : olo;
-    if (wave == 0 && sub == 0 && pos_new >= 0 && pos_new < max_len) {   // one lane per 16-B chunk: the appended row
-      *(u32x4*)(rp.kc + base + (int64_t)pos_new * D + dc * 8) = k_new;
-      *(u32x4*)(rp.vc + base + (int64_t)pos_new * D + dc * 8) = v_new;
+    Wd k_row;
+#pragma unroll
+    for (int c = 0; c < EPL / 8; ++c) {                  // 8 elements per rope_rot8
+      const int ic = i0 + 8 * c;
+      const u32x4 qlo = *(const u32x4*)(row + ic), qhi = *(const u32x4*)(row + ic + HALF);
+      const u32x4 klo = *(const u32x4*)(row + rp.k_off + ic), khi = *(const u32x4*)(row + rp.k_off + ic + HALF);
+      const float* cp = rp.cosT + (int64_t)pos_new * HALF + ic;
+      const float* sp = rp.sinT + (int64_t)pos_new * HALF + ic;
+      const f32x4 c0 = *(const f32x4*)cp, c1 = *(const f32x4*)(cp + 4), s0 = *(const f32x4*)sp, s1 = *(const f32x4*)(sp + 4);
+      u32x4 olo, ohi;
+      rope_rot8(qlo, qhi, c0, c1, s0, s1, olo, ohi);
+      const u32x4 qo = is_hi ? ohi : olo;
+      rope_rot8(klo, khi, c0, c1, s0, s1, olo, ohi);
+      const u32x4 ko = is_hi ? ohi : olo;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        q_raw[4 * c + t] = qo[t];
+        k_row[4 * c + t] = ko[t];
+      }
+    }
+    const Wd v_row = *(const Wd*)(row + rp.v_off + dc * EPL);
+    if constexpr (F8) {            // every lane rounds (the row maximum is a shuffle over the row's LPR lanes)
+      unsigned kx[NW], vx[NW], kq[NW / 2], vq[NW / 2];
+#pragma unroll
+      for (int t = 0; t < NW; ++t) {
+        kx[t] = k_row[t];
+        vx[t] = v_row[t];
+      }
+      kv_fp8_quant<LPR, NW>(kx, kq, ks_new);
+      kv_fp8_quant<LPR, NW>(vx, vq, vs_new);
+#pragma unroll
+      for (int t = 0; t < NW / 2; ++t) {
+        k_new[t] = kq[t];
+        v_new[t] = vq[t];
+      }
+    } else {
+      k_new = k_row;
+      v_new = v_row;
+    }
+    if (wave == 0 && sub == 0 && pos_new >= 0 && pos_new < max_len) {   // one lane per chunk: the appended row
+      *(Raw*)((char*)rp.kc + (base + (int64_t)pos_new * D + dc * EPL) * EB) = k_new;
+      *(Raw*)((char*)rp.vc + (base + (int64_t)pos_new * D + dc * EPL) * EB) = v_new;
+      if (F8 && dc == 0) {
+        rp.ks[sbase + pos_new] = ks_new;
+        rp.vs[sbase + pos_new] = vs_new;
+      }
     }
   } else {
-    q_raw = *(const u32x4*)(Q + (int64_t)b * ldq + h * D + dc * 8);
+    q_raw = *(const Wd*)(Q + (int64_t)b * ldq + h * D + dc * EPL);
   }
-  float q[8];
+  float q[EPL];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) {
+  for (int t = 0; t < NW; ++t) {
     q[2 * t] = __uint_as_float(q_raw[t] << 16) * scale_log2e;
     q[2 * t + 1] = __uint_as_float(q_raw[t] & 0xffff0000u) * scale_log2e;
   }
-  float m = NEG_BIG, l = 0.f, o[8];
+  float m = NEG_BIG, l = 0.f, o[EPL];
 #pragma unroll
-  for (int t = 0; t < 8; ++t) o[t] = 0.f;
+  for (int t = 0; t < EPL; ++t) o[t] = 0.f;
 
-  // A stream folds its keys in GROUPS of G = 4 (the same groups whatever UNR is: bit-identical for any UNR): the four scores of
-  // a group are independent dot products, ONE running-maximum update and ONE rescale serve all four, and their exponentials and
-  // the o / l updates are independent again.  The per-key form was one serial chain per key — maximum, two exponentials, nine
-  // dependent FMAs — 24 links deep for a 385-key prompt at one sequence per block (22 us per call at a decode batch of 1).
+  // A stream folds its keys in GROUPS of G = 4 (the same groups whatever UNR is): the four scores of a group are independent dot
+  // products, ONE running-maximum update and ONE rescale serve all four, and their exponentials and the o / l updates are
+  // independent again.  The per-key form was one serial chain per key — maximum, two exponentials, nine dependent FMAs — 24 links
+  // deep for a 385-key prompt at one sequence per block (22 us per call at a decode batch of 1).
   constexpr int G = 4;
   static_assert(UNR % G == 0, "key rounds are consumed in groups of four");
   for (int j0 = wave * KPW; j0 < len; j0 += 4 * KPW * UNR) {
-    u32x4 kr[UNR], vr[UNR];
+    Raw kr[UNR], vr[UNR];
+    float ksr[UNR], vsr[UNR];
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const int key = min(j0 + u * 4 * KPW + sub, len - 1);
-      kr[u] = *(const u32x4*)(kp + (int64_t)key * D);
-      vr[u] = *(const u32x4*)(vp + (int64_t)key * D);
+      kr[u] = *(const Raw*)(kp + (int64_t)key * D * EB);
+      vr[u] = *(const Raw*)(vp + (int64_t)key * D * EB);
+      if constexpr (F8) {
+        ksr[u] = Ks[sbase + key];
+        vsr[u] = Vs[sbase + key];
+      } else {
+        ksr[u] = vsr[u] = 1.f;
+      }
       if (FUSE && key == pos_new) {      // the row this launch appends: from registers (the store above may not have landed)
         kr[u] = k_new;
         vr[u] = v_new;
+        ksr[u] = ks_new;
+        vsr[u] = vs_new;
       }
     }
 #pragma unroll
@@ -109,11 +192,12 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
 #pragma unroll
       for (int i = 0; i < G; ++i) {
         const int u = g * G + i;
+        const Wd kw = kv_words<F8, EPL>(kr[u], ksr[u]);
         float d = 0.f;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          d += q[2 * t] * __uint_as_float(kr[u][t] << 16);
-          d += q[2 * t + 1] * __uint_as_float(kr[u][t] & 0xffff0000u);
+        for (int t = 0; t < NW; ++t) {
+          d += q[2 * t] * __uint_as_float(kw[t] << 16);
+          d += q[2 * t + 1] * __uint_as_float(kw[t] & 0xffff0000u);
         }
 #pragma unroll
         for (int x = 1; x < LPR; x <<= 1) d += __shfl_xor(d, x, 64);
@@ -127,13 +211,16 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
       for (int i = 0; i < G; ++i) pe[i] = ok[i] ? __builtin_amdgcn_exp2f(s[i] - m_new) : 0.f;
       m = m_new;
       l = l * alpha + ((pe[0] + pe[1]) + (pe[2] + pe[3]));
+      Wd vw[G];
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
+      for (int i = 0; i < G; ++i) vw[i] = kv_words<F8, EPL>(vr[g * G + i], vsr[g * G + i]);
+#pragma unroll
+      for (int t = 0; t < NW; ++t) {
         float a0 = o[2 * t] * alpha, a1 = o[2 * t + 1] * alpha;
 #pragma unroll
         for (int i = 0; i < G; ++i) {
-          a0 = fmaf(pe[i], __uint_as_float(vr[g * G + i][t] << 16), a0);
-          a1 = fmaf(pe[i], __uint_as_float(vr[g * G + i][t] & 0xffff0000u), a1);
+          a0 = fmaf(pe[i], __uint_as_float(vw[i][t] << 16), a0);
+          a1 = fmaf(pe[i], __uint_as_float(vw[i][t] & 0xffff0000u), a1);
         }
         o[2 * t] = a0;
         o[2 * t + 1] = a1;
@@ -142,7 +229,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
   }
   const int stream = wave * KPW + sub;
 #pragma unroll
-  for (int t = 0; t < 8; ++t) sm[stream][dc * 8 + t] = o[t];
+  for (int t = 0; t < EPL; ++t) sm[stream][dc * EPL + t] = o[t];
   if (dc == 0) {
     sm[stream][D] = m;
     sm[stream][D + 1] = l;
@@ -160,61 +247,120 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
       L += sm[s][D + 1] * w;
       acc += sm[s][d] * w;
     }
-    O[(int64_t)b * ldo + h * D + d] = f32_to_bf16_bits(L > 0.f ? acc / L : 0.f);
+    // F8: a NaN cache row (a non-finite appended k / v) makes L NaN, and the output of this (sequence, head) NaN; the bf16
+    // kernel's L > 0 test would turn it into zeros.  Identical for every finite input.
+    const bool live = F8 ? !(L <= 0.f) : L > 0.f;
+    O[(int64_t)b * ldo + h * D + d] = f32_to_bf16_bits(live ? acc / L : 0.f);
   }
 }
 
 }  // namespace
 
-static int launch_attn_decode(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O, int64_t ldo, const int32_t* lens,
-                              int32_t n_seqs, int32_t n_heads, int32_t head_dim, int32_t max_len, float scale, const DecodeRope* rope,
-                              void* stream, const char* who) {
+// epl: 8 = the production bf16 kernel; 16 = the fp8 kernel (Ks != NULL) or its bf16 reference instantiation
+static int launch_attn_decode(const void* Q, int64_t ldq, const void* Kc, const void* Vc, const float* Ks, const float* Vs, void* O,
+                              int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads, int32_t head_dim, int32_t max_len,
+                              float scale, const DecodeRope* rope, int epl, void* stream, const char* who) {
   dim3 grid(n_heads, n_seqs);
   const bool few = (int64_t)n_seqs * n_heads <= 1024;      // at most four workgroups per CU: latency-bound, not bandwidth-bound
   const DecodeRope rp = rope ? *rope : DecodeRope{};
-#define ICL_DECODE_CASE(DD, UU, FF)                                                                                       \
-  hipLaunchKernelGGL((attn_decode_kernel<DD, UU, FF>), grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short*)Q, ldq, \
-                     (const unsigned short*)Kc, (const unsigned short*)Vc, (unsigned short*)O, ldo, lens, n_heads, max_len, \
+  const bool f8 = Ks != nullptr;
+#define ICL_DECODE_CASE(DD, UU, FF, F8_, EE)                                                                                   \
+  hipLaunchKernelGGL((attn_decode_kernel<DD, UU, FF, F8_, EE>), grid, dim3(256), 0, (hipStream_t)stream,                       \
+                     (const unsigned short*)Q, ldq, Kc, Vc, Ks, Vs, (unsigned short*)O, ldo, lens, n_heads, max_len,          \
                      scale * LOG2E, rp)
-  if (rope) {
-    if (head_dim == 64) { if (few) ICL_DECODE_CASE(64, 16, true); else ICL_DECODE_CASE(64, 4, true); }
-    else                { if (few) ICL_DECODE_CASE(128, 16, true); else ICL_DECODE_CASE(128, 4, true); }
+  // few: 16 key rounds at 8 elements per lane, 8 at 16 (the same keys in flight per loop iteration); a full chip: 4
+#define ICL_DECODE_D(FF, F8_, EE)                                                                                              \
+  do {                                                                                                                         \
+    constexpr int UFEW = EE == 8 ? 16 : 8;                                                                                     \
+    if (head_dim == 64) { if (few) ICL_DECODE_CASE(64, UFEW, FF, F8_, EE); else ICL_DECODE_CASE(64, 4, FF, F8_, EE); }         \
+    else                { if (few) ICL_DECODE_CASE(128, UFEW, FF, F8_, EE); else ICL_DECODE_CASE(128, 4, FF, F8_, EE); }       \
+  } while (0)
+  if (f8) {
+    if (rope) ICL_DECODE_D(true, true, 16); else ICL_DECODE_D(false, true, 16);
+  } else if (epl == 16) {
+    ICL_DECODE_D(false, false, 16);
   } else {
-    if (head_dim == 64) { if (few) ICL_DECODE_CASE(64, 16, false); else ICL_DECODE_CASE(64, 4, false); }
-    else                { if (few) ICL_DECODE_CASE(128, 16, false); else ICL_DECODE_CASE(128, 4, false); }
+    if (rope) ICL_DECODE_D(true, false, 8); else ICL_DECODE_D(false, false, 8);
   }
+#undef ICL_DECODE_D
 #undef ICL_DECODE_CASE
   ICL_CHECK_LAUNCH(who);
   return ICL_OK;
 }
 
+#define ICL_DECODE_CHECKS(who)                                                                                                 \
+  ICL_CHECK_ARG(Q && Kc && Vc && O && lens, who ": NULL pointer");                                                           \
+  ICL_CHECK_ARG(head_dim == 64 || head_dim == 128, who ": head_dim=%d (only 64 and 128)", head_dim);                           \
+  ICL_CHECK_ARG(n_seqs > 0 && n_seqs <= 65535 && n_heads > 0 && max_len > 0, who ": bad sizes");                               \
+  ICL_CHECK_ARG(ldq % 8 == 0 && ((uintptr_t)Q & 15) == 0 && ((uintptr_t)Kc & 15) == 0 && ((uintptr_t)Vc & 15) == 0,            \
+                who ": misaligned operands")
+
 extern "C" int icl_attn_decode_bf16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O,
                                     int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads,
                                     int32_t head_dim, int32_t max_len, float scale, void* stream) {
-  ICL_CHECK_ARG(Q && Kc && Vc && O && lens, "icl_attn_decode_bf16: NULL pointer");
-  ICL_CHECK_ARG(head_dim == 64 || head_dim == 128, "icl_attn_decode_bf16: head_dim=%d (only 64 and 128)", head_dim);
-  ICL_CHECK_ARG(n_seqs > 0 && n_seqs <= 65535 && n_heads > 0 && max_len > 0, "icl_attn_decode_bf16: bad sizes");
-  ICL_CHECK_ARG(ldq % 8 == 0 && ((uintptr_t)Q & 15) == 0 && ((uintptr_t)Kc & 15) == 0 && ((uintptr_t)Vc & 15) == 0,
-                "icl_attn_decode_bf16: misaligned operands");
-  return launch_attn_decode(Q, ldq, Kc, Vc, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, nullptr, stream,
-                            "icl_attn_decode_bf16");
+  ICL_DECODE_CHECKS("icl_attn_decode_bf16");
+  return launch_attn_decode(Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, nullptr, 8,
+                            stream, "icl_attn_decode_bf16");
 }
+
+extern "C" int icl_attn_decode_bf16_epl16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O,
+                                          int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads,
+                                          int32_t head_dim, int32_t max_len, float scale, void* stream) {
+  ICL_DECODE_CHECKS("icl_attn_decode_bf16_epl16");
+  return launch_attn_decode(Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, nullptr, 16,
+                            stream, "icl_attn_decode_bf16_epl16");
+}
+
+extern "C" int icl_attn_decode_fp8(const void* Q, int64_t ldq, const void* kq, const void* vq, const float* kscale,
+                                   const float* vscale, void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads,
+                                   int32_t head_dim, int32_t max_len, float scale, void* stream) {
+  const void* Kc = kq;
+  const void* Vc = vq;
+  ICL_DECODE_CHECKS("icl_attn_decode_fp8");
+  ICL_CHECK_ARG(kscale && vscale, "icl_attn_decode_fp8: NULL pointer");
+  ICL_CHECK_ARG(((uintptr_t)kscale & 3) == 0 && ((uintptr_t)vscale & 3) == 0, "icl_attn_decode_fp8: misaligned operands");
+  return launch_attn_decode(Q, ldq, kq, vq, kscale, vscale, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, nullptr, 16,
+                            stream, "icl_attn_decode_fp8");
+}
+#undef ICL_DECODE_CHECKS
+
+#define ICL_DECODE_ROPE_CHECKS(who)                                                                                            \
+  ICL_CHECK_ARG(qkv && cosT && sinT && pos && kc && vc && O && lens, who ": NULL pointer");                                    \
+  ICL_CHECK_ARG(head_dim == 64 || head_dim == 128, who ": head_dim=%d (only 64 and 128)", head_dim);                           \
+  ICL_CHECK_ARG(n_seqs > 0 && n_seqs <= 65535 && n_heads > 0 && max_len > 0, who ": bad sizes");                               \
+  ICL_CHECK_ARG(ld % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0 && k_off >= (int64_t)n_heads * head_dim &&                     \
+                    v_off >= k_off + (int64_t)n_heads * head_dim && ld >= v_off + (int64_t)n_heads * head_dim,                 \
+                who ": q | k | v column blocks must be 8-element aligned and disjoint inside a row");                           \
+  ICL_CHECK_ARG(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)kc & 15) == 0 && ((uintptr_t)vc & 15) == 0 &&                        \
+                    ((uintptr_t)cosT & 15) == 0 && ((uintptr_t)sinT & 15) == 0, who ": misaligned operands")
 
 extern "C" int icl_attn_decode_rope_bf16(const void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* cosT,
                                          const float* sinT, const int32_t* pos, const int32_t* seq_ids, void* kcache, void* vcache,
                                          void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads,
                                          int32_t head_dim, int32_t max_len, float scale, void* stream) {
-  ICL_CHECK_ARG(qkv && cosT && sinT && pos && kcache && vcache && O && lens, "icl_attn_decode_rope_bf16: NULL pointer");
-  ICL_CHECK_ARG(head_dim == 64 || head_dim == 128, "icl_attn_decode_rope_bf16: head_dim=%d (only 64 and 128)", head_dim);
-  ICL_CHECK_ARG(n_seqs > 0 && n_seqs <= 65535 && n_heads > 0 && max_len > 0, "icl_attn_decode_rope_bf16: bad sizes");
-  ICL_CHECK_ARG(ld % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0 && k_off >= (int64_t)n_heads * head_dim &&
-                    v_off >= k_off + (int64_t)n_heads * head_dim && ld >= v_off + (int64_t)n_heads * head_dim,
-                "icl_attn_decode_rope_bf16: q | k | v column blocks must be 8-element aligned and disjoint inside a row");
-  ICL_CHECK_ARG(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)kcache & 15) == 0 && ((uintptr_t)vcache & 15) == 0 &&
-                    ((uintptr_t)cosT & 15) == 0 && ((uintptr_t)sinT & 15) == 0, "icl_attn_decode_rope_bf16: misaligned operands");
+  void* kc = kcache;
+  void* vc = vcache;
+  ICL_DECODE_ROPE_CHECKS("icl_attn_decode_rope_bf16");
   DecodeRope rp;
   rp.cosT = cosT; rp.sinT = sinT; rp.pos = pos; rp.seq_ids = seq_ids;
-  rp.kc = (unsigned short*)kcache; rp.vc = (unsigned short*)vcache; rp.k_off = k_off; rp.v_off = v_off;
-  return launch_attn_decode(qkv, ld, kcache, vcache, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, &rp, stream,
-                            "icl_attn_decode_rope_bf16");
+  rp.kc = kcache; rp.vc = vcache; rp.ks = rp.vs = nullptr; rp.k_off = k_off; rp.v_off = v_off;
+  return launch_attn_decode(qkv, ld, kcache, vcache, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, &rp,
+                            8, stream, "icl_attn_decode_rope_bf16");
 }
+
+extern "C" int icl_attn_decode_rope_fp8(const void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* cosT,
+                                        const float* sinT, const int32_t* pos, const int32_t* seq_ids, void* kq, void* vq,
+                                        float* kscale, float* vscale, void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs,
+                                        int32_t n_heads, int32_t head_dim, int32_t max_len, float scale, void* stream) {
+  void* kc = kq;
+  void* vc = vq;
+  ICL_DECODE_ROPE_CHECKS("icl_attn_decode_rope_fp8");
+  ICL_CHECK_ARG(kscale && vscale, "icl_attn_decode_rope_fp8: NULL pointer");
+  ICL_CHECK_ARG(((uintptr_t)kscale & 3) == 0 && ((uintptr_t)vscale & 3) == 0, "icl_attn_decode_rope_fp8: misaligned operands");
+  DecodeRope rp;
+  rp.cosT = cosT; rp.sinT = sinT; rp.pos = pos; rp.seq_ids = seq_ids;
+  rp.kc = kq; rp.vc = vq; rp.ks = kscale; rp.vs = vscale; rp.k_off = k_off; rp.v_off = v_off;
+  return launch_attn_decode(qkv, ld, kq, vq, kscale, vscale, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, &rp, 16, stream,
+                            "icl_attn_decode_rope_fp8");
+}
+#undef ICL_DECODE_ROPE_CHECKS

@@ -10,10 +10,12 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+typedef __attribute__((ext_vector_type(8))) unsigned int u32x8;
 
 // ---- error plumbing (host) ------------------------------------------------------------------
 void icl_set_error(const char* fmt, ...);
@@ -63,6 +65,70 @@ __device__ __forceinline__ void rope_rot8(u32x4 lo, u32x4 hi, f32x4 c0, f32x4 c1
     ohi[j] = pack_bf16x2(__fadd_rn(__fmul_rn(b0, cA), __fmul_rn(a0, sA)), __fadd_rn(__fmul_rn(b1, cB), __fmul_rn(a1, sB)));
   }
 }
+// FP8 rounding rule shared by the weight packer (gemm.hip) and the FP8 KV cache (kv_fp8.hip): the smallest e with
+// m <= 448 * 2^e (0 for m = 0), and RNE into OCP e4m3fn of a value |x| <= 448.
+__device__ __forceinline__ int fp8_row_exponent(float m) {
+  if (m == 0.f) return 0;
+  int k;
+  const float f = frexpf(m, &k);            // m = f * 2^k, f in [0.5, 1);  448 = 0.875 * 2^9
+  return f <= 0.875f ? k - 9 : k - 8;
+}
+// |x| <= 448: round to nearest even into e4m3fn, integer arithmetic on the f32 bits (sign kept, -0 -> 0x80 as torch does)
+__device__ __forceinline__ unsigned f32_to_e4m3fn(float x) {
+  const unsigned u = __float_as_uint(x), a = u & 0x7fffffffu;
+  unsigned c;
+  if (a < 0x3c800000u) c = (unsigned)rintf(__uint_as_float(a) * 512.f);   // |x| < 2^-6: the subnormal grid 2^-9 (8 -> 0x08 = 2^-6)
+  else c = ((a + 0x7ffffu + ((a >> 20) & 1u)) >> 20) - (120u << 3);      // 3 mantissa bits, exponent bias 127 -> 7
+  return ((u >> 24) & 0x80u) | c;
+}
+// FP8 KV cache (include/icl_hip.h, "FP8 KV cache"): one lane's 2*NW elements (NW dwords of bf16 pairs, element 2t in the low half
+// of x[t]) of a head_dim row held by LPR adjacent lanes (all LPR lanes must call it) -> their e4m3fn codes (element i in byte i of
+// q, NW/2 dwords) and the row scale 2^e.  A row with a non-finite element gets codes 0x7f (NaN) and a NaN scale: every element of it
+// dequantizes to NaN.
+template <int LPR, int NW>
+__device__ __forceinline__ void kv_fp8_quant(const unsigned* x, unsigned* q, float& sc) {
+  float a = 0.f;
+#pragma unroll
+  for (int j = 0; j < NW; ++j) {
+    const float x0 = fabsf(__uint_as_float(x[j] << 16)), x1 = fabsf(__uint_as_float(x[j] & 0xffff0000u));
+    a = fmaxf(a, fmaxf(x0 <= 3.4028235e38f ? x0 : __builtin_inff(), x1 <= 3.4028235e38f ? x1 : __builtin_inff()));
+  }
+#pragma unroll
+  for (int o = 1; o < LPR; o <<= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
+  if (!(a <= 3.4028235e38f)) {
+#pragma unroll
+    for (int j = 0; j < NW / 2; ++j) q[j] = 0x7f7f7f7fu;
+    sc = __uint_as_float(0x7fc00000u);
+    return;
+  }
+  const int e = fp8_row_exponent(a);
+  sc = ldexpf(1.f, e);
+#pragma unroll
+  for (int j = 0; j < NW / 2; ++j) q[j] = 0u;
+#pragma unroll
+  for (int j = 0; j < NW; ++j) {
+    const unsigned c0 = f32_to_e4m3fn(ldexpf(__uint_as_float(x[j] << 16), -e));
+    const unsigned c1 = f32_to_e4m3fn(ldexpf(__uint_as_float(x[j] & 0xffff0000u), -e));
+    q[j >> 1] |= (c0 | (c1 << 8)) << ((j & 1) * 16);
+  }
+}
+template <int LPR>
+__device__ __forceinline__ void kv_fp8_quant8(u32x4 x, u32x2& q, float& sc) {
+  const unsigned xs[4] = {x[0], x[1], x[2], x[3]};
+  unsigned qs[2];
+  kv_fp8_quant<LPR, 4>(xs, qs, sc);
+  q = u32x2{qs[0], qs[1]};
+}
+// 4 * NQ e4m3fn codes (element i in byte i) of a row with scale sc -> f32 q * sc (exact: x' of the contract)
+template <int NQ>
+__device__ __forceinline__ void kv_fp8_deq(const unsigned* q, float sc, float* out) {
+  const f32x2 s = {sc, sc};
+#pragma unroll
+  for (int j = 0; j < NQ; ++j) {
+    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8(q[j], false) * s, b = __builtin_amdgcn_cvt_pk_f32_fp8(q[j], true) * s;
+    out[4 * j] = a[0]; out[4 * j + 1] = a[1]; out[4 * j + 2] = b[0]; out[4 * j + 3] = b[1];
+  }
+}
 // exact-erf GELU for the GEMM epilogues (128 values per thread, VALU-bound next to a K = 1280 main loop):
 //     gelu(x) = x Phi(x) = relu(x) - |x| Q(|x|),   Q(t) = 1 - Phi(t) = erfc(t / sqrt 2) / 2 = 2^P(t)
 // with P = log2 Q as ONE degree-7 polynomial (the -t^2/2 log2 e of the Gaussian tail folded into its quadratic term; minimax fit of
@@ -73,7 +139,6 @@ __device__ __forceinline__ void rope_rot8(u32x4 lo, u32x4 hi, f32x4 c0, f32x4 c1
 // carried a mistyped leading coefficient (0.53060 for 0.53070: 2.6e-5 absolute error, still far inside the tolerance, found when
 // this form was checked against it).  Explicit FMAs only (the same contraction at every call site: all tile shapes must
 // round alike), written on pairs so that hipcc emits v_pk_fma_f32 (two values per issue slot).
-typedef __attribute__((ext_vector_type(2))) float f32x2;
 __device__ __forceinline__ f32x2 gelu_erf2(f32x2 x) {
   const f32x2 ax = __builtin_elementwise_abs(x);
   const f32x2 t = __builtin_elementwise_min(ax, f32x2{7.0f, 7.0f});

@@ -670,20 +670,7 @@ __global__ __launch_bounds__(256) void pack_decode_w_kernel(const unsigned short
 // of an MFMA weight fragment holds ONE output row, so the scale is per lane), -> bf16 (exact).  It then issues the MFMA sequence
 // of the bf16 skinny kernel on those fragments, so its output is the bits tile 6 produces on the decode-packed copy of W'.
 // =================================================================================================================
-__device__ __forceinline__ int fp8_row_exponent(float m) {
-  if (m == 0.f) return 0;
-  int k;
-  const float f = frexpf(m, &k);            // m = f * 2^k, f in [0.5, 1);  448 = 0.875 * 2^9
-  return f <= 0.875f ? k - 9 : k - 8;
-}
-// |x| <= 448: round to nearest even into e4m3fn, integer arithmetic on the f32 bits (sign kept, -0 -> 0x80 as torch does)
-__device__ __forceinline__ unsigned f32_to_e4m3fn(float x) {
-  const unsigned u = __float_as_uint(x), a = u & 0x7fffffffu;
-  unsigned c;
-  if (a < 0x3c800000u) c = (unsigned)rintf(__uint_as_float(a) * 512.f);   // |x| < 2^-6: the subnormal grid 2^-9 (8 -> 0x08 = 2^-6)
-  else c = ((a + 0x7ffffu + ((a >> 20) & 1u)) >> 20) - (120u << 3);      // 3 mantissa bits, exponent bias 127 -> 7
-  return ((u >> 24) & 0x80u) | c;
-}
+// fp8_row_exponent / f32_to_e4m3fn: common.h (shared with the FP8 KV cache)
 // q * 2^e as bf16 bits (exact whenever the result is a bf16 normal)
 __device__ __forceinline__ unsigned short e4m3fn_scaled_to_bf16(unsigned c, int e) {
   const int E = (c >> 3) & 15, M = c & 7;

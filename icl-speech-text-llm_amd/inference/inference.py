@@ -101,6 +101,9 @@ def parse_args(argv=None):
     p.add_argument("--llm_weights", type=str, default="bf16", choices=["bf16", "fp8"],
                    help="decoder GEMM weights: bf16, or fp8 = the opt-in FP8 weight mode (each weight replaced by its FP8 rounding; "
                         "decode at <= 8 rows streams half the bytes)")
+    p.add_argument("--llm_kv", type=str, default="bf16", choices=["bf16", "fp8"],
+                   help="decoder KV cache: bf16, or fp8 = the opt-in FP8 KV cache (each cached key / value row rounded to e4m3fn "
+                        "with a power-of-two scale when it is appended; half the cache bytes)")
     return p.parse_args(argv)
 
 
@@ -213,6 +216,8 @@ def run_inference(args) -> Dict[str, Any]:
             model_args["arch"] = args.arch
         if getattr(args, "llm_weights", "bf16") != "bf16":
             model_args["llm_weight_dtype"] = args.llm_weights
+        if getattr(args, "llm_kv", "bf16") != "bf16":
+            model_args["llm_kv_dtype"] = args.llm_kv
         model = ModelFactory.create_model(model_type=args.model_type, multi_task=False, device=args.device,
                                           low_resource=True, **model_args)
         if args.peft_model_path and args.peft_model_path.strip():

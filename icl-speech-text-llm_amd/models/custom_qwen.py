@@ -23,7 +23,7 @@ from ..runtime import synth
 from ..runtime.config import QwenAudioCfg
 from ..utils.tokenization import ByteTokenizer, Encoding
 from .base_model import BaseModel
-from .custom_salmon import PackedTreeModule, check_llm_weight_dtype
+from .custom_salmon import PackedTreeModule, check_llm_kv_dtype, check_llm_weight_dtype
 
 logger = logging.getLogger(__name__)
 
@@ -53,10 +53,11 @@ def _read_generation_config(model_path) -> Dict[str, Any]:
 class QwenModule(PackedTreeModule):
     """Parameter tree under HF Qwen2-Audio key names + the packed HIP runtime built from it on first use."""
 
-    def __init__(self, cfg: QwenAudioCfg, device, seed: int = 0, llm_weight_dtype: str = "bf16"):
+    def __init__(self, cfg: QwenAudioCfg, device, seed: int = 0, llm_weight_dtype: str = "bf16", llm_kv_dtype: str = "bf16"):
         super().__init__()
         self.cfg = cfg
         self.llm_weight_dtype = check_llm_weight_dtype(llm_weight_dtype)
+        self.llm_kv_dtype = check_llm_kv_dtype(llm_kv_dtype)
         self._init_tree(device, synth.qwen_audio_state(cfg, seed=seed, device=torch.device(device), dtype=torch.bfloat16))
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
@@ -70,7 +71,8 @@ class QwenModule(PackedTreeModule):
 
     def _build_runtime(self):
         from ..runtime.qwen import QwenAudioRuntime
-        return QwenAudioRuntime(self.cfg, self.state_dict(), device=self._device, llm_weight_dtype=self.llm_weight_dtype)
+        return QwenAudioRuntime(self.cfg, self.state_dict(), device=self._device, llm_weight_dtype=self.llm_weight_dtype,
+                                llm_kv_dtype=self.llm_kv_dtype)
 
 
 class QwenSpecialTokenizer(ByteTokenizer):
@@ -185,8 +187,9 @@ class CustomQwen(BaseModel):
                  lora_rank: int = 8, lora_alpha: int = 32, lora_dropout: float = 0.05, prompt_template: str = "",
                  max_txt_len: int = 512, ckpt_path: Optional[str] = None, device=None, use_fp16: bool = True,
                  arch=None, tokenizer=None, seed: int = 0, generation_config: Optional[Dict[str, Any]] = None,
-                 llm_weight_dtype: str = "bf16", **ignored):
+                 llm_weight_dtype: str = "bf16", llm_kv_dtype: str = "bf16", **ignored):
         super().__init__(device=device, use_fp16=use_fp16)
+        check_llm_kv_dtype(llm_kv_dtype)              # "fp8": the opt-in FP8 KV cache of the decoder
         check_llm_weight_dtype(llm_weight_dtype)      # "fp8": the opt-in FP8 weight mode of the decoder (never implied by low_resource)
         if ignored:
             logger.info("CustomQwen: ignoring unknown kwargs %s", sorted(ignored))
@@ -195,7 +198,8 @@ class CustomQwen(BaseModel):
         cfg = replace(cfg, llm=replace(cfg.llm, lora_rank=lora_rank if lora else 0, lora_alpha=float(lora_alpha)))
         self.cfg = cfg
         self.llm_weight_dtype = llm_weight_dtype
-        self.model = QwenModule(cfg, self.device, seed=seed, llm_weight_dtype=llm_weight_dtype)
+        self.llm_kv_dtype = llm_kv_dtype
+        self.model = QwenModule(cfg, self.device, seed=seed, llm_weight_dtype=llm_weight_dtype, llm_kv_dtype=llm_kv_dtype)
         if ckpt_path and os.path.isfile(ckpt_path):
             ckpt = torch.load(ckpt_path, map_location="cpu")
             self.model.load_state_dict(ckpt.get("model", ckpt), strict=False)

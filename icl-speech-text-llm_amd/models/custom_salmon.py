@@ -116,6 +116,13 @@ def build_labels(prompt_len: int, target_ids: torch.Tensor, target_mask: torch.T
 LLM_WEIGHT_DTYPES = ("bf16", "fp8")
 
 
+def check_llm_kv_dtype(value: str) -> str:
+    """``llm_kv_dtype`` of the plugins: "bf16" (default) or "fp8" — the opt-in FP8 KV cache of the LLM decoder
+    (runtime/engines.py KVCache, include/icl_hip.h "FP8 KV cache").  Anything else is a ValueError."""
+    from ..runtime.engines import check_kv_dtype
+    return check_kv_dtype(value)
+
+
 def check_llm_weight_dtype(value: str) -> str:
     """``llm_weight_dtype`` of the plugins: "bf16" (default) or "fp8" — the opt-in FP8 weight mode of the LLM decoder
     (runtime/engines.py LlamaHIP, include/icl_hip.h icl_pack_fp8_weights).  Anything else is a ValueError."""
@@ -204,10 +211,11 @@ class SalmonnModule(PackedTreeModule):
     (``speech_encoder.*``, ``beats.*``, ``ln_speech``, ``ln_audio``, ``speech_Qformer.bert.*``, ``speech_query_tokens``,
     ``speech_llama_proj.*``, ``llama_model.*``) plus the packed HIP runtime built from it on first use."""
 
-    def __init__(self, cfg: SalmonnCfg, device, seed: int = 0, llm_weight_dtype: str = "bf16"):
+    def __init__(self, cfg: SalmonnCfg, device, seed: int = 0, llm_weight_dtype: str = "bf16", llm_kv_dtype: str = "bf16"):
         super().__init__()
         self.cfg = cfg
         self.llm_weight_dtype = check_llm_weight_dtype(llm_weight_dtype)
+        self.llm_kv_dtype = check_llm_kv_dtype(llm_kv_dtype)
         self._init_tree(device, synth.salmonn_state(cfg, seed=seed, device=torch.device(device), dtype=torch.bfloat16))
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
@@ -220,7 +228,8 @@ class SalmonnModule(PackedTreeModule):
 
     def _build_runtime(self):
         from ..runtime.salmonn import SalmonnRuntime
-        return SalmonnRuntime(self.cfg, self.state_dict(), device=self._device, llm_weight_dtype=self.llm_weight_dtype)
+        return SalmonnRuntime(self.cfg, self.state_dict(), device=self._device, llm_weight_dtype=self.llm_weight_dtype,
+                              llm_kv_dtype=self.llm_kv_dtype)
 
     def encode_speech(self, spectrogram=None, raw_wav=None, audio_padding_mask=None):
         """SALMONN.encode_speech signature (reference call: custom_salmon.py:550-554) -> (embeds [B,88,H], atts [B,88])."""
@@ -290,9 +299,11 @@ class CustomSALMONN(BaseModel):
                  freeze_speech_llama_proj: bool = False, lora: bool = True, lora_rank: int = 8, lora_alpha: int = 16,
                  lora_dropout: float = 0.05, ckpt_path: str = "/data2/neeraja/neeraja/salmonn_v1.pth", device=None,
                  low_resource: bool = False, use_fp16: bool = False, max_txt_len: int = 128,
-                 arch=None, tokenizer=None, seed: int = 0, llm_weight_dtype: str = "bf16", **ignored):
+                 arch=None, tokenizer=None, seed: int = 0, llm_weight_dtype: str = "bf16", llm_kv_dtype: str = "bf16",
+                 **ignored):
         super().__init__(device=device, use_fp16=use_fp16)
         check_llm_weight_dtype(llm_weight_dtype)
+        check_llm_kv_dtype(llm_kv_dtype)
         if ignored:
             logger.info("CustomSALMONN: ignoring unknown kwargs %s", sorted(ignored))  # e.g. use_cache (model_factory.py:142)
         if not (use_speech_Qformer and window_level_Qformer and num_speech_query_token == 1):
@@ -307,8 +318,10 @@ class CustomSALMONN(BaseModel):
         self.max_txt_len = max_txt_len
         # low_resource (8-bit bitsandbytes in the reference) has no effect: the north star computes in bf16.  The opt-in FP8
         # weight mode of the decoder is llm_weight_dtype="fp8" (the CLI's --llm_weights), never implied by low_resource.
+        # The opt-in FP8 KV cache is llm_kv_dtype="fp8" (the CLI's --llm_kv), independent of the weight mode.
         self.llm_weight_dtype = llm_weight_dtype
-        self.salmonn = SalmonnModule(cfg, self.device, seed=seed, llm_weight_dtype=llm_weight_dtype)
+        self.llm_kv_dtype = llm_kv_dtype
+        self.salmonn = SalmonnModule(cfg, self.device, seed=seed, llm_weight_dtype=llm_weight_dtype, llm_kv_dtype=llm_kv_dtype)
         from ..runtime.checkpoints import load_pretrained_parts
         pretrained = load_pretrained_parts(llama_path, whisper_path, beats_path, vocab=cfg.llama.vocab)
         if pretrained:

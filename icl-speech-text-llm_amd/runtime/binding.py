@@ -91,6 +91,19 @@ _SIGNATURES = {
     "icl_kv_copy_spans_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                        c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "icl_kv_copy_spans_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int64] * 12 +
+                              [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int32] * 9 + [c_void_p]),
+    "icl_kv_append_fp8": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "icl_rope_kv_fp8": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "icl_attn_decode_bf16_epl16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                           c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "icl_attn_decode_fp8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                    c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "icl_attn_decode_rope_fp8": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32,
+                                         c_int32, c_float, c_void_p]),
     "icl_logmel_whisper": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
                                    c_void_p, c_int64, c_void_p, c_void_p]),
     "icl_spec_to_xt": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
@@ -368,6 +381,65 @@ def attn_decode_rope(qkv, k_off: int, v_off: int, cos, sin, pos, seq_ids, kcache
     return out
 
 
+def _fp8_cache(kq, vq, ks, vs):
+    assert kq.dtype == torch.uint8 and vq.dtype == torch.uint8 and ks.dtype == torch.float32 and vs.dtype == torch.float32
+
+
+def attn_decode_bf16_epl16(q, kcache, vcache, out, lens, n_heads: int, head_dim: int, max_len: int, scale: float):
+    """``attn_decode`` with the fp8 kernel's lane mapping (16 elements per lane): the bf16 reference of ``attn_decode_fp8``."""
+    _require_gpu(q, kcache, vcache, out, lens)
+    assert lens.dtype == torch.int32
+    _check(load_library().icl_attn_decode_bf16_epl16(q.data_ptr(), q.stride(0), kcache.data_ptr(), vcache.data_ptr(),
+                                                     out.data_ptr(), out.stride(0), lens.data_ptr(), q.shape[0], n_heads, head_dim,
+                                                     max_len, scale, _stream()), "icl_attn_decode_bf16_epl16")
+    return out
+
+
+def attn_decode_fp8(q, kq, vq, ks, vs, out, lens, n_heads: int, head_dim: int, max_len: int, scale: float):
+    """``attn_decode`` over an FP8 KV cache (uint8 rows kq / vq, f32 row scales ks / vs): icl_attn_decode_fp8."""
+    _require_gpu(q, kq, vq, ks, vs, out, lens)
+    _fp8_cache(kq, vq, ks, vs)
+    assert lens.dtype == torch.int32
+    _check(load_library().icl_attn_decode_fp8(q.data_ptr(), q.stride(0), kq.data_ptr(), vq.data_ptr(), ks.data_ptr(), vs.data_ptr(),
+                                              out.data_ptr(), out.stride(0), lens.data_ptr(), q.shape[0], n_heads, head_dim,
+                                              max_len, scale, _stream()), "icl_attn_decode_fp8")
+    return out
+
+
+def attn_decode_rope_fp8(qkv, k_off: int, v_off: int, cos, sin, pos, seq_ids, kq, vq, ks, vs, out, lens, n_heads: int,
+                         head_dim: int, max_len: int, scale: float):
+    """``attn_decode_rope`` over an FP8 KV cache (icl_attn_decode_rope_fp8): the appended row is rounded and served rounded."""
+    _require_gpu(qkv, cos, sin, pos, seq_ids, kq, vq, ks, vs, out, lens)
+    _fp8_cache(kq, vq, ks, vs)
+    assert lens.dtype == torch.int32 and pos.dtype == torch.int32 and qkv.dtype == torch.bfloat16
+    _check(load_library().icl_attn_decode_rope_fp8(qkv.data_ptr(), qkv.stride(0), k_off, v_off, cos.data_ptr(), sin.data_ptr(),
+                                                   pos.data_ptr(), _ptr(seq_ids), kq.data_ptr(), vq.data_ptr(), ks.data_ptr(),
+                                                   vs.data_ptr(), out.data_ptr(), out.stride(0), lens.data_ptr(), qkv.shape[0],
+                                                   n_heads, head_dim, max_len, scale, _stream()), "icl_attn_decode_rope_fp8")
+    return out
+
+
+def rope_kv_fp8(qkv, k_off: int, v_off: int, cos, sin, pos, seq_ids, kq, vq, ks, vs, n_heads: int, head_dim: int,
+                max_len: int, M=None):
+    """``rope_kv`` with an FP8 KV cache (icl_rope_kv_fp8): q rotated in place, the rotated k and v rounded into the cache."""
+    _require_gpu(qkv, cos, sin, pos, seq_ids, kq, vq, ks, vs)
+    _fp8_cache(kq, vq, ks, vs)
+    M = qkv.shape[0] if M is None else M
+    _check(load_library().icl_rope_kv_fp8(qkv.data_ptr(), qkv.stride(0), k_off, v_off, cos.data_ptr(), sin.data_ptr(),
+                                          pos.data_ptr(), seq_ids.data_ptr(), kq.data_ptr(), vq.data_ptr(), ks.data_ptr(),
+                                          vs.data_ptr(), M, n_heads, head_dim, max_len, _stream()), "icl_rope_kv_fp8")
+
+
+def kv_append_fp8(qkv, k_off: int, v_off: int, pos, seq_ids, kq, vq, ks, vs, n_heads: int, head_dim: int, max_len: int, M=None):
+    """Round the (already rotated) k / v blocks of M qkv rows into an FP8 KV cache at (seq_ids[m], pos[m]): icl_kv_append_fp8."""
+    _require_gpu(qkv, pos, seq_ids, kq, vq, ks, vs)
+    _fp8_cache(kq, vq, ks, vs)
+    M = qkv.shape[0] if M is None else M
+    _check(load_library().icl_kv_append_fp8(qkv.data_ptr(), qkv.stride(0), k_off, v_off, pos.data_ptr(), seq_ids.data_ptr(),
+                                            kq.data_ptr(), vq.data_ptr(), ks.data_ptr(), vs.data_ptr(), M, n_heads, head_dim,
+                                            max_len, _stream()), "icl_kv_append_fp8")
+
+
 def layernorm(x, gamma, beta, out, eps: float, *, res=None, alpha: float = 1.0, out2=None, M=None, N=None):
     _require_gpu(x, gamma, beta, out, res, out2)
     M = x.shape[0] if M is None else M
@@ -477,20 +549,34 @@ def beam_step(logits, state: BeamState, step: int, eos_id, length_penalty: float
                                         state.parent.data_ptr(), _stream()), "icl_beam_step")
 
 
-def kv_copy_spans(src, dst, n_rows: int, *, src_seq=None, src_t0=None, dst_seq=None, dst_t0=None, n_t=None, n_fixed: int = 0):
+def kv_copy_spans(src, dst, n_rows: int, *, src_seq=None, src_t0=None, dst_seq=None, dst_t0=None, n_t=None, n_fixed: int = 0,
+                  src_scale=None, dst_scale=None):
     """src / dst: bf16 [layers][seqs][heads][positions][head_dim] (any strides on the first three dims); copies, per row r,
-    layer and head, ``n_t[r]`` (or ``n_fixed``) positions from (src_seq[r], src_t0[r]) to (dst_seq[r], dst_t0[r])."""
-    _require_gpu(src, dst, src_seq, src_t0, dst_seq, dst_t0, n_t)
-    assert src.dtype == torch.bfloat16 and dst.dtype == torch.bfloat16 and src.dim() == 5 and dst.dim() == 5
+    layer and head, ``n_t[r]`` (or ``n_fixed``) positions from (src_seq[r], src_t0[r]) to (dst_seq[r], dst_t0[r]).
+    FP8 KV cache: src / dst are the uint8 row bytes and ``src_scale`` / ``dst_scale`` their f32 [layers][seqs][heads][positions]
+    scale planes (icl_kv_copy_spans_fp8 moves both)."""
+    _require_gpu(src, dst, src_seq, src_t0, dst_seq, dst_t0, n_t, src_scale, dst_scale)
+    fp8 = src.dtype == torch.uint8
+    assert src.dtype == dst.dtype and src.dtype in (torch.bfloat16, torch.uint8) and src.dim() == 5 and dst.dim() == 5
     assert src.stride(4) == 1 and dst.stride(4) == 1 and src.stride(3) == src.shape[4] and dst.stride(3) == dst.shape[4]
     assert src.shape[0] == dst.shape[0] and src.shape[2] == dst.shape[2] and src.shape[4] == dst.shape[4]
     for t in (src_seq, src_t0, dst_seq, dst_t0, n_t):
         assert t is None or (t.dtype == torch.int32 and t.numel() >= n_rows)
+    ids = (_ptr(src_seq), _ptr(src_t0), _ptr(dst_seq), _ptr(dst_t0), _ptr(n_t), n_fixed, n_rows, src.shape[0], src.shape[2],
+           src.shape[4], src.shape[1], dst.shape[1], src.shape[3], dst.shape[3], _stream())
+    if fp8:
+        assert src_scale is not None and dst_scale is not None and src_scale.dtype == torch.float32 and dst_scale.dtype == torch.float32
+        assert tuple(src_scale.shape) == tuple(src.shape[:4]) and tuple(dst_scale.shape) == tuple(dst.shape[:4])
+        assert src_scale.stride(3) == 1 and dst_scale.stride(3) == 1
+        _check(load_library().icl_kv_copy_spans_fp8(src.data_ptr(), src_scale.data_ptr(), dst.data_ptr(), dst_scale.data_ptr(),
+                                                    src.stride(0), src.stride(1), src.stride(2), dst.stride(0), dst.stride(1),
+                                                    dst.stride(2), src_scale.stride(0), src_scale.stride(1), src_scale.stride(2),
+                                                    dst_scale.stride(0), dst_scale.stride(1), dst_scale.stride(2), *ids),
+               "icl_kv_copy_spans_fp8")
+        return
+    assert src_scale is None and dst_scale is None
     _check(load_library().icl_kv_copy_spans_bf16(src.data_ptr(), dst.data_ptr(), src.stride(0), src.stride(1), src.stride(2),
-                                                 dst.stride(0), dst.stride(1), dst.stride(2), _ptr(src_seq), _ptr(src_t0),
-                                                 _ptr(dst_seq), _ptr(dst_t0), _ptr(n_t), n_fixed, n_rows, src.shape[0],
-                                                 src.shape[2], src.shape[4], src.shape[1], dst.shape[1], src.shape[3],
-                                                 dst.shape[3], _stream()), "icl_kv_copy_spans_bf16")
+                                                 dst.stride(0), dst.stride(1), dst.stride(2), *ids), "icl_kv_copy_spans_bf16")
 
 
 def logmel_whisper(wav, wav_lens, mel_filters, n_mel: int, spec, xt, workspace):

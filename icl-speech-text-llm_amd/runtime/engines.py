@@ -462,11 +462,12 @@ class LlamaHIP:
     # ---- one decoder layer over M packed rows ---------------------------------------------------
     def _layer(self, ws: Workspace, L, h, M: int, tag: str, attn_fn, pos, seq_ids, kc, vc, max_len: int,
                split: Optional[dict] = None, kv_rows_to_c: bool = True, xn_ready: bool = False, next_norm=None,
-               attn_does_rope: bool = False):
+               attn_does_rope: bool = False, rope_fn=None):
         """``xn_ready``: the previous call has already written this layer's normalised input (decode: fused into the reduction
         of the previous down_proj).  ``next_norm`` = (gamma, out bf16 [M, >= hidden]) of the RMSNorm that follows this layer
         (the next layer's input norm into the same ``xn`` buffer, or the final norm): decode fuses it into the down_proj's
-        split-K reduction, as it does the post-attention norm into the o_proj's (icl_gemm_rmsnorm_bf16)."""
+        split-K reduction, as it does the post-attention norm into the o_proj's (icl_gemm_rmsnorm_bf16).  ``rope_fn(qkv)``
+        replaces the stand-alone RoPE + cache append of a decode step (the FP8 KV cache's icl_rope_kv_fp8)."""
         c, w = self.w.cfg, self.w
         hd, I, D, H = c.hidden, c.ffn, c.head_dim, c.n_heads
         xn = ws.get(tag + "xn", (M, w.k_aug), BF16, zero=True)   # augmentation tail stays zero
@@ -506,7 +507,9 @@ class LlamaHIP:
         else:
             B.gemm(xn, weight_of("qkv", 0, L.wqkv), qkv, bias=L.bqkv, split_k=sk.get("qkv", 1),
                    workspace=wsk, tile=tile_of("qkv"), N=3 * hd, K=w.k_aug, w_scale=scale_of("qkv", 0))
-            if not attn_does_rope:      # decode: RoPE + cache append run inside the attention launch (icl_attn_decode_rope_bf16)
+            if rope_fn is not None:
+                rope_fn(qkv)
+            elif not attn_does_rope:    # decode: RoPE + cache append run inside the attention launch (icl_attn_decode_rope_bf16)
                 B.rope_kv(qkv, hd, 2 * hd, w.rope_cos, w.rope_sin, pos, seq_ids, kc, vc, H, D, max_len, M=M)
         attn_fn(qkv, att)
         fuse = split is not None and self.fuse_decode_norms
@@ -546,7 +549,10 @@ class LlamaHIP:
         # With a cache and the fused QKV epilogue, k / v are written ONCE — into the cache — and the attention reads them
         # there ([seq][head][pos][D]: 256-B rows at a 256-B stride instead of a 3*hidden stride); the k / v columns of the QKV
         # buffer are never written.  Without a cache (teacher-forced forward) they stay packed next to q.
-        kv_from_cache = cache is not None and B.rope_fusable(M, H, D, self.w.k_aug)
+        # FP8 KV cache: prefill attends to its own unrounded k / v, so the layer runs as without a cache (k / v rows into the QKV
+        # buffer) and one icl_kv_append_fp8 pass rounds them into the cache before the attention.
+        fp8 = cache is not None and cache.dtype == "fp8"
+        kv_from_cache = cache is not None and not fp8 and B.rope_fusable(M, H, D, self.w.k_aug)
 
         def attn(qkv, att):
             B.attn_fwd(qkv[:, :hd], qkv[:, hd:2 * hd], qkv[:, 2 * hd:], att, cu, maxS, H, D, D ** -0.5, causal=True)
@@ -555,6 +561,13 @@ class LlamaHIP:
             kc = cache.k[i] if cache is not None else None
             vc = cache.v[i] if cache is not None else None
             fn = attn
+            if fp8:
+                def fn(qkv, att, i=i):
+                    B.kv_append_fp8(qkv, hd, 2 * hd, pos, sid, cache.k[i], cache.v[i], cache.ks[i], cache.vs[i], H, D, cache.max_len,
+                                    M=M)
+                    attn(qkv, att)
+                self._layer(ws, L, h, M, "pf_", fn, pos, sid, None, None, 0)
+                continue
             if kv_from_cache:
                 def fn(qkv, att, kc=kc, vc=vc):
                     B.attn_fwd(qkv[:, :hd], kc, vc, att, cu, maxS, H, D, D ** -0.5, causal=True, kv_cache_max_len=cache.max_len)
@@ -619,15 +632,29 @@ class LlamaHIP:
         xn_next = ws.get("dc_xn", (Bn, self.w.k_aug), BF16, zero=True)          # the layers' normalised-input buffer (_layer's tag + "xn")
         xn_final = ws.get("dc_logits_xn", (Bn, c.hidden), BF16)
         ready = False
+        fp8 = cache.dtype == "fp8"
         for i, L in enumerate(layers):
             kc, vc = cache.k[i], cache.v[i]
+            ks, vs = (cache.ks[i], cache.vs[i]) if fp8 else (None, None)
 
             # One launch: rotate q / k at pos, append k / v, attend — bit-identical to the two launches, so the choice is free.
             # Same-box A/B (tools/ab_decode_rope.sh, profiles/r04_decode_rope_ab.txt): at 256 rows decode 143.2 -> 142.5 ms; at ONE
             # sequence 58.4 -> 59.6 ms per utterance — the rotation's dependent loads (pos -> cos / sin, q, k) sit in front of a
             # latency-bound attention and cost more than the 5-us launch they replace — so small batches keep the two launches.
             fuse_rope = self.fuse_decode_rope and Bn > 8
-            if fuse_rope:
+            rope_fn = None
+            if fp8 and fuse_rope:       # FP8 KV cache: the same two forms, rounding the appended row to x' (icl_hip.h)
+                def attn(qkv, att, kc=kc, vc=vc, ks=ks, vs=vs):
+                    B.attn_decode_rope_fp8(qkv, c.hidden, 2 * c.hidden, self.w.rope_cos, self.w.rope_sin, pos, sid, kc, vc, ks, vs,
+                                           att, lens, H, D, cache.max_len, D ** -0.5)
+            elif fp8:
+                def rope_fn(qkv, ks=ks, vs=vs, kc=kc, vc=vc):
+                    B.rope_kv_fp8(qkv, c.hidden, 2 * c.hidden, self.w.rope_cos, self.w.rope_sin, pos, sid, kc, vc, ks, vs, H, D,
+                                  cache.max_len, M=Bn)
+
+                def attn(qkv, att, kc=kc, vc=vc, ks=ks, vs=vs):
+                    B.attn_decode_fp8(qkv[:, :c.hidden], kc, vc, ks, vs, att, lens, H, D, cache.max_len, D ** -0.5)
+            elif fuse_rope:
                 def attn(qkv, att, kc=kc, vc=vc):
                     B.attn_decode_rope(qkv, c.hidden, 2 * c.hidden, self.w.rope_cos, self.w.rope_sin, pos, sid, kc, vc, att, lens,
                                        H, D, cache.max_len, D ** -0.5)
@@ -637,24 +664,50 @@ class LlamaHIP:
 
             nxt = (layers[i + 1].rms1, xn_next) if i + 1 < len(layers) else (self.w.norm, xn_final)
             ready = self._layer(ws, L, h, Bn, "dc_", attn, pos, sid, kc, vc, cache.max_len, split=split, xn_ready=ready,
-                                next_norm=nxt, attn_does_rope=fuse_rope)
+                                next_norm=nxt, attn_does_rope=fuse_rope, rope_fn=rope_fn)
         return self.logits(ws, h, name="dc_logits", xn_ready=ready)
 
 
-class KVCache:
-    """bf16 K/V cache, per layer [n_seqs][n_heads][max_len][head_dim] (one contiguous stream per (seq, head)): a view of
-    the workspace's single ``kv_k`` / ``kv_v`` allocations, which grow to the largest (n_seqs x max_len) seen."""
+KV_DTYPES = ("bf16", "fp8")
 
-    def __init__(self, cfg, n_seqs: int, max_len: int, ws: Workspace):
-        self.n_seqs, self.max_len = n_seqs, max_len
+
+def check_kv_dtype(value: str) -> str:
+    """The KV-cache dtype of the LLM decoder: "bf16" (default) or "fp8" (the opt-in FP8 KV cache, include/icl_hip.h)."""
+    if value not in KV_DTYPES:
+        raise ValueError(f"llm_kv_dtype must be one of {KV_DTYPES}, not {value!r}")
+    return value
+
+
+class KVCache:
+    """K/V cache, per layer [n_seqs][n_heads][max_len][head_dim] (one contiguous stream per (seq, head)): a view of
+    the workspace's single ``kv_k`` / ``kv_v`` allocations, which grow to the largest (n_seqs x max_len) seen.
+
+    ``dtype="fp8"`` (the opt-in FP8 KV cache, include/icl_hip.h): ``k`` / ``v`` hold the e4m3fn bytes of every row (uint8, the
+    same shape) and ``ks`` / ``vs`` its f32 scale 2^e, [n_layers][n_seqs][n_heads][max_len]; all four keep the ``kv_`` prefix,
+    so captured decode graphs are retired when they move (Workspace.GRAPH_VISIBLE)."""
+
+    def __init__(self, cfg, n_seqs: int, max_len: int, ws: Workspace, dtype: str = "bf16"):
+        self.n_seqs, self.max_len, self.dtype = n_seqs, max_len, check_kv_dtype(dtype)
         shape = (cfg.n_layers, n_seqs, cfg.n_heads, max_len, cfg.head_dim)
-        self.k = ws.get("kv_k", shape, BF16)
-        self.v = ws.get("kv_v", shape, BF16)
+        if dtype == "fp8":
+            self.k = ws.get("kv_k8", shape, torch.uint8)
+            self.v = ws.get("kv_v8", shape, torch.uint8)
+            self.ks = ws.get("kv_ks", shape[:4], F32)
+            self.vs = ws.get("kv_vs", shape[:4], F32)
+        else:
+            self.k = ws.get("kv_k", shape, BF16)
+            self.v = ws.get("kv_v", shape, BF16)
+            self.ks = self.vs = None
+
+    def planes(self):
+        """((k, k scales), (v, v scales)); the scales are None in a bf16 cache."""
+        return ((self.k, self.ks), (self.v, self.vs))
 
     def rows(self, b0: int, b1: int) -> "KVCache":
         """The cache of sequences b0 .. b1-1 only (views; sequence ids inside are relative to b0): a prefill over a chunk of
         the batch appends into, and reads from, its own block of the one allocation."""
         sub = object.__new__(KVCache)
-        sub.n_seqs, sub.max_len = b1 - b0, self.max_len
+        sub.n_seqs, sub.max_len, sub.dtype = b1 - b0, self.max_len, self.dtype
         sub.k, sub.v = self.k[:, b0:b1], self.v[:, b0:b1]
+        sub.ks, sub.vs = (self.ks[:, b0:b1], self.vs[:, b0:b1]) if self.ks is not None else (None, None)
         return sub

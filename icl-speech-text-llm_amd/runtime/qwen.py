@@ -10,7 +10,7 @@ import torch
 
 from . import binding as B
 from .config import QwenAudioCfg
-from .engines import BF16, F32, I32, LlamaHIP, LogMel, QwenAudioTowerHIP, WhisperEncoderHIP, Workspace, _i32
+from .engines import BF16, F32, I32, LlamaHIP, LogMel, QwenAudioTowerHIP, WhisperEncoderHIP, Workspace, _i32, check_kv_dtype
 from .packing import _bf, _f32, _take, pack_llama, pack_whisper
 from .salmonn import CausalLMRuntimeMixin, speech_segment
 
@@ -40,12 +40,13 @@ def normalize_qwen_keys(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
 
 class QwenAudioRuntime(CausalLMRuntimeMixin):
     def __init__(self, cfg: QwenAudioCfg, state_dict: Dict[str, torch.Tensor], device="cuda", consume: bool = False,
-                 llm_weight_dtype: str = "bf16"):
+                 llm_weight_dtype: str = "bf16", llm_kv_dtype: str = "bf16"):
         if not torch.cuda.is_available():
             raise B.IclError("QwenAudioRuntime needs a GPU: the HIP path has no CPU fallback")
         B.load_library()
         self.cfg, self.lm_cfg = cfg, cfg.llm
         self.device = torch.device(device)
+        self.kv_dtype = check_kv_dtype(llm_kv_dtype)
         sd = state_dict if consume else normalize_qwen_keys(state_dict)
         self.ws = Workspace(self.device)
         self.logmel = LogMel(cfg.audio.n_mels, self.device)

@@ -18,7 +18,8 @@ import torch
 
 from . import binding as B
 from .config import SalmonnCfg
-from .engines import BF16, F32, I32, BeatsHIP, KVCache, LlamaHIP, LogMel, SpeechQFormerHIP, WhisperEncoderHIP, Workspace, _i32
+from .engines import (BF16, F32, I32, BeatsHIP, KVCache, LlamaHIP, LogMel, SpeechQFormerHIP, WhisperEncoderHIP, Workspace, _i32,
+                      check_kv_dtype)
 from .packing import normalize_keys, pack_beats, pack_llama, pack_qformer, pack_whisper
 
 Segment = Union[Sequence[int], Tuple[str, int, int]]  # token ids | ("speech", first_row, n_rows)
@@ -42,6 +43,7 @@ class CausalLMRuntimeMixin:
     (Llama-2 / Vicuna) and Qwen2-Audio runtimes."""
 
     use_graphs = True          # capture the decode loop in a HIP graph (per batch shape) after its first eager pass
+    kv_dtype = "bf16"          # the decoder's KV cache: "bf16", or "fp8" (the opt-in FP8 KV cache; engines.KVCache)
 
     # --------------------------------------------------------------------------------------------
     # K9: prompt segments -> gather indices
@@ -107,7 +109,7 @@ class CausalLMRuntimeMixin:
     def _cache(self, n_seqs: int, max_len: int) -> KVCache:
         """K/V views over the workspace's one K and one V allocation (they grow to the largest n_seqs x max_len seen; a
         move bumps ``ws.generation``, which retires every captured graph)."""
-        return KVCache(self.lm_cfg, n_seqs, max_len, self.ws)
+        return KVCache(self.lm_cfg, n_seqs, max_len, self.ws, dtype=self.kv_dtype)
 
     prefill_chunk = int(os.environ.get("ICL_PREFILL_CHUNK", "128"))   # sequences per prefill pass of generate() (see there)
 
@@ -280,7 +282,7 @@ class CausalLMRuntimeMixin:
             # The decode loop is launch-bound at small batch (~17 kernels x layers x steps): after one eager pass that
             # sizes every workspace buffer, it is captured ONCE per (batch, cache length, steps, eos, pad) into a HIP
             # graph and replayed — all pointers are workspace-stable and nothing inside synchronises or allocates.
-            gkey = (Bn, max_len, steps, eos, pad, knobs, trace is not None)
+            gkey = (Bn, max_len, steps, eos, pad, knobs, trace is not None, self.kv_dtype)
             graph, warm = self._graph_lookup(gkey) if self.use_graphs else (None, False)
             if graph is not None:
                 graph.replay()
@@ -381,8 +383,8 @@ class CausalLMRuntimeMixin:
         if T > 1:
             src = ws.get("gen_beam_src", (BK,), I32)           # beam b*K+k starts from the prompt rows of sequence BK + b
             src.copy_(torch.tensor([BK + b for b in range(Bn) for _ in range(K)], dtype=I32), non_blocking=True)
-            for kv in (whole.k, whole.v):
-                B.kv_copy_spans(kv, kv, BK, src_seq=src, n_t=plen)
+            for kv, sc in whole.planes():
+                B.kv_copy_spans(kv, kv, BK, src_seq=src, n_t=plen, src_scale=sc, dst_scale=sc)
             steps = T - 1
             pos_all = ws.get("gen_pos", (steps, BK), I32)
             len_all = ws.get("gen_len", (steps, BK), I32)
@@ -390,31 +392,38 @@ class CausalLMRuntimeMixin:
             pos_all.copy_(torch.tensor([[s + t for s in lens_rep] for t in range(steps)], dtype=I32), non_blocking=True)
             len_all.copy_(torch.tensor([[s + t + 1 for s in lens_rep] for t in range(steps)], dtype=I32), non_blocking=True)
             sid.copy_(torch.arange(BK, dtype=I32), non_blocking=True)
-            tmp_k = ws.get("beam_tmp_k", (c.n_layers, BK, c.n_heads, steps, c.head_dim), BF16)
-            tmp_v = ws.get("beam_tmp_v", tuple(tmp_k.shape), BF16)
+            tmp_k = ws.get("beam_tmp_k", (c.n_layers, BK, c.n_heads, steps, c.head_dim), cache.k.dtype)
+            tmp_v = ws.get("beam_tmp_v", tuple(tmp_k.shape), cache.k.dtype)
+            tmp_ks = tmp_vs = None
+            if cache.dtype == "fp8":                           # FP8 KV cache: the row scales travel with the row bytes
+                tmp_ks = ws.get("beam_tmp_ks", tuple(tmp_k.shape[:4]), F32)
+                tmp_vs = ws.get("beam_tmp_vs", tuple(tmp_k.shape[:4]), F32)
             for t in range(steps):
                 if t:                                          # the t positions generated so far follow their beam's parent
-                    for kv, tmp in ((cache.k, tmp_k), (cache.v, tmp_v)):
-                        B.kv_copy_spans(kv, tmp, BK, src_seq=st.parent, src_t0=plen, n_fixed=t)
-                        B.kv_copy_spans(tmp, kv, BK, dst_t0=plen, n_fixed=t)
+                    for (kv, sc), tmp, tsc in zip(cache.planes(), (tmp_k, tmp_v), (tmp_ks, tmp_vs)):
+                        B.kv_copy_spans(kv, tmp, BK, src_seq=st.parent, src_t0=plen, n_fixed=t, src_scale=sc, dst_scale=tsc)
+                        B.kv_copy_spans(tmp, kv, BK, dst_t0=plen, n_fixed=t, src_scale=tsc, dst_scale=sc)
                 lg = self.llama.decode_step(ws, cache, st.next_ids, pos_all[t], len_all[t], sid)
                 score(lg, t + 1)
         best = st.fin_seq[:, 0].cpu().to(torch.int64)                                   # the only D2H pair of the call
         blen = st.fin_len[:, 0].cpu()
-        ws.release("beam_tmp_k", "beam_tmp_v")      # 2 x layers x rows x heads x (T-1) x head_dim bf16: not kept between calls
+        # 2 x layers x rows x heads x (T-1) x head_dim cache elements (+ the fp8 cache's row scales): not kept between calls
+        ws.release("beam_tmp_k", "beam_tmp_v", "beam_tmp_ks", "beam_tmp_vs")
         width = max(1, int(blen.max()))
         return GenerateResult(tokens=best[:, :width].contiguous(), first_logits=first)
 
 
 class SalmonnRuntime(CausalLMRuntimeMixin):
     def __init__(self, cfg: SalmonnCfg, state_dict: Dict[str, torch.Tensor], device="cuda", consume: bool = False,
-                 parts: Sequence[str] = ("whisper", "beats", "qformer", "llama"), llm_weight_dtype: str = "bf16"):
+                 parts: Sequence[str] = ("whisper", "beats", "qformer", "llama"), llm_weight_dtype: str = "bf16",
+                 llm_kv_dtype: str = "bf16"):
         if not torch.cuda.is_available():
             raise B.IclError("SalmonnRuntime needs a GPU: the HIP path has no CPU fallback")
         B.load_library()
         self.cfg = cfg
         self.lm_cfg = cfg.llama
         self.device = torch.device(device)
+        self.kv_dtype = check_kv_dtype(llm_kv_dtype)
         sd = normalize_keys(state_dict) if not consume else state_dict
         self.ws = Workspace(self.device)
         self.whisper = self.beats = self.qformer = self.llama = None

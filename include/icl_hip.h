@@ -402,6 +402,56 @@ int icl_kv_copy_spans_bf16(const void* src, void* dst, int64_t src_layer_stride,
                            int32_t n_rows, int32_t n_layers, int32_t n_heads, int32_t head_dim,
                            int32_t src_n_seqs, int32_t dst_n_seqs, int32_t src_len, int32_t dst_len, void* stream);
 
+/* ---- K10/K11 (opt-in FP8 KV cache): fp8 append, decode attention and beam copy -------------------------------
+ * Numeric contract.  A cache row x is one (layer, sequence, head, position) vector of head_dim elements: the post-RoPE key or the
+ * value.  It is stored as head_dim OCP e4m3fn bytes q and one scale 2^e, where e is the smallest integer with
+ * max_i |x[i]| <= 448 * 2^e (0 for an all-zero row) and q[i] = RNE_e4m3fn(x[i] / 2^e), never saturated: the bytes of
+ * torch's (x.float() / 2**e).to(torch.float8_e4m3fn), the rule of icl_pack_fp8_weights per weight row.  x' = q * 2^e is exact in
+ * bf16.  A row holding a non-finite element is stored as bytes 0x7f (NaN) with a NaN scale: all of it reads back as NaN.
+ * Layout: bytes [n_seqs][n_heads][max_len][head_dim] (uint8) per layer, as the bf16 cache; scales f32 [n_seqs][n_heads][max_len]
+ * (one f32 2^e per row, a plane of its own).  head_dim is 64 or 128.
+ * The fp8-KV model is the bf16 model whose cache entries are replaced by x' when they are appended: prefill attends to its own
+ * unrounded K/V (the caller runs the QKV GEMM with kv_rows_to_c and no bf16 append, then icl_kv_append_fp8), and every decode
+ * step attends over x', the row appended in that step included.
+ *
+ * icl_kv_append_fp8: for every row m < M of qkv bf16 [M][ld] (k / v column blocks at k_off / v_off, already rotated), rounds
+ *   the k and v of each head and stores them at (seq_ids[m], head, pos[m]).  A position outside [0, max_len) stores nothing.
+ * icl_rope_kv_fp8: icl_rope_kv_bf16 with an fp8 cache: rotates q in place and k (rope_rot8, the same bf16 rounding points), and
+ *   appends the rounded rotated k and v.  The k block of qkv is left unrotated (decode reads only q).
+ * icl_attn_decode_fp8 / icl_attn_decode_rope_fp8: icl_attn_decode_bf16 / icl_attn_decode_rope_bf16 over an fp8 cache.  A
+ *   lane reads 16 elements of a key row (one 16-byte load; head_dim / 16 lanes per row) and its scale, rebuilds x' exactly and
+ *   runs the bf16 kernel's arithmetic (key groups, online softmax, merge) on it.  The output is bit-identical to
+ *   icl_attn_decode_bf16_epl16 — the bf16 kernel instantiated with the same 16-element lane mapping, a reference entry point —
+ *   on a bf16 cache holding x'; against icl_attn_decode_bf16 (8 elements per lane) only the order of each score's partial sums
+ *   differs.  The fused form rounds the appended row in registers and attends over that rounded row.  A NaN row (see above) makes the output of its (sequence, head) NaN.
+ * icl_kv_copy_spans_fp8: icl_kv_copy_spans_bf16 over both planes (byte strides for the row bytes, element strides for the
+ *   scales); head_dim a multiple of 16.
+ */
+int icl_kv_append_fp8(const void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const int32_t* pos, const int32_t* seq_ids,
+                      void* kq, void* vq, float* kscale, float* vscale, int32_t M, int32_t n_heads, int32_t head_dim,
+                      int32_t max_len, void* stream);
+int icl_rope_kv_fp8(void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* cos, const float* sin,
+                    const int32_t* pos, const int32_t* seq_ids, void* kq, void* vq, float* kscale, float* vscale,
+                    int32_t M, int32_t n_heads, int32_t head_dim, int32_t max_len, void* stream);
+int icl_attn_decode_bf16_epl16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O, int64_t ldo,
+                               const int32_t* lens, int32_t n_seqs, int32_t n_heads, int32_t head_dim, int32_t max_len,
+                               float scale, void* stream);
+int icl_attn_decode_fp8(const void* Q, int64_t ldq, const void* kq, const void* vq, const float* kscale, const float* vscale,
+                        void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads, int32_t head_dim,
+                        int32_t max_len, float scale, void* stream);
+int icl_attn_decode_rope_fp8(const void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* cos, const float* sin,
+                             const int32_t* pos, const int32_t* seq_ids, void* kq, void* vq, float* kscale, float* vscale,
+                             void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads, int32_t head_dim,
+                             int32_t max_len, float scale, void* stream);
+int icl_kv_copy_spans_fp8(const void* src, const float* src_scale, void* dst, float* dst_scale, int64_t src_layer_stride,
+                          int64_t src_seq_stride, int64_t src_head_stride, int64_t dst_layer_stride, int64_t dst_seq_stride,
+                          int64_t dst_head_stride, int64_t src_scale_layer_stride, int64_t src_scale_seq_stride,
+                          int64_t src_scale_head_stride, int64_t dst_scale_layer_stride, int64_t dst_scale_seq_stride,
+                          int64_t dst_scale_head_stride, const int32_t* src_seq, const int32_t* src_t0, const int32_t* dst_seq,
+                          const int32_t* dst_t0, const int32_t* n_t, int32_t n_fixed, int32_t n_rows, int32_t n_layers,
+                          int32_t n_heads, int32_t head_dim, int32_t src_n_seqs, int32_t dst_n_seqs, int32_t src_len,
+                          int32_t dst_len, void* stream);
+
 /* ---- K12: causal-LM cross entropy (teacher-forced forward only) -------------------------------
  * row_loss[r] = logsumexp(logits[r][:]) - logits[r][labels[r]] for labels[r] in [0,V), else 0;
  * mean_loss[0] = mean of row_loss over the valid rows (NaN if none) — torch CrossEntropyLoss with
