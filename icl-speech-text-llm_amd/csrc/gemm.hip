@@ -337,12 +337,15 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmParams p) {
 // form), stores the f32 row, and the block then reduces sum(v^2) (wave shuffles, the four wave sums added in wave order: a
 // fixed order, not the one-wave-per-row order of norm_kernel) and writes xn = bf16(v * rsqrt(mean + eps) * gamma).
 // Saves a launch and a re-read of the row per instance (9.8 + 13.8 us -> one kernel at 256 rows).
+// split_k == 1 with ws == C (icl_gemm_rmsnorm_bf16's row-per-block norm over rows the GEMM has finished): C is read as the one
+// slab and NOT stored again — 0 + x would turn a -0.0 into +0.0, and C must keep the GEMM's bits.
 template <int VPT>   // 16-B pieces per thread: N <= 1024 * VPT
 __global__ __launch_bounds__(256) void splitk_reduce_rmsnorm_kernel(GemmParams p, const float* gamma, float eps,
                                                                     unsigned short* xn, int64_t ldx) {
   __shared__ float wsum[4];
   const int m = blockIdx.x, tid = threadIdx.x, nvec = p.N >> 2;
   const int64_t slab = (int64_t)p.M * p.N;
+  const bool store_c = p.split_k > 1 || p.ws != (const float*)p.C;
   f32x4 v[VPT];
 #pragma unroll
   for (int i = 0; i < VPT; ++i) {
@@ -356,7 +359,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_rmsnorm_kernel(GemmParams p
     const int c = tid + i * 256;
     if (c < nvec) {
       if (p.epi & ICL_EPI_RESIDUAL) v[i] = v[i] + *(const f32x4*)((const float*)p.R + (int64_t)m * p.ldr + c * 4);
-      *(f32x4*)((float*)p.C + (int64_t)m * p.ldc + c * 4) = v[i];
+      if (store_c) *(f32x4*)((float*)p.C + (int64_t)m * p.ldc + c * 4) = v[i];
       ss += v[i][0] * v[i][0] + v[i][1] * v[i][1] + v[i][2] * v[i][2] + v[i][3] * v[i][3];
     }
   }

@@ -226,7 +226,9 @@ void launch_norm(hipStream_t st, const void* x, int64_t ldx, const void* res, fl
                    (RMS || ((uintptr_t)beta % 16) == 0);
   // measured at micro-batch 128 (tools/bench_norm128.py): Whisper LN (N = 1280) 399 -> 317 us, 13B RMS (N = 5120) 258 -> 221 us;
   // N <= 1024 (BEATs), N = 4096 and the residual / dual-output forms are as fast or faster on the one-row-per-wave kernel.
-  // The choice depends on N and the call form only, never on M: a row must round the same in any batch.
+  // The choice depends on N and the call form only, never on M: a row must round the same in any batch.  (One exception outside
+  // this file: icl_gemm_rmsnorm_bf16 normalises M <= 64 rows with the row-per-block kernel of its split-K path, whose sum of
+  // squares runs in a different fixed order — its xn for a row can differ by 1 bf16 ulp between M <= 64 and M > 64; gemm.hip.)
   const int pl8 = ((N >> 3) + 63) / 64;
 #ifndef ICL_NORM8_ALL
 #define ICL_NORM8_ALL 0      // A/B: route every eligible shape to the streaming variant

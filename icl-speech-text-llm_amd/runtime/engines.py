@@ -10,6 +10,7 @@ Reference call sites: models/custom_salmon.py:546-554 (encode_speech), :115-299 
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -387,6 +388,89 @@ class SpeechQFormerHIP:
 
 
 # ================================================================================================
+# K11 decode GEMM planner: which kernel runs each GEMM of a decode step (a pure function of the batch, the model dims and the
+# device's CU count, so the plan can be computed and checked without a GPU: tests/test_decode_plan.py)
+# ================================================================================================
+DECODE_SITES = ("qkv", "o", "gu", "down")
+
+
+@dataclass(frozen=True)
+class GemmLaunch:
+    """One GEMM launch of a decode step.  ``tile``: the icl_gemm_args tile (0 = the library's auto choice, icl_gemm_select_tile)
+    or "fp8w" (icl_gemm_fp8w); ``weight``: "row" (the row-major layer weight), "packed" (its decode-packed copy) or "fp8" (the
+    fp8 decode-packed copy + row scales); ``fused_norm``: the RMSNorm after the GEMM runs in the same call (icl_gemm_rmsnorm_*)."""
+    tile: object
+    split_k: int
+    weight: str
+    N: int
+    K: int
+    fused_norm: bool = False
+
+
+@dataclass(frozen=True)
+class DecodePlan:
+    Bn: int
+    sites: Dict[str, GemmLaunch]    # DECODE_SITES + "lm_head"
+    workspace: int                  # f32 elements of the layers' shared split-K workspace (0: no site splits)
+
+
+def lm_head_tile(R: int) -> int:
+    """LM head over R rows: the skinny kernel for a decode-sized batch, else the library's choice."""
+    return 4 if R <= 8 else 0
+
+
+def t256_split(N: int, K: int, n_cu: int) -> int:
+    """Split-K of a 256-row decode GEMM on the 256x256 tile: one M-tile, ceil(N / 256) N-tiles; the slices fill ~80 % of the
+    CUs (a second partial round of blocks costs more than idle CUs) and stay >= 8 K-tiles deep (the pipeline's fill / drain);
+    0 = leave the GEMM on the decode tile (too few blocks either way)."""
+    tiles = (N + 255) // 256
+    split = min(K // 512, int(0.8 * n_cu) // tiles)
+    return split if split >= 2 and tiles * split >= 0.45 * n_cu else 0
+
+
+def decode_plan(Bn: int, cfg, k_aug: int, n_cu: int, weight_dtype: str = "bf16", decode_packed: bool = True,
+                decode_t256: Sequence[str] = DECODE_SITES, fuse_norms: bool = True) -> DecodePlan:
+    """The GEMM launches of one decode step over ``Bn`` rows of a Llama-family decoder (``cfg``: LlamaCfg, ``k_aug``: the QKV
+    projection's K with its LoRA columns).
+    Weights are streamed once per step, from decode-packed copies of the layer weights (made once, on the first decode
+    step: a second 12.9 GB for Llama-2-7B — the prefill kernels keep the row-major originals; HBM is sized for both): a
+    wave-load is 1 KB contiguous instead of 16 rows x 64 B.  Per layer, rotating weights: Bn <= 8 the skinny kernel
+    (in-block split-K) 90-108 -> 79-87 us (5.1 TB/s at Bn = 1); 9..256 the decode tile (64-, 128- or 256-row blocks, about one
+    block per CU) 115-167 -> 97-132 us at 128 rows, 214 us at 256 (0.84 vs 1.06 us per row: a weight byte serves twice the rows);
+    above 256 the 64x64 LDS tile + split-K on the row-major weights."""
+    hd, I = cfg.hidden, cfg.ffn
+    shapes = dict(qkv=(3 * hd, k_aug), o=(hd, hd), gu=(2 * I, hd), down=(hd, I))
+
+    def sk(N, K):
+        tiles = ((N + 63) // 64) * ((Bn + 63) // 64)
+        s = max(1, min(K // 512, (2 * n_cu + tiles - 1) // tiles))
+        return min(s, 16)
+
+    def sk5(N, K):
+        return max(1, min(n_cu // ((N + 127) // 128), K // 512))
+    plan = {}
+    for name, (N, K) in shapes.items():
+        if Bn <= 8 and weight_dtype == "fp8":
+            tile, split, weight = "fp8w", 1, "fp8"    # FP8 weight mode: the fp8-weight skinny kernel (tile 6's arithmetic on W')
+        elif Bn <= 256 and decode_packed:
+            if Bn <= 8:
+                tile, split, weight = 6, 1, "packed"
+            else:
+                tile, split, weight = 5, sk5(N, K), "packed"
+                s256 = t256_split(N, K, n_cu) if Bn > 128 and name in decode_t256 else 0
+                if s256:
+                    tile, split, weight = 3, s256, "row"
+        elif Bn <= 8:
+            tile, split, weight = 4, 1, "row"
+        else:
+            tile, split, weight = 2, sk(N, K), "row"
+        plan[name] = GemmLaunch(tile, split, weight, N, K, fused_norm=fuse_norms and name in ("o", "down"))
+    plan["lm_head"] = GemmLaunch(lm_head_tile(Bn), 1, "row", cfg.vocab, hd)
+    nsplit = max(p.split_k for p in plan.values())
+    return DecodePlan(Bn, plan, nsplit * Bn * max(3 * hd, 2 * I) if nsplit > 1 else 0)
+
+
+# ================================================================================================
 # K9 + K10 + K11 (+K12 host side): Llama
 # ================================================================================================
 class LlamaHIP:
@@ -402,12 +486,12 @@ class LlamaHIP:
     decode_t256 = tuple(x for x in os.environ.get("ICL_DECODE_T256", "qkv,o,gu,down").split(",") if x)
 
     def _t256_split(self, N: int, K: int) -> int:
-        """Split-K of a 256-row decode GEMM on the 256x256 tile: one M-tile, ceil(N / 256) N-tiles; the slices fill ~80 % of the
-        CUs (a second partial round of blocks costs more than idle CUs) and stay >= 8 K-tiles deep (the pipeline's fill / drain);
-        0 = leave the GEMM on the decode tile (too few blocks either way)."""
-        tiles = (N + 255) // 256
-        split = min(K // 512, int(0.8 * self.n_cu) // tiles)
-        return split if split >= 2 and tiles * split >= 0.45 * self.n_cu else 0
+        return t256_split(N, K, self.n_cu)
+
+    def decode_plan(self, Bn: int) -> DecodePlan:
+        """The GEMM launches of a decode step over Bn rows on this device, in this runtime's weight mode (``decode_plan``)."""
+        return decode_plan(Bn, self.w.cfg, self.w.k_aug, self.n_cu, self.weight_dtype, self.decode_packed_weights,
+                           self.decode_t256, self.fuse_decode_norms)
 
     def __init__(self, w: PackedLlama, device, decode_packed: Optional[bool] = None, pack_now: bool = True,
                  weight_dtype: str = "bf16"):
@@ -461,34 +545,35 @@ class LlamaHIP:
 
     # ---- one decoder layer over M packed rows ---------------------------------------------------
     def _layer(self, ws: Workspace, L, h, M: int, tag: str, attn_fn, pos, seq_ids, kc, vc, max_len: int,
-               split: Optional[dict] = None, kv_rows_to_c: bool = True, xn_ready: bool = False, next_norm=None,
+               split: Optional[DecodePlan] = None, kv_rows_to_c: bool = True, xn_ready: bool = False, next_norm=None,
                attn_does_rope: bool = False, rope_fn=None):
         """``xn_ready``: the previous call has already written this layer's normalised input (decode: fused into the reduction
         of the previous down_proj).  ``next_norm`` = (gamma, out bf16 [M, >= hidden]) of the RMSNorm that follows this layer
         (the next layer's input norm into the same ``xn`` buffer, or the final norm): decode fuses it into the down_proj's
         split-K reduction, as it does the post-attention norm into the o_proj's (icl_gemm_rmsnorm_bf16).  ``rope_fn(qkv)``
-        replaces the stand-alone RoPE + cache append of a decode step (the FP8 KV cache's icl_rope_kv_fp8)."""
+        replaces the stand-alone RoPE + cache append of a decode step (the FP8 KV cache's icl_rope_kv_fp8).  ``split``: the decode
+        step's GEMM plan (``decode_plan``); None = prefill (the library's tile choice, no split-K)."""
         c, w = self.w.cfg, self.w
         hd, I, D, H = c.hidden, c.ffn, c.head_dim, c.n_heads
         xn = ws.get(tag + "xn", (M, w.k_aug), BF16, zero=True)   # augmentation tail stays zero
         qkv = ws.get(tag + "qkv", (M, 3 * hd), BF16)
         att = ws.get(tag + "att", (M, hd), BF16)
         act = ws.get(tag + "act", (M, I), BF16)
-        sk = split or {}
+        site = split.sites if split is not None else {}
+        ps = {k: site[k] if k in site else GemmLaunch(0, 1, "row", 0, 0) for k in DECODE_SITES}
 
-        def tile_of(name):          # per-GEMM kernel choice of a decode step ("tile_qkv" ...), else the step's common one
-            return sk.get("tile_" + name, sk.get("tile", 0))
+        def tile_of(name):
+            return ps[name].tile
 
-        def weight_of(name, idx, row_major):       # the decode tiles (5 / 6) stream the decode-packed copy, every other tile the original
-            t = tile_of(name)
-            if t == "fp8w":                        # FP8 weight mode, <= 8 rows: the fp8 decode-packed copy (+ its scales, scale_of)
+        def weight_of(name, idx, row_major):       # the plan's weight form: row-major, decode-packed (tiles 5 / 6) or fp8 (fp8w)
+            if ps[name].weight == "fp8":           # FP8 weight mode, <= 8 rows: the fp8 decode-packed copy (+ its scales, scale_of)
                 return L.fp8[idx][0]
-            return L.decode_packed[idx] if t in (5, 6) else row_major
+            return L.decode_packed[idx] if ps[name].weight == "packed" else row_major
 
         def scale_of(name, idx):
-            return L.fp8[idx][1] if tile_of(name) == "fp8w" else None
-        nsplit = max([v for k, v in sk.items() if not k.startswith("tile")], default=1)
-        wsk = ws.get(tag + "splitk", (nsplit * M * max(3 * hd, 2 * I),), F32) if nsplit > 1 else None
+            return L.fp8[idx][1] if ps[name].weight == "fp8" else None
+        sk = {k: p.split_k for k, p in ps.items()}
+        wsk = ws.get(tag + "splitk", (split.workspace,), F32) if split is not None and split.workspace else None
         if not xn_ready:
             B.rmsnorm(h, L.rms1, xn, c.rms_eps, N=hd)
         if L.lora_a is not None:   # x_aug[:, hd:hd+2r] = x @ (s*A)^T : a skinny GEMM for prefill, a GEMV-style kernel for decode
@@ -512,8 +597,7 @@ class LlamaHIP:
             elif not attn_does_rope:    # decode: RoPE + cache append run inside the attention launch (icl_attn_decode_rope_bf16)
                 B.rope_kv(qkv, hd, 2 * hd, w.rope_cos, w.rope_sin, pos, seq_ids, kc, vc, H, D, max_len, M=M)
         attn_fn(qkv, att)
-        fuse = split is not None and self.fuse_decode_norms
-        if fuse:     # decode: h += att Wo^T and the post-attention RMSNorm in one call (one kernel when the GEMM is split-K)
+        if ps["o"].fused_norm:     # decode: h += att Wo^T and the post-attention RMSNorm in one call (one kernel when the GEMM is split-K)
             B.gemm_rmsnorm(att, weight_of("o", 1, L.wo), h, L.rms2, c.rms_eps, xn, residual=h, split_k=sk.get("o", 1),
                            workspace=wsk, tile=tile_of("o"), N=hd, K=hd, w_scale=scale_of("o", 1))
         else:
@@ -522,7 +606,7 @@ class LlamaHIP:
             B.rmsnorm(h, L.rms2, xn, c.rms_eps, N=hd)
         B.gemm(xn, weight_of("gu", 2, L.wgu), act, swiglu=True, K=hd, split_k=sk.get("gu", 1), workspace=wsk,
                tile=tile_of("gu"), N=2 * I, w_scale=scale_of("gu", 2))
-        if fuse and next_norm is not None:
+        if ps["down"].fused_norm and next_norm is not None:
             B.gemm_rmsnorm(act, weight_of("down", 3, L.wdown), h, next_norm[0], c.rms_eps, next_norm[1], residual=h,
                            split_k=sk.get("down", 1), workspace=wsk, tile=tile_of("down"), N=hd, K=I, w_scale=scale_of("down", 3))
             return True
@@ -584,7 +668,7 @@ class LlamaHIP:
         out = ws.get(name, (R, c.vocab), F32)
         if not xn_ready:
             B.rmsnorm(h_rows, self.w.norm, xn, c.rms_eps)
-        B.gemm(xn, self.w.lm_head, out, tile=4 if R <= 8 else 0)
+        B.gemm(xn, self.w.lm_head, out, tile=lm_head_tile(R))
         return out
 
     # ---- K11: one decode step for Bn sequences -----------------------------------------------------
@@ -594,39 +678,9 @@ class LlamaHIP:
         Bn = next_ids.numel()
         h = self.embed(ws, next_ids, None, name="dc_h")
         H, D = c.n_heads, c.head_dim
-        # Weights are streamed once per step, from decode-packed copies of the layer weights (made once, on the first decode
-        # step: a second 12.9 GB for Llama-2-7B — the prefill kernels keep the row-major originals; HBM is sized for both): a
-        # wave-load is 1 KB contiguous instead of 16 rows x 64 B.  Per layer, rotating weights: Bn <= 8 the skinny kernel
-        # (in-block split-K) 90-108 -> 79-87 us (5.1 TB/s at Bn = 1); 9..256 the decode tile (64-, 128- or 256-row blocks, about one
-        # block per CU) 115-167 -> 97-132 us at 128 rows, 214 us at 256 (0.84 vs 1.06 us per row: a weight byte serves twice the rows);
-        # above 256 the 64x64 LDS tile + split-K on the row-major weights.
-        def sk(N, K):
-            tiles = ((N + 63) // 64) * ((Bn + 63) // 64)
-            s = max(1, min(K // 512, (2 * self.n_cu + tiles - 1) // tiles))
-            return min(s, 16)
-
-        def sk5(N, K):
-            return max(1, min(self.n_cu // ((N + 127) // 128), K // 512))
-        if Bn <= 8 and self.weight_dtype == "fp8":
-            split = dict(tile="fp8w")    # FP8 weight mode: the fp8-weight skinny kernel (tile 6's arithmetic on W', half the bytes)
-        elif Bn <= 256 and self.decode_packed_weights:
+        split = self.decode_plan(Bn)
+        if any(p.weight == "packed" for p in split.sites.values()):
             self.ensure_decode_packed()
-            if Bn <= 8:
-                split = dict(tile=6)
-            else:
-                split = dict(qkv=sk5(3 * c.hidden, self.w.k_aug), o=sk5(c.hidden, c.hidden), gu=sk5(2 * c.ffn, c.hidden),
-                             down=sk5(c.hidden, c.ffn), tile=5)
-                if Bn > 128:
-                    for name, (N, K) in (("qkv", (3 * c.hidden, self.w.k_aug)), ("o", (c.hidden, c.hidden)),
-                                         ("gu", (2 * c.ffn, c.hidden)), ("down", (c.hidden, c.ffn))):
-                        s256 = self._t256_split(N, K) if name in self.decode_t256 else 0
-                        if s256:
-                            split[name], split["tile_" + name] = s256, 3
-        elif Bn <= 8:
-            split = dict(tile=4)
-        else:
-            split = dict(qkv=sk(3 * c.hidden, self.w.k_aug), o=sk(c.hidden, c.hidden), gu=sk(2 * c.ffn, c.hidden),
-                         down=sk(c.hidden, c.ffn), tile=2)
 
         layers = self.w.layers
         xn_next = ws.get("dc_xn", (Bn, self.w.k_aug), BF16, zero=True)          # the layers' normalised-input buffer (_layer's tag + "xn")

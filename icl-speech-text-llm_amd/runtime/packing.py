@@ -279,12 +279,17 @@ class PackedLlama:
     rope_sin: torch.Tensor
 
 
+def llama_k_aug(cfg: LlamaCfg) -> int:
+    """K of the packed QKV projection: hidden + the LoRA K-augmentation columns (when the decoder has LoRA)."""
+    return cfg.hidden + (LORA_PAD if cfg.lora_rank else 0)
+
+
 def pack_llama(sd: SD, cfg: LlamaCfg, device, prefix: str = "llama_model.", consume: bool = False) -> PackedLlama:
     """HF causal-LM names under `prefix`: model.embed_tokens, model.layers.{i}.*, model.norm, lm_head (Llama and Qwen2 alike)."""
     h, I, r = cfg.hidden, cfg.ffn, cfg.lora_rank
     assert h % 64 == 0 and I % 64 == 0 and cfg.head_dim in (64, 128)
     p = prefix + "model."
-    k_aug = h + (LORA_PAD if r else 0)
+    k_aug = llama_k_aug(cfg)
     assert len(cfg.lora_targets) * r <= LORA_PAD and all(t in ("q_proj", "k_proj", "v_proj") for t in cfg.lora_targets)
     layers = []
     for i in range(cfg.n_layers):
