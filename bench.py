@@ -15,11 +15,15 @@ logits bf16 [b, V]) of every rank.  `python bench.py --gpus N` (N > 1, not alrea
 itself through `python -m torch.distributed.run` as a CHILD process before anything touches the GPU and relays its output
 and exit code; under an external launcher (WORLD_SIZE set) it is simply one rank.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` (dominant kernel: the 256x256 bf16 MFMA
-GEMM, timed live with HIP events on the launch stream inside the timed region) and, at N=1, `cpu_baseline` (the fp32 CPU
-oracle on one utterance of the same workload) and `parity` (the same utterance at FULL size against the oracle with the
-bf16 rounding hook, stage by stage, all 10 greedy decisions teacher-forced; plus a decisive-margin weight set on which
-the ids must match exactly).  A parity bound exceeded makes the process exit 4 after printing the line.
+A plain run does only what the headline figure needs: it builds the model, makes the inputs resident, runs the warm-up and
+the timed steps, writes --dump-outputs if asked, and prints ONE JSON line on rank 0 (contract in the task statement) incl.
+`roofline` (dominant kernel: the 256x256 bf16 MFMA GEMM, timed live with HIP events on the launch stream inside the timed
+region).  `--full` adds the side legs after that: `phases` (one extra untimed step with HIP events at the phase boundaries),
+`through_plugin` (the path through the reference-compatible plugin, at every N), and at N=1 `cpu_baseline` (the fp32 CPU
+oracle on one utterance of the same workload), `parity` (the same utterance at FULL size against the oracle with the bf16
+rounding hook, stage by stage, all 10 greedy decisions teacher-forced; plus a decisive-margin weight set on which the ids
+must match exactly) and `other_workloads` (configs 4 / 5, 4-beam search, batch 1).  A parity bound exceeded makes the
+process exit 4 after printing the line.
 """
 from __future__ import annotations
 
@@ -82,31 +86,35 @@ def host_cores() -> int:
     return n
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=256, help="utterances per step per GPU (prefilled 128 at a time, decoded together)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle legs (cpu_baseline + parity)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's own work, also run the side legs: the per-phase step, the through-plugin "
+                         "leg, the CPU baseline and full-size parity (N = 1) and the other workloads (N = 1); a few minutes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle legs (cpu_baseline + parity)")
     ap.add_argument("--cpu-baseline-full", action="store_true",
-                    help="BASELINE.md §3 in full: 16 utterances at 8 threads and at all cores (median), plus config 1 "
-                         "(text_only, 160 positions); ~10+ minutes of host time, result also written to --cpu-baseline-out")
+                    help="implies --full; BASELINE.md §3 in full: 16 utterances at 8 threads and at all cores (median), plus "
+                         "config 1 (text_only, 160 positions); ~10+ minutes of host time, result also written to --cpu-baseline-out")
     ap.add_argument("--cpu-baseline-out", default=None)
     ap.add_argument("--no-gemm-profile", action="store_true", help="no per-launch HIP events in the timed region (roofline = null)")
     ap.add_argument("--no-graphs", action="store_true", help="run the decode loop eagerly (rocprofv3 --pmc crashes on HIP-graph capture)")
-    ap.add_argument("--no-phases", action="store_true", help="skip the extra untimed per-phase step (profiling passes: fewer dispatches)")
+    ap.add_argument("--no-phases", action="store_true", help="with --full: skip the extra untimed per-phase step (profiling passes: fewer dispatches)")
     ap.add_argument("--tiny", action="store_true", help="miniature model (smoke only; not a valid bench number)")
     ap.add_argument("--through-plugin", action="store_true",
-                    help="(default on the headline workload, at every N: with N > 1 each rank runs it on its own shard) also time the path through the reference-compatible plugin: "
-                         "ModelFactory -> SalmonProcessor / DataLoader -> generate_output (H2D, tokenisation, batch_decode inside "
-                         "the timed region; SURVEY.md §8d)")
+                    help="(on by default with --full on the headline workload, at every N: with N > 1 each rank runs it on its own "
+                         "shard; this flag runs it without --full too, and with --tiny) also time the path through the "
+                         "reference-compatible plugin: ModelFactory -> SalmonProcessor / DataLoader -> generate_output (H2D, "
+                         "tokenisation, batch_decode inside the timed region; SURVEY.md §8d)")
     ap.add_argument("--no-through-plugin", action="store_true", help="skip the plugin-path leg")
     ap.add_argument("--plugin-workers", type=int, default=8, help="item-pipeline workers of the plugin-path leg (capped at cores per rank - 1)")
     ap.add_argument("--plugin-rows", type=int, default=0, help="distinct clips in the on-disk dataset of the plugin-path leg (default min(256, batch))")
     ap.add_argument("--plugin-batch", type=int, default=None, help="batch size of the plugin-path leg (default: --batch, the micro-batch of the runtime number)")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip the BASELINE.json configs 4 and 5 (1-GPU halves) that the default N = 1 run appends after the headline legs")
+                    help="with --full: skip the BASELINE.json configs 4 and 5 (1-GPU halves) that an N = 1 run appends after the headline legs")
     ap.add_argument("--other-batch", type=int, default=128, help="micro-batch of the configs 4 / 5 legs")
     ap.add_argument("--workload", default="c2", choices=["c2", "c2s", "c4", "c5"],
                     help="BASELINE.md §4: c2 = headline (default); c2s = 5 speech exemplars; c4 = Qwen2-Audio HVB; "
@@ -115,12 +123,24 @@ def parse():
                     help="after the timed steps write what the last timed step returned (utterance indices, generated ids, "
                          "first-step logits) as DIR/<name>.npy in float32, at most 64 MB in all, for output-by-output A/B "
                          "of two builds on the same arguments")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be >= 1")
     if args.warmup < 0:
         ap.error("--warmup must be >= 0")
+    if args.cpu_baseline_full:
+        args.full = True
     return args
+
+
+def side_legs(args, world: int, rank: int) -> dict:
+    """The legs this rank runs besides the headline line's own work (build, inputs, warm-up, timed steps, --dump-outputs):
+    none in a plain run, except the plugin leg when --through-plugin asks for it."""
+    c2 = args.workload == "c2"
+    return {"phases": rank == 0 and args.full and c2 and not args.tiny and not args.no_phases,
+            "through_plugin": c2 and not args.no_through_plugin and (args.through_plugin or (args.full and not args.tiny)),
+            "cpu": world == 1 and rank == 0 and args.full and c2 and not args.no_cpu_baseline,
+            "other_workloads": world == 1 and args.full and c2 and not args.tiny and not args.no_other_workloads}
 
 
 DUMP_BUDGET_BYTES = 64_000_000 - 64 * 1024     # 64 MB in all, .npy headers included
@@ -211,27 +231,47 @@ def workload_roofline(wl: str, utt_per_s: float, profile, elapsed: float):
     return out
 
 
-def synth_utterances(first: int, count: int, vocab: int):
-    """SURVEY.md §8d synthetic inputs: audio N(0,0.1^2) clipped, default_rng(1234+i); ids uniform [3,32000), default_rng(99+i)."""
-    wav = np.empty((count, 480000), dtype=np.float32)
+CLIP_SAMPLES = 480000      # 30 s at 16 kHz
+
+
+def synth_clip(seed: int) -> np.ndarray:
+    """One synthetic 30 s waveform: N(0, 0.1^2) from default_rng(seed), clipped to [-1, 1], float32."""
+    return np.clip(np.random.default_rng(seed).normal(0.0, 0.1, CLIP_SAMPLES), -1.0, 1.0).astype(np.float32)
+
+
+def clip_seeds(workload: str, first: int, count: int):
+    """The synth_clip seeds of utterances first .. first + count - 1 of `workload`, in the row order of the wav arrays of
+    synth_utterances (c2) and synth_workload (the others)."""
+    if workload == "c2":
+        return [1234 + i for i in range(first, first + count)]
+    n_audio = WORKLOADS[workload][2]
+    return [1234 + i * 7 + a for i in range(first, first + count) for a in range(n_audio)]
+
+
+def synth_utterances(first: int, count: int, vocab: int, audio: bool = True):
+    """SURVEY.md §8d synthetic inputs: audio N(0,0.1^2) clipped, default_rng(1234+i); ids uniform [3,32000), default_rng(99+i).
+    audio=False: the ids only (wav is None; the clips come from ClipMaker)."""
+    wav = np.empty((count, CLIP_SAMPLES), dtype=np.float32) if audio else None
     ids = np.empty((count, S_TEXT), dtype=np.int64)
     for j in range(count):
         i = first + j
-        wav[j] = np.clip(np.random.default_rng(1234 + i).normal(0.0, 0.1, 480000), -1.0, 1.0).astype(np.float32)
+        if audio:
+            wav[j] = synth_clip(1234 + i)
         ids[j] = np.random.default_rng(99 + i).integers(3, min(32000, vocab - 1), S_TEXT)
     return wav, ids
 
 
-def synth_workload(first: int, count: int, vocab: int, text_lens, n_audio: int, audio_tokens: int):
+def synth_workload(first: int, count: int, vocab: int, text_lens, n_audio: int, audio_tokens: int, audio: bool = True):
     """Generalisation of synth_utterances for the non-headline workloads: per utterance `n_audio` clips and a prompt of
-    text_lens[i % len] tokens with the audio slots spread through it (exemplars first, query slot 8 tokens before the end)."""
+    text_lens[i % len] tokens with the audio slots spread through it (exemplars first, query slot 8 tokens before the end).
+    audio=False: the prompts only (wav is None)."""
     from icl_speech_text_llm_amd.runtime.salmonn import speech_segment
-    wav = np.empty((count * n_audio, 480000), dtype=np.float32)
+    wav = np.empty((count * n_audio, CLIP_SAMPLES), dtype=np.float32) if audio else None
     prompts = []
     for j in range(count):
         i = first + j
-        for a in range(n_audio):
-            wav[j * n_audio + a] = np.clip(np.random.default_rng(1234 + i * 7 + a).normal(0.0, 0.1, 480000), -1.0, 1.0)
+        for a in range(n_audio if audio else 0):
+            wav[j * n_audio + a] = synth_clip(1234 + i * 7 + a)
         n = text_lens[i % len(text_lens)]
         ids = np.random.default_rng(99 + i).integers(3, min(32000, vocab - 1), n).tolist()
         cuts = [int((n - 8) * (k + 1) / n_audio) for k in range(n_audio)]
@@ -243,6 +283,64 @@ def synth_workload(first: int, count: int, vocab: int, text_lens, n_audio: int, 
         segs.append(ids[prev:])
         prompts.append([sg for sg in segs if not (isinstance(sg, list) and not sg)])
     return wav, prompts
+
+
+_CLIP_RING = None      # a ClipMaker worker's view of the shared ring, [depth, rows, CLIP_SAMPLES]
+
+
+def _clip_worker_init(ring, depth: int, rows: int):
+    global _CLIP_RING
+    _CLIP_RING = np.frombuffer(ring, dtype=np.float32).reshape(depth, rows, CLIP_SAMPLES)
+
+
+def _clip_worker_fill(slot: int, row: int, seeds):
+    for j, seed in enumerate(seeds):
+        _CLIP_RING[slot, row + j] = synth_clip(seed)
+
+
+class ClipMaker:
+    """The synth_clip waveforms of every step's seeds (`step_seeds[s]`), made ahead of the caller.  numpy's generator holds the
+    GIL and one core makes a clip in ~8 ms (2048 clips at the default 6 + 2 steps), so with workers > 1 they are made by spawned
+    processes (never forked: the caller holds the GPU) into a shared ring of `depth` steps.  take(s), in step order, returns
+    step s's float32 [rows, CLIP_SAMPLES] array, valid until the next take()."""
+
+    def __init__(self, step_seeds, workers: int, depth: int = 3):
+        self.step_seeds = step_seeds
+        self.pool = None
+        if workers <= 1 or not step_seeds:
+            return
+        import ctypes
+        import multiprocessing
+        from concurrent.futures import ProcessPoolExecutor
+        ctx = multiprocessing.get_context("spawn")
+        self.depth = min(depth, len(step_seeds))
+        rows = max(len(s) for s in step_seeds)
+        ring = ctx.RawArray(ctypes.c_float, self.depth * rows * CLIP_SAMPLES)   # /dev/shm if it has room, else a temp file
+        self.ring = np.frombuffer(ring, dtype=np.float32).reshape(self.depth, rows, CLIP_SAMPLES)
+        self.chunk = max(1, -(-rows // (2 * workers)))
+        self.pool = ProcessPoolExecutor(workers, mp_context=ctx, initializer=_clip_worker_init, initargs=(ring, self.depth, rows))
+        self.pending = {s: self._submit(s) for s in range(self.depth)}
+
+    def _submit(self, s: int):
+        seeds = self.step_seeds[s]
+        return [self.pool.submit(_clip_worker_fill, s % self.depth, r, seeds[r:r + self.chunk])
+                for r in range(0, len(seeds), self.chunk)]
+
+    def take(self, s: int) -> np.ndarray:
+        seeds = self.step_seeds[s]
+        if self.pool is None:
+            return np.stack([synth_clip(seed) for seed in seeds])
+        nxt = s - 1 + self.depth          # step s - 1's slot is free now: refill it
+        if s >= 1 and nxt < len(self.step_seeds):
+            self.pending[nxt] = self._submit(nxt)
+        for f in self.pending.pop(s):     # KeyError: take() out of step order
+            f.result()
+        return self.ring[s % self.depth, :len(seeds)]
+
+    def close(self):
+        if self.pool is not None:
+            self.pool.shutdown(cancel_futures=True)
+            self.pool = None
 
 
 def build_prompts(ids: np.ndarray):
@@ -749,41 +847,49 @@ def main():
         cfg = QwenAudioCfg.tiny() if args.tiny else QwenAudioCfg()
     else:
         cfg = SalmonnCfg.tiny() if args.tiny else (SalmonnCfg.llama2_13b() if args.workload == "c5" else SalmonnCfg.llama2_7b())
-    log(f"building {'tiny ' if args.tiny else ''}{wl_desc} synthetic weights on {dev} ...")
-    t_build = time.perf_counter()
-    if is_qwen:
-        sd = synth.qwen_audio_state(cfg, seed=0, device=dev, dtype=torch.bfloat16)
-        rt = QwenAudioRuntime(cfg, dict(sd), device=dev)
-    else:
-        sd = synth.salmonn_state(cfg, seed=0, device=dev, dtype=torch.bfloat16)   # identical replica on every rank
-        rt = SalmonnRuntime(cfg, dict(sd), device=dev)
-    if args.no_graphs:
-        rt.use_graphs = False
-    want_cpu = (world == 1 and rank == 0 and not args.no_cpu_baseline and args.workload == "c2")
-    if not want_cpu:
-        del sd
-    torch.cuda.synchronize()
-    t_build = time.perf_counter() - t_build
-    log(f"model packed in {t_build:.1f} s ({torch.cuda.memory_allocated(dev) / 2**30:.1f} GiB allocated)")
-
-    # ---- inputs, resident in HBM before the timed region ----------------------------------------
+    legs = side_legs(args, world, rank)
     Bm, total_steps = args.batch, args.warmup + args.steps
-    vocab = cfg.llm.vocab if is_qwen else cfg.llama.vocab
-    audio_tokens = 750 if is_qwen else N_AUDIO_TOK
-    wavs, prompts, firsts = [], [], []
-    lens = [480000] * (Bm * wl_naudio)
-    for s in range(total_steps):
-        first = (s * world + rank) * Bm           # utterance i belongs to rank (i // Bm) % world of step i // (Bm*world)
-        firsts.append(first)
-        if args.workload == "c2":
-            w, ids = synth_utterances(first, Bm, vocab)
-            prompts.append(build_prompts(ids))
-            if s == 0:
-                w0, ids0 = w[0].copy(), ids[0].copy()
+    # utterance i belongs to rank (i // Bm) % world of step i // (Bm*world)
+    firsts = [(s * world + rank) * Bm for s in range(total_steps)]
+    # the input waveforms are made on the host while the model is built on the GPU
+    clips = ClipMaker([clip_seeds(args.workload, first, Bm) for first in firsts], workers=min(16, cores_per_rank))
+    try:
+        log(f"building {'tiny ' if args.tiny else ''}{wl_desc} synthetic weights on {dev} ...")
+        t_build = time.perf_counter()
+        if is_qwen:
+            sd = synth.qwen_audio_state(cfg, seed=0, device=dev, dtype=torch.bfloat16)
+            rt = QwenAudioRuntime(cfg, dict(sd), device=dev)
         else:
-            w, pr = synth_workload(first, Bm, vocab, wl_text, wl_naudio, audio_tokens)
-            prompts.append(pr)
-        wavs.append(torch.from_numpy(w).to(dev))
+            sd = synth.salmonn_state(cfg, seed=0, device=dev, dtype=torch.bfloat16)   # identical replica on every rank
+            rt = SalmonnRuntime(cfg, dict(sd), device=dev)
+        if args.no_graphs:
+            rt.use_graphs = False
+        want_cpu = legs["cpu"]
+        if not want_cpu:
+            del sd
+        torch.cuda.synchronize()
+        t_build = time.perf_counter() - t_build
+        log(f"model packed in {t_build:.1f} s ({torch.cuda.memory_allocated(dev) / 2**30:.1f} GiB allocated)")
+
+        # ---- inputs, resident in HBM before the timed region ----------------------------------------
+        vocab = cfg.llm.vocab if is_qwen else cfg.llama.vocab
+        audio_tokens = 750 if is_qwen else N_AUDIO_TOK
+        wavs, prompts = [], []
+        lens = [480000] * (Bm * wl_naudio)
+        for s in range(total_steps):
+            if args.workload == "c2":
+                _, ids = synth_utterances(firsts[s], Bm, vocab, audio=False)
+                prompts.append(build_prompts(ids))
+            else:
+                _, pr = synth_workload(firsts[s], Bm, vocab, wl_text, wl_naudio, audio_tokens, audio=False)
+                prompts.append(pr)
+            w = clips.take(s)
+            if s == 0 and args.workload == "c2":
+                w0, ids0 = w[0].copy(), ids[0].copy()
+            wavs.append(torch.from_numpy(w).to(dev))      # a synchronous copy: the ring slot may be refilled after it
+            del w
+    finally:
+        clips.close()
     # §8e result row: (utterance index, gen_ids int32 [10], gen_len, first-step logits bf16 [V]); ONE all-gather per step
     packer = dp.result_packer(NEW_TOKENS, vocab)
     cdev = dp.collective_device(dist, dev) if world > 1 else dev
@@ -911,7 +1017,7 @@ def main():
                 f"{fl / tt / 1e12:7.1f} TF/s, {100 * tt / elapsed:5.1f}% of step time")
     # ---- per-phase timing: ONE extra, untimed step with HIP events at the phase boundaries -----------------
     phases = None
-    if rank == 0 and args.workload == "c2" and not args.tiny and not args.no_phases:
+    if legs["phases"]:
         marks = {k: torch.cuda.Event(enable_timing=True) for k in ("enc_start", "prefill_start", "prefill_end", "decode_end")}
         rt.phase_marks = marks
         marks["enc_start"].record()
@@ -937,7 +1043,7 @@ def main():
         }
         log(f"phases: encoder {t_enc * 1e3:.1f} ms, prefill {t_pre * 1e3:.1f} ms, decode {t_dec * 1e3:.1f} ms")
     parity_failed = False
-    want_plugin = args.workload == "c2" and not args.no_through_plugin and (args.through_plugin or not args.tiny)
+    want_plugin = legs["through_plugin"]
     plugin_block = None
     if world > 1 and want_plugin:
         # every rank: hand the runtime leg's model and workspace back first (the plugin builds its own replica), then the
@@ -977,7 +1083,7 @@ def main():
         if plugin_block is not None:
             out["through_plugin"] = plugin_block
             log(f"through-plugin (all ranks): {json.dumps({k: v for k, v in plugin_block.items() if k not in ('per_rank', 'note')})}")
-        if world == 1:
+        if world == 1 and (want_plugin or want_cpu or legs["other_workloads"]):
             # the side legs below build a second model (plugin) and a third set of decoder weights (margin parity) next to this
             # one: hand the 94 GiB of micro-batch-256 workspace back first (the parity legs run one utterance and re-grow
             # what they need)
@@ -1036,7 +1142,7 @@ def main():
                 cb["tokens_match_gpu_on_margin_weights"] = par["margin_weights"]["tokens_match"]
                 out["parity"] = par
                 parity_failed = not par["ok"]
-        if world == 1 and args.workload == "c2" and not args.tiny and not args.no_other_workloads:
+        if legs["other_workloads"]:
             # last: the parent's model, workspace and side models are released first (the children build their own)
             try:
                 del rt

@@ -6,6 +6,6 @@ for round in 1 2 3; do
 done
 for round in 1 2; do
   for f in 1 0; do
-    echo -n "round $round fuse=$f batch256: "; ICL_FUSE_DECODE_ROPE=$f python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-through-plugin --no-other-workloads 2>&1 | grep -E "phases:"
+    echo -n "round $round fuse=$f batch256: "; ICL_FUSE_DECODE_ROPE=$f python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-through-plugin --no-other-workloads 2>&1 | grep -E "phases:"
   done
 done
