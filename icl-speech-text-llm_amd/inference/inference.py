@@ -98,6 +98,9 @@ def parse_args(argv=None):
     p.add_argument("--synthetic_items", type=int, default=64, help="items per task of the synthetic dataset")
     p.add_argument("--arch", type=str, default=None, help="7b | 13b | tiny (default: inferred from llama_path)")
     p.add_argument("--max_new_tokens", type=int, default=10)
+    p.add_argument("--constrain_labels", type=_bool, default=False,
+                   help="label-constrained greedy decoding: every row of a task with a closed label set follows a token automaton "
+                        "of its valid answers (one label, or a ', '-joined list), so the prediction is always a valid answer")
     p.add_argument("--llm_weights", type=str, default="bf16", choices=["bf16", "fp8"],
                    help="decoder GEMM weights: bf16, or fp8 = the opt-in FP8 weight mode (each weight replaced by its FP8 rounding; "
                         "decode at <= 8 rows streams half the bytes)")
@@ -288,6 +291,8 @@ def run_inference(args) -> Dict[str, Any]:
                 b_idx = indices[batch_idx * args.batch_size: batch_idx * args.batch_size + n_b]
                 try:
                     batch["max_new_tokens"] = args.max_new_tokens      # SALMONN reads it from the batch dict (custom_salmon.py:708)
+                    if getattr(args, "constrain_labels", False):
+                        batch["constrain_labels"] = True
                     t0 = time.time()
                     res = model.generate_ids(batch, want_first_logits=True)
                     outputs = model.decode_ids(res.tokens)

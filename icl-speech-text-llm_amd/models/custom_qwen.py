@@ -284,16 +284,17 @@ class CustomQwen(BaseModel):
 
     def generate_ids(self, batch: Dict[str, Any], want_first_logits: bool = False):
         """Batch dict -> ``GenerateResult`` (new token ids, first-step logits on request); see CustomSALMONN.generate_ids."""
+        g = dict(self.generation_config)
+        eos = g.get("eos_token_id", self.cfg.llm.eos_id)          # an id or HF's list form (Qwen2-Audio: [151645, 151643])
+        constraint = self._label_constraint(batch, eos)            # batch key ``constrain_labels`` (absent = off); before any launch
         rows, segs, speech, _, _ = self._rows_and_audio(batch)
         # The reference calls generate(max_new_tokens=10) and takes EVERY other knob from the model's generation config
         # (custom_qwen.py:227-233): keys a caller puts in the batch dict — MultiTaskModel's max_new_tokens / num_beams / do_sample /
         # temperature among them — never reach HF there, so they are not read here either.  ``self.generation_config`` (the
         # checkpoint folder's generation_config.json, the constructor kwarg, or assigned afterwards) is the one place to set them,
-        # ``max_new_tokens`` included; a sampling ``generator`` (not a reference key) may ride in the batch.
-        g = dict(self.generation_config)
+        # ``max_new_tokens`` included; a sampling ``generator`` and ``constrain_labels`` (not reference keys) may ride in the batch.
         if "generator" in batch:
             g["generator"] = batch["generator"]
-        eos = g.get("eos_token_id", self.cfg.llm.eos_id)          # an id or HF's list form (Qwen2-Audio: [151645, 151643])
         res = self.runtime.generate(segs, speech, max_new_tokens=int(g.get("max_new_tokens", 10)),
                                     eos_id=tuple(eos) if isinstance(eos, (list, tuple)) else int(eos),
                                     pad_id=int(g.get("pad_token_id", self.cfg.llm.pad_id)),
@@ -301,13 +302,27 @@ class CustomQwen(BaseModel):
                                     top_p=float(g.get("top_p", 1.0)), top_k=int(g.get("top_k", 50)),
                                     repetition_penalty=float(g.get("repetition_penalty", 1.0)), generator=g.get("generator"),
                                     want_first_logits=want_first_logits, overlong="drop", num_beams=int(g.get("num_beams", 1)),
-                                    length_penalty=float(g.get("length_penalty", 1.0)))
+                                    length_penalty=float(g.get("length_penalty", 1.0)), constraint=constraint)
         self.last_dropped_rows = tuple(res.dropped)      # rows over max_pos cost their own utterance only (see CustomSALMONN)
         if res.dropped:
             logger.error("rows %s of this batch were not generated: prompt + new tokens exceed max_pos %d", list(res.dropped),
                          self.cfg.llm.max_pos)
         self.batch_counter += 1
         return res
+
+    def _label_constraint(self, batch: Dict[str, Any], eos):
+        """See CustomSALMONN._label_constraint; the automaton's EOS is the first id of the generation config's EOS list."""
+        if not batch.get("constrain_labels", False):
+            return None
+        if "dataset_type" not in batch:
+            raise ValueError("constrain_labels needs the batch's dataset_type column: the label set is the task's")
+        from ..runtime.constraints import constraint_for_batch
+        types = batch["dataset_type"]
+        ids = batch["input_ids"]
+        types = list(types) if isinstance(types, (list, tuple)) else [types] * (1 if ids.dim() == 1 else ids.shape[0])
+        cache = self.__dict__.setdefault("_label_automata", {})
+        first_eos = int(eos[0]) if isinstance(eos, (list, tuple)) else int(eos)
+        return constraint_for_batch(cache, self.input_processor.tokenizer, types, first_eos, self.cfg.llm.vocab)
 
     def decode_ids(self, tokens) -> List[str]:
         return self.input_processor.batch_decode(tokens, skip_special_tokens=True, clean_up_tokenization_spaces=False)

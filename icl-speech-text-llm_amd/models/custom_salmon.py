@@ -578,6 +578,7 @@ class CustomSALMONN(BaseModel):
         fixed-shape tensors and decodes on rank 0."""
         t0 = time.perf_counter()
         samples = self._host_counts(samples)
+        constraint = self._label_constraint(samples)           # batch key ``constrain_labels`` (absent = off); before any launch
         speech_embeds, _, example_embeds, _ = self.get_speech_embeddings(samples)
         t1 = time.perf_counter()
         num_examples = samples.get("num_examples", torch.zeros(len(samples["prompt"]), dtype=torch.long))
@@ -593,7 +594,7 @@ class CustomSALMONN(BaseModel):
                                     repetition_penalty=float(samples.get("repetition_penalty", 1.0)),
                                     generator=samples.get("generator"), want_first_logits=want_first_logits,
                                     overlong="drop", num_beams=int(samples.get("num_beams", 1)),
-                                    length_penalty=float(samples.get("length_penalty", 1.0)))
+                                    length_penalty=float(samples.get("length_penalty", 1.0)), constraint=constraint)
         # a prompt over max_pos costs ITS utterance, not the batch (the reference runs batch 1: inference/inference.py:370-373);
         # such rows come back pad-filled and are listed here for the caller (the CLI reports them as missing indices)
         self.last_dropped_rows = tuple(res.dropped)
@@ -605,6 +606,20 @@ class CustomSALMONN(BaseModel):
         self.last_stage_seconds = {"speech_launch": t1 - t0, "segments": t2 - t1, "generate": time.perf_counter() - t2}
         self.batch_counter += 1
         return res
+
+    def _label_constraint(self, samples: Dict[str, Any]):
+        """``(automaton, start states)`` for a batch that sets ``constrain_labels`` (one grammar per row, by its ``dataset_type``),
+        else ``None``.  Automata are built once per set of dataset types from this model's tokenizer and kept."""
+        if not samples.get("constrain_labels", False):
+            return None
+        if "dataset_type" not in samples:
+            raise ValueError("constrain_labels needs the batch's dataset_type column: the label set is the task's")
+        from ..runtime.constraints import constraint_for_batch
+        types = samples["dataset_type"]
+        types = list(types) if isinstance(types, (list, tuple)) else [types] * len(samples["prompt"])
+        cache = self.__dict__.setdefault("_label_automata", {})
+        return constraint_for_batch(cache, self.llama_tokenizer, types, self.llama_tokenizer.eos_token_id,
+                                    self.cfg.llama.vocab)
 
     def decode_ids(self, tokens) -> List[str]:
         return self.llama_tokenizer.batch_decode(tokens, skip_special_tokens=True)

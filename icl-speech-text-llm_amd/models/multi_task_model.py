@@ -1,7 +1,7 @@
 """Per-task wrapper around one model — mirror of the reference's ``models/multi_task_model.py:7-162``.
 
 ``task_configs[task]`` may hold a ``prompt_template`` and generation knobs (``max_new_tokens``, ``num_beams``,
-``do_sample``, ``temperature``); ``generate_output`` takes the task of the first batch row, makes it current and writes its
+``do_sample``, ``temperature``, and this path's opt-in ``constrain_labels``); ``generate_output`` takes the task of the first batch row, makes it current and writes its
 knobs into the batch before delegating (:130-149); ``forward`` swaps each row's template for its task's when the batch
 carries a ``task`` column (:108-120) and tags the outputs with the current task.  Unlike the reference's plain class, this
 wrapper forwards ``to`` / ``eval`` / attribute reads to the wrapped model, so ``ModelFactory.create_model(multi_task=True,
@@ -79,6 +79,8 @@ class MultiTaskModel:
             cfg = self.task_configs[task]
             samples.update({"max_new_tokens": cfg.get("max_new_tokens", 10), "num_beams": cfg.get("num_beams", 1),
                             "do_sample": cfg.get("do_sample", False), "temperature": cfg.get("temperature", 0.8)})
+            if "constrain_labels" in cfg:          # opt-in label-constrained decoding; a key the caller put in the batch stays
+                samples["constrain_labels"] = cfg["constrain_labels"]
         return self.model.generate_output(samples)
 
     @classmethod

@@ -83,6 +83,9 @@ _SIGNATURES = {
                                             c_int32, c_int32, c_void_p]),
     "icl_argmax_eos": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                c_int32, c_int32, c_void_p, c_void_p]),
+    "icl_argmax_fsm": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                               c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
+                               c_void_p, c_void_p]),
     "icl_sample_eos": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int32,
                                c_float, c_float, c_int32, c_float, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
@@ -489,6 +492,26 @@ def argmax_eos(logits, eos_id, pad_id: int, finished, out_tokens, step: int, nex
                                          logits.shape[1] if V is None else V, e1, e2, pad_id, finished.data_ptr(),
                                          out_tokens.data_ptr(), out_tokens.stride(0), step, next_ids.data_ptr(),
                                          _stream()), "icl_argmax_eos")
+
+
+def argmax_fsm(logits, tables, state, steps_left: int, eos_id, pad_id: int, finished, out_tokens, step: int, next_ids,
+               out_logprob=None, V=None):
+    """Constrained greedy decode tail (icl_argmax_fsm).  ``tables`` = the device copy of a ``constraints.LabelAutomaton``
+    (``.state_off`` / ``.edge_tok`` / ``.edge_next`` / ``.state_dist`` int32, ``.n_states``, ``.n_edges``, ``.vocab``); ``state``
+    int32 [B] holds each row's state (-1 = free row) and is advanced in place; ``out_logprob`` f32 shaped like ``out_tokens``."""
+    _require_gpu(logits, tables.state_off, tables.edge_tok, tables.edge_next, tables.state_dist, state, finished, out_tokens,
+                 next_ids, out_logprob)
+    V = logits.shape[1] if V is None else V
+    if tables.vocab > V:           # the kernel reads logits[b][edge_tok[e]]: an automaton over a larger vocabulary is a caller's error
+        raise ValueError(f"automaton built for a vocabulary of {tables.vocab} ids used on logits of {V}")
+    assert logits.dtype == torch.float32 and state.dtype == torch.int32 and state.numel() == logits.shape[0]
+    assert out_logprob is None or (out_logprob.dtype == torch.float32 and out_logprob.stride(0) == out_tokens.stride(0))
+    e1, e2 = _eos_pair(eos_id)
+    _check(load_library().icl_argmax_fsm(logits.data_ptr(), logits.stride(0), logits.shape[0], V, tables.state_off.data_ptr(),
+                                         tables.edge_tok.data_ptr(), tables.edge_next.data_ptr(), tables.state_dist.data_ptr(),
+                                         tables.n_states, tables.n_edges, state.data_ptr(), steps_left, e1, e2, pad_id,
+                                         finished.data_ptr(), out_tokens.data_ptr(), out_tokens.stride(0), step,
+                                         next_ids.data_ptr(), _ptr(out_logprob), _stream()), "icl_argmax_fsm")
 
 
 def sample_eos(logits, work, uniforms, eos_id, pad_id: int, finished, out_tokens, step: int, next_ids, *,

@@ -35,6 +35,8 @@ class GenerateResult:
     first_logits: Optional[torch.Tensor] = None  # f32 [B, V] (device) logits of the first generated position
     step_logits: Optional[torch.Tensor] = None   # f32 [max_new_tokens, B, V] (device): the logits every token was chosen from
     dropped: Tuple[int, ...] = ()                # rows NOT generated (``overlong="drop"``): pad-filled tokens, NaN logits
+    token_logprobs: Optional[torch.Tensor] = None   # f32 [B, width] on CPU, with a ``constraint`` only: log-probability of every
+    #                                                 token among the candidates it was chosen from (0 after a row's EOS)
 
 
 class CausalLMRuntimeMixin:
@@ -128,7 +130,7 @@ class CausalLMRuntimeMixin:
                  cache_len_multiple: int = 64, do_sample: bool = False, temperature: float = 1.0, top_p: float = 1.0,
                  top_k: int = 50, repetition_penalty: float = 1.0, generator: Optional[torch.Generator] = None,
                  sample_debug=None, want_step_logits: bool = False, overlong: str = "raise", num_beams: int = 1,
-                 length_penalty: float = 1.0, beam_debug: Optional[dict] = None) -> GenerateResult:
+                 length_penalty: float = 1.0, beam_debug: Optional[dict] = None, constraint=None) -> GenerateResult:
         """Greedy search with HF ``generate(inputs_embeds=…)`` semantics (models/custom_salmon.py:704-720): returns only
         the new tokens; a row that has emitted EOS is filled with pad; the width is that of the longest row
         (``min_length`` is a no-op with inputs_embeds).  All steps are enqueued without a host sync; the
@@ -145,10 +147,21 @@ class CausalLMRuntimeMixin:
         tokens are pad, its logits NaN) — the reference runs batch 1, where one over-long prompt costs one utterance
         (inference/inference.py:370-373), not the batch it happens to be collated with.
 
-        ``num_beams > 1``: HF beam search (``early_stopping=False``; ``length_penalty`` as in HF; see ``_generate_beam``)."""
+        ``num_beams > 1``: HF beam search (``early_stopping=False``; ``length_penalty`` as in HF; see ``_generate_beam``).
+
+        ``constraint`` = ``(constraints.LabelAutomaton, start_states)``, one start state per prompt (-1 = a free row): opt-in
+        label-constrained greedy decoding.  The tail of every step is ``icl_argmax_fsm``: a constrained row's token is the best
+        of the outgoing edges of its automaton state that can still reach an accepting state within the tokens left, so a row
+        that runs out of ``max_new_tokens`` stops on a complete answer; the result carries ``token_logprobs``.  Prefill, KV cache
+        and decode step are the unconstrained ones.  Greedy only: sampling, a repetition penalty, beams and ``suppress_eos``
+        together with a constraint, a ``max_new_tokens`` below a row's shortest answer, and a start-state list of the wrong
+        length are ``ValueError``s raised before anything is launched."""
         c, ws, dev = self.lm_cfg, self.ws, self.device
         if overlong not in ("raise", "drop"):
             raise ValueError(f"overlong must be 'raise' or 'drop', not {overlong!r}")
+        if constraint is not None:
+            constraint = self._check_constraint(constraint, len(prompts), max_new_tokens, eos_id, do_sample, repetition_penalty,
+                                                num_beams, suppress_eos)
         limit = c.max_pos // cache_len_multiple * cache_len_multiple      # cache lengths are multiples of cache_len_multiple
         plens = self._prompt_lengths(prompts)
         bad = [b for b, n in enumerate(plens) if n + max_new_tokens > limit]
@@ -162,7 +175,8 @@ class CausalLMRuntimeMixin:
                                 cache_len_multiple=cache_len_multiple, do_sample=do_sample, temperature=temperature, top_p=top_p,
                                 top_k=top_k, repetition_penalty=repetition_penalty, generator=generator,
                                 sample_debug=sample_debug, want_step_logits=want_step_logits, num_beams=num_beams,
-                                length_penalty=length_penalty)
+                                length_penalty=length_penalty,
+                                constraint=None if constraint is None else (constraint[0], [constraint[1][b] for b in keep]))
             n, kidx = len(plens), torch.tensor(keep)
             toks = torch.full((n, sub.tokens.shape[1]), c.pad_id if pad_id is None else pad_id, dtype=torch.int64)
             toks[kidx] = sub.tokens
@@ -173,7 +187,11 @@ class CausalLMRuntimeMixin:
             if sub.step_logits is not None:
                 steps = torch.full((sub.step_logits.shape[0], n, sub.step_logits.shape[2]), float("nan"), dtype=F32, device=dev)
                 steps[:, kidx.to(dev)] = sub.step_logits
-            return GenerateResult(tokens=toks, first_logits=first, step_logits=steps, dropped=tuple(bad))
+            lps = None
+            if sub.token_logprobs is not None:
+                lps = torch.full((n, sub.token_logprobs.shape[1]), float("nan"), dtype=F32)
+                lps[kidx] = sub.token_logprobs
+            return GenerateResult(tokens=toks, first_logits=first, step_logits=steps, dropped=tuple(bad), token_logprobs=lps)
         eos = c.eos_id if eos_id is None else eos_id            # an id, or HF's list form (one or two ids: binding._eos_pair)
         eos = tuple(int(e) for e in eos) if isinstance(eos, (tuple, list)) else int(eos)
         pad = c.pad_id if pad_id is None else pad_id
@@ -231,7 +249,20 @@ class CausalLMRuntimeMixin:
         toks = ws.get("gen_tokens", (Bn, max_new_tokens), I32)
         nxt = ws.get("gen_next", (Bn,), I32)
         sampled = do_sample or repetition_penalty != 1.0
-        if sampled:
+        lps = None
+        if constraint is not None:
+            # the automaton's tables are uploaded once and kept; the rows' states restart from their start states on every call
+            # (outside the captured decode loop, like ``finished``), and the upload's id keys the graph below
+            tables = constraint[0].upload(dev)
+            fsm_state = ws.get("gen_fsm_state", (Bn,), I32)
+            fsm_state.copy_(torch.tensor(constraint[1], dtype=I32), non_blocking=True)
+            lps = ws.get("gen_token_logprobs", (Bn, max_new_tokens), F32)
+            knobs = ("fsm", tables.uid)
+
+            def tail(lg, step):
+                B.argmax_fsm(lg, tables, fsm_state, max_new_tokens - step, eos, pad, finished, toks, step, nxt, out_logprob=lps,
+                             V=c.vocab)
+        elif sampled:
             # HF's TopKLogitsWarper clamps top_k to the vocabulary; 0 / None switch it off.  The kernel takes 1..SAMPLE_TOP_K_MAX, or
             # the vocabulary size for "off" (full-row normalisation, nucleus over the 1024 most likely tokens); anything else is
             # a caller's argument error and is refused HERE, before a launch — never as a device-side failure
@@ -306,14 +337,43 @@ class CausalLMRuntimeMixin:
                     self._graph_warm.add(gkey)
         if marks is not None:
             marks["decode_end"].record()
-        out = toks.cpu().to(torch.int64)                                                 # the only D2H of the call
+        out = toks.cpu().to(torch.int64)                                # the only D2H of the call (two with a constraint)
         width = max_new_tokens
         if B._eos_pair(eos)[0] >= 0:
             is_eos = torch.isin(out, torch.tensor([e for e in B._eos_pair(eos) if e >= 0]))
             first_eos = torch.where(is_eos.any(1), is_eos.float().argmax(1) + 1, torch.full((Bn,), max_new_tokens))
             width = int(first_eos.max())
         return GenerateResult(tokens=out[:, :width].contiguous(), first_logits=first,
-                              step_logits=trace.clone() if trace is not None else None)
+                              step_logits=trace.clone() if trace is not None else None,
+                              token_logprobs=lps.cpu()[:, :width].contiguous() if lps is not None else None)
+
+    def _check_constraint(self, constraint, n_rows: int, max_new_tokens: int, eos_id, do_sample: bool, repetition_penalty: float,
+                          num_beams: int, suppress_eos: bool):
+        """Host validation of ``generate(constraint=...)``: everything is a ``ValueError`` (a caller's mistake, never a device
+        failure) and is raised before any launch.  Returns ``(automaton, [start states as ints])``."""
+        try:
+            automaton, starts = constraint
+            starts = [int(x) for x in starts]
+        except (TypeError, ValueError):
+            raise ValueError("constraint must be (LabelAutomaton, one start state per prompt)") from None
+        c = self.lm_cfg
+        if do_sample or float(repetition_penalty) != 1.0 or num_beams != 1 or suppress_eos:
+            raise ValueError("constrained decoding is greedy: do_sample, repetition_penalty != 1, num_beams > 1 and suppress_eos "
+                             "cannot be combined with a constraint")
+        if len(starts) != n_rows:
+            raise ValueError(f"{len(starts)} start states for {n_rows} prompts")
+        if any(not -1 <= x < automaton.n_states for x in starts):
+            raise ValueError(f"start state outside [-1,{automaton.n_states})")
+        if automaton.vocab > c.vocab:
+            raise ValueError(f"automaton built for a vocabulary of {automaton.vocab} ids, the model has {c.vocab}")
+        eos = c.eos_id if eos_id is None else eos_id
+        if automaton.eos_id not in B._eos_pair(tuple(eos) if isinstance(eos, (tuple, list)) else eos):
+            raise ValueError(f"automaton built for EOS id {automaton.eos_id}, generate() stops on {eos}")
+        short = [b for b, x in enumerate(starts) if automaton.min_tokens(x) > max_new_tokens]
+        if short:
+            raise ValueError(f"max_new_tokens={max_new_tokens} is below the shortest answer of row(s) {short[:8]} "
+                             f"({[automaton.min_tokens(starts[b]) for b in short[:8]]} tokens): no complete label fits")
+        return automaton, starts
 
 
     beam_rows = 256            # decode rows (sequences x beams) per pass of beam search: the widest decode tile

@@ -273,6 +273,33 @@ int icl_argmax_eos(const float* logits, int64_t ldl, int32_t B, int32_t V, int32
                    int32_t pad_id, int32_t* finished, int32_t* out_tokens, int32_t out_stride,
                    int32_t step, int32_t* next_ids, void* stream);
 
+/* ---- K11 (constrained): greedy argmax along a token automaton + EOS/pad bookkeeping + log-probability ----
+ * The automaton is CSR: the edges of state s are state_off[s] .. state_off[s+1] - 1, sorted by edge_tok and unique, edge e
+ * leads to edge_next[e]; state_dist[s] = the fewest tokens from s to an accepting state (one with an edge on the EOS id).
+ * The tables are trusted: the caller validates them before the upload (offsets monotone, tokens in [0,V), next states in
+ * [0,n_states)).  Per row b (state[b] is read and written; steps_left = the tokens the row may still emit, this one included):
+ *   finished[b]                     tok = pad_id, out_logprob = 0, state[b] untouched;
+ *   state[b] == -1 (a free row; any id outside [0,n_states) is treated the same and is never used as an index):
+ *                                   tok = icl_argmax_eos's (lowest index on ties, a NaN logit cannot be chosen and carries no
+ *                                   mass); out_logprob = logits[b][tok] - log-sum-exp over the whole row;
+ *   otherwise                       candidates = the edges e of state[b] with state_dist[edge_next[e]] <= steps_left - 1; tok =
+ *                                   the edge_tok of the candidate with the largest logit (NaN counts as -inf; the lowest token
+ *                                   id on ties, hence the first candidate when all are -inf); state[b] = its edge_next;
+ *                                   out_logprob = its logit - log-sum-exp over the candidates.
+ * Log-sum-exp is f32 with the maximum subtracted first; out_logprob is NaN where that is undefined (no finite candidate, or a
+ * +inf one).  A constrained row without any candidate (the caller broke steps_left >= state_dist[state[b]]) ends: tok = pad_id,
+ * finished[b] = 1, out_logprob = NaN.  Then icl_argmax_eos's bookkeeping word for word: finished[b] |= tok is an EOS id;
+ * out_tokens[b*out_stride + step] = next_ids[b] = tok.  out_logprob is NULL or f32 [B][out_stride], written at the same index.
+ * One workgroup per row, one pass over the row (free) or over one state's edges (constrained); nothing allocates or
+ * synchronises, so the launch can be captured in a graph.  No counterpart in the reference, which repairs free-running
+ * output on the host afterwards (utils/evaluation_utils.py clean_prediction).
+ */
+int icl_argmax_fsm(const float* logits, int64_t ldl, int32_t B, int32_t V, const int32_t* state_off, const int32_t* edge_tok,
+                   const int32_t* edge_next, const int32_t* state_dist, int32_t n_states, int32_t n_edges, int32_t* state,
+                   int32_t steps_left, int32_t eos_id, int32_t eos_id2, int32_t pad_id, int32_t* finished,
+                   int32_t* out_tokens, int32_t out_stride, int32_t step, int32_t* next_ids, float* out_logprob,
+                   void* stream);
+
 /* ---- K11 (sampled): repetition penalty -> temperature -> top-k -> top-p -> inverse-CDF draw + EOS/pad bookkeeping ----
  * Per sequence b: scores = logits[b] with every token in prev_tokens[b][0..n_prev) rescaled (x<0 ? x*penalty : x/penalty),
  * all divided by temperature; candidates = scores >= the top_k-th largest score (ties kept); probabilities = softmax over
