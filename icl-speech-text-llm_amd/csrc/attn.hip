@@ -69,8 +69,13 @@ __device__ __forceinline__ float max_xhalf(float v) {
   return __builtin_fmaxf(__builtin_bit_cast(float, lo), __builtin_bit_cast(float, hi));
 }
 
-template <int D, bool CAUSAL, bool BIAS>
-__global__ __launch_bounds__(256, (D == 64 && BIAS) ? 3 : 2) void attn_fwd_kernel(AttnParams p) {
+// SUFFIX (icl_attn_fwd_suffix_bf16): sequence `seq` brings only its LAST q_len = cu_q[seq+1] - cu_q[seq] queries, packed at
+// row cu_q[seq] of Q / O; query i sits at position len - q_len + i of its `len` keys.  The grid, the q-blocks and the waves
+// are laid over POSITIONS exactly as in the full launch, so a query keeps its wave, its lane, its K/V tiles (the 64-key grid from
+// key 0, ascending) and the interior / masked form of every tile: its output is the full launch's, bit for bit.  Blocks and waves
+// whose positions hold no query drop out (a wave still stages its share of each tile and keeps the barriers).
+template <int D, bool CAUSAL, bool BIAS, bool SUFFIX = false>
+__global__ __launch_bounds__(256, (D == 64 && BIAS) ? 3 : 2) void attn_fwd_kernel(AttnParams p, const int* cu_q) {
   // 32-query blocks per wave.  D = 64 without bias runs attn_fwd_il64_kernel below (two blocks per wave sharing every K / V
   // fragment, stages interleaved by hand); this kernel serves D = 128 and the gated-bias variant, one block per wave
   // (measured for the bias variant: its longer per-score sequence wants the third wave per SIMD more than the sharing,
@@ -116,10 +121,18 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS) ? 3 : 2) void attn_fwd_kerne
   const int len = p.cu[seq + 1] - row0;
   const int qb = qblk * BQ;
   if (qb >= len) return;
+  int qrow0 = row0, qstart = 0;   // SUFFIX: first packed Q / O row of the sequence, position of its first query
+  if constexpr (SUFFIX) {
+    qrow0 = cu_q[seq];
+    const int qlen = cu_q[seq + 1] - qrow0;
+    qstart = max(len - qlen, 0);
+    if (qlen <= 0 || qb + BQ <= qstart) return;
+  }
   int kvlen = len;
   if (p.kv_lens) kvlen = min(max(p.kv_lens[seq], 1), len);
   const int kv_end = CAUSAL ? min(kvlen, qb + BQ) : kvlen;
   const int n_tiles = (kv_end + 63) >> 6;
+  const bool wave_has_q = !SUFFIX || qb + wave * (32 * QB) + 32 * QB > qstart;   // wave-uniform
 
   int qw[QB], qpos[QB];           // first query of each of this wave's q-blocks / this lane's query in it
   bf16x8 qf[QB][KS];              // Q fragments (B operand of S^T = K Q^T): lane (q, hh) holds Q[q][16ks + 8hh .. +7]
@@ -130,7 +143,7 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS) ? 3 : 2) void attn_fwd_kerne
     qw[qi] = qb + (wave * QB + qi) * 32;
     qpos[qi] = qw[qi] + ql;
     const int qrow = min(qpos[qi], len - 1);
-    const unsigned short* qp = p.Q + (int64_t)(row0 + qrow) * p.ldq + head * D + hh * 8;
+    const unsigned short* qp = p.Q + (int64_t)(SUFFIX ? qrow0 + max(qrow - qstart, 0) : row0 + qrow) * p.ldq + head * D + hh * 8;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) qf[qi][ks] = *(const bf16x8*)(qp + ks * 16);
     gate[qi] = 0.f;
@@ -245,6 +258,7 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS) ? 3 : 2) void attn_fwd_kerne
 #pragma unroll
     for (int qi = 0; qi < QB; ++qi) {
       active[qi] = !MAYMASK || !CAUSAL || (k0 <= qw[qi] + 31);
+      if constexpr (SUFFIX) active[qi] = active[qi] && wave_has_q;
       any_active |= active[qi];
     }
     if (any_active) {
@@ -488,14 +502,14 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS) ? 3 : 2) void attn_fwd_kerne
       const int row = it * RPI + lane / LPR, cc = lane % LPR;
       const int q = qw[row >> 5] + (row & 31);
       const u32x4 v = *(const u32x4*)(stg + row * PITCH + cc * 16);
-      if (q < len) *(u32x4*)(p.O + (int64_t)(row0 + q) * p.ldo + head * D + cc * 8) = v;
+      if (q < len && (!SUFFIX || q >= qstart)) *(u32x4*)(p.O + (int64_t)(SUFFIX ? qrow0 + q - qstart : row0 + q) * p.ldo + head * D + cc * 8) = v;
     }
     return;
   }
 #pragma unroll
   for (int qi = 0; qi < QB; ++qi) {
-    if (qpos[qi] < len) {
-      unsigned short* op = p.O + (int64_t)(row0 + qpos[qi]) * p.ldo + head * D;
+    if (qpos[qi] < len && (!SUFFIX || qpos[qi] >= qstart)) {
+      unsigned short* op = p.O + (int64_t)(SUFFIX ? qrow0 + qpos[qi] - qstart : row0 + qpos[qi]) * p.ldo + head * D;
 #pragma unroll
       for (int d = 0; d < DB; ++d) {
 #pragma unroll
@@ -509,7 +523,6 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS) ? 3 : 2) void attn_fwd_kerne
     }
   }
 }
-
 
 // =====================================================================================================================
 // D = 64 without bias (Whisper / Qwen2-Audio encoder, Q-Former): the kernel above with its stages INTERLEAVED by hand.
@@ -839,7 +852,7 @@ __global__ __launch_bounds__(64 * NW, CAUSAL ? 1 : 2) void attn_fwd_il64_kernel(
 }
 
 template <int D>
-int launch_attn(const AttnParams& p, const icl_attn_args* a, hipStream_t stream) {
+int launch_attn(const AttnParams& p, const icl_attn_args* a, const int* cu_q, hipStream_t stream) {
   const int bq = (D == 64 && !a->rel_bias) ? IL64_NW * 64 : 128;   // queries per workgroup
   dim3 grid(((a->max_seqlen + bq - 1) / bq) * a->n_heads * a->n_seqs, 1, 1);
   const bool bias = a->rel_bias != nullptr;
@@ -849,16 +862,21 @@ int launch_attn(const AttnParams& p, const icl_attn_args* a, hipStream_t stream)
     ICL_CHECK_LAUNCH("icl_attn_fwd_bf16");
     return ICL_OK;
   }
+  if (cu_q) {       // D = 128, causal, no bias: checked by the caller
+    if constexpr (D == 128) hipLaunchKernelGGL((attn_fwd_kernel<128, true, false, true>), grid, dim3(256), 0, stream, p, cu_q);
+    ICL_CHECK_LAUNCH("icl_attn_fwd_suffix_bf16");
+    return ICL_OK;
+  }
   if (a->causal) {
     if (bias)
-      hipLaunchKernelGGL((attn_fwd_kernel<D, true, true>), grid, dim3(256), 0, stream, p);
+      hipLaunchKernelGGL((attn_fwd_kernel<D, true, true>), grid, dim3(256), 0, stream, p, nullptr);
     else
-      hipLaunchKernelGGL((attn_fwd_kernel<D, true, false>), grid, dim3(256), 0, stream, p);
+      hipLaunchKernelGGL((attn_fwd_kernel<D, true, false>), grid, dim3(256), 0, stream, p, nullptr);
   } else {
     if (bias)
-      hipLaunchKernelGGL((attn_fwd_kernel<D, false, true>), grid, dim3(256), 0, stream, p);
+      hipLaunchKernelGGL((attn_fwd_kernel<D, false, true>), grid, dim3(256), 0, stream, p, nullptr);
     else
-      hipLaunchKernelGGL((attn_fwd_kernel<D, false, false>), grid, dim3(256), 0, stream, p);
+      hipLaunchKernelGGL((attn_fwd_kernel<D, false, false>), grid, dim3(256), 0, stream, p, nullptr);
   }
   ICL_CHECK_LAUNCH("icl_attn_fwd_bf16");
   return ICL_OK;
@@ -866,7 +884,7 @@ int launch_attn(const AttnParams& p, const icl_attn_args* a, hipStream_t stream)
 
 }  // namespace
 
-extern "C" int icl_attn_fwd_bf16(const icl_attn_args* a, void* stream) {
+static int attn_fwd_impl(const icl_attn_args* a, const int32_t* cu_q, void* stream) {
   ICL_CHECK_ARG(a != nullptr, "icl_attn_fwd_bf16: args is NULL");
   ICL_CHECK_ARG(a->Q && a->K && a->V && a->O && a->cu_seqlens, "icl_attn_fwd_bf16: NULL pointer");
   ICL_CHECK_ARG(a->head_dim == 64 || a->head_dim == 128, "icl_attn_fwd_bf16: head_dim=%d (only 64 and 128)", a->head_dim);
@@ -898,5 +916,14 @@ extern "C" int icl_attn_fwd_bf16(const icl_attn_args* a, void* stream) {
   const int bq = (a->head_dim == 64 && !a->rel_bias) ? IL64_NW * 64 : 128;
   p.n_qblocks = (a->max_seqlen + bq - 1) / bq;
   p.scale_log2e = a->scale * LOG2E;
-  return a->head_dim == 64 ? launch_attn<64>(p, a, (hipStream_t)stream) : launch_attn<128>(p, a, (hipStream_t)stream);
+  return a->head_dim == 64 ? launch_attn<64>(p, a, cu_q, (hipStream_t)stream) : launch_attn<128>(p, a, cu_q, (hipStream_t)stream);
+}
+
+extern "C" int icl_attn_fwd_bf16(const icl_attn_args* a, void* stream) { return attn_fwd_impl(a, nullptr, stream); }
+
+extern "C" int icl_attn_fwd_suffix_bf16(const icl_attn_args* a, const int32_t* cu_q, void* stream) {
+  ICL_CHECK_ARG(a != nullptr && cu_q != nullptr, "icl_attn_fwd_suffix_bf16: NULL pointer");
+  ICL_CHECK_ARG(a->head_dim == 128 && a->causal && !a->rel_bias && !a->rel_gate && !a->kv_lens,
+                "icl_attn_fwd_suffix_bf16: the suffix-query form is built for head_dim 128, causal, without bias or kv_lens");
+  return attn_fwd_impl(a, cu_q, stream);
 }

@@ -79,12 +79,13 @@ __global__ __launch_bounds__(256) void beats_posconv_pack_kernel(float* x, const
       u32x4{pack_bf16x2(v0[0], v0[1]), pack_bf16x2(v0[2], v0[3]), pack_bf16x2(v1[0], v1[1]), pack_bf16x2(v1[2], v1[3])};
 }
 
-__global__ __launch_bounds__(256) void gather_rows_kernel(const float* src, int64_t lds_, const int* idx, float* out,
+// one block per row, 16-byte pieces: a piece is four f32 or eight bf16 (N counts pieces, lds_ / ldo are in pieces)
+__global__ __launch_bounds__(256) void gather_rows_kernel(const u32x4* src, int64_t lds_, const int* idx, u32x4* out,
                                                            int64_t ldo, int N) {
   const int64_t r = blockIdx.x;
-  const float* s = src + (int64_t)idx[r] * lds_;
-  float* d = out + r * ldo;
-  for (int c = threadIdx.x * 4; c < N; c += blockDim.x * 4) *(f32x4*)(d + c) = *(const f32x4*)(s + c);
+  const u32x4* s = src + (int64_t)idx[r] * lds_;
+  u32x4* d = out + r * ldo;
+  for (int c = threadIdx.x; c < N; c += blockDim.x) d[c] = s[c];
 }
 
 }  // namespace
@@ -118,7 +119,19 @@ extern "C" int icl_gather_rows_f32(const float* src, int64_t ld_src, const int32
   ICL_CHECK_ARG(src && idx && out && rows > 0 && N > 0 && N % 4 == 0 && ld_src % 4 == 0 && ld_out % 4 == 0,
                 "icl_gather_rows_f32: bad arguments");
   ICL_CHECK_ARG(((uintptr_t)src & 15) == 0 && ((uintptr_t)out & 15) == 0, "icl_gather_rows_f32: misaligned");
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, src, ld_src, idx, out, ld_out, N);
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const u32x4*)src, ld_src / 4, idx,
+                     (u32x4*)out, ld_out / 4, N / 4);
   ICL_CHECK_LAUNCH("icl_gather_rows_f32");
+  return ICL_OK;
+}
+
+extern "C" int icl_gather_rows_bf16(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out,
+                                    int32_t rows, int32_t N, void* stream) {
+  ICL_CHECK_ARG(src && idx && out && rows > 0 && N > 0 && N % 8 == 0 && ld_src % 8 == 0 && ld_out % 8 == 0,
+                "icl_gather_rows_bf16: bad arguments (N and the leading dimensions must be multiples of 8)");
+  ICL_CHECK_ARG(((uintptr_t)src & 15) == 0 && ((uintptr_t)out & 15) == 0, "icl_gather_rows_bf16: misaligned");
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const u32x4*)src, ld_src / 8, idx,
+                     (u32x4*)out, ld_out / 8, N / 8);
+  ICL_CHECK_LAUNCH("icl_gather_rows_bf16");
   return ICL_OK;
 }

@@ -1124,8 +1124,12 @@ extern "C" int icl_gemm_rope_kv_bf16(const icl_gemm_args* a, int64_t k_off, int6
                                      void* stream) {
   ICL_CHECK_ARG(a != nullptr && cosT && sinT && pos, "icl_gemm_rope_kv_bf16: NULL pointer");
   ICL_CHECK_ARG(head_dim == 128, "icl_gemm_rope_kv_bf16: head_dim=%d (the fused epilogue is built for 128)", head_dim);
-  ICL_CHECK_ARG(n_heads > 0 && k_off == (int64_t)n_heads * 128 && v_off == 2 * k_off && a->N == 3 * k_off && k_off % 256 == 0,
-                "icl_gemm_rope_kv_bf16: need q|k|v blocks of n_heads*128 columns each, a multiple of 256 (N=%d k_off=%lld v_off=%lld)",
+  // column sections q = [0, k_off), k = [k_off, v_off), v = [v_off, N): each n_heads*128 wide or EMPTY (a launch over the k | v
+  // rows of the weight alone has k_off = 0; one over its q rows alone has k_off = v_off = N) — a tile lies inside one section
+  const int64_t hd = (int64_t)n_heads * 128;
+  ICL_CHECK_ARG(n_heads > 0 && hd % 256 == 0 && (k_off == 0 || k_off == hd) && (v_off == k_off || v_off == k_off + hd) &&
+                    (a->N == v_off || a->N == v_off + hd) && a->N > 0,
+                "icl_gemm_rope_kv_bf16: need q|k|v blocks of n_heads*128 columns each (or empty), a multiple of 256 (N=%d k_off=%lld v_off=%lld)",
                 a->N, (long long)k_off, (long long)v_off);
   ICL_CHECK_ARG(a->batch == 1 && a->out_dtype == ICL_BF16 && (a->epilogue & ~ICL_EPI_BIAS) == 0,
                 "icl_gemm_rope_kv_bf16: batch 1, bf16 output, bias-only epilogue");

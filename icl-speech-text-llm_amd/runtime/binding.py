@@ -62,6 +62,7 @@ _SIGNATURES = {
     "icl_gemm_rmsnorm_bf16": (c_int, [POINTER(GemmArgs), c_void_p, c_float, c_void_p, c_int64, c_void_p]),
     "icl_gemm_select_tile": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "icl_attn_fwd_bf16": (c_int, [POINTER(AttnArgs), c_void_p]),
+    "icl_attn_fwd_suffix_bf16": (c_int, [POINTER(AttnArgs), c_void_p, c_void_p]),
     "icl_attn_decode_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                      c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
     "icl_attn_decode_rope_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -124,6 +125,7 @@ _SIGNATURES = {
     "icl_beats_posconv_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                        c_void_p]),
     "icl_gather_rows_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
+    "icl_gather_rows_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
     "icl_cross_entropy": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
 }
 
@@ -330,17 +332,25 @@ def pack_fp8_weights(w: torch.Tensor, K=None, out=None):
     return q, scales, out
 
 
+def rope_epilogue_ok(n_heads: int, head_dim: int, K: int) -> bool:
+    """True when the 256x256 tile's fused RoPE epilogue can serve this QKV projection at all (its shape conditions; ``gemm(...,
+    tile=3, rope=...)`` then runs at any M — tiles 1 - 3 sum K in the same order, so pinning the tile changes no bits)."""
+    return head_dim == 128 and (n_heads * head_dim) % 256 == 0 and K >= 128
+
+
 def rope_fusable(M: int, n_heads: int, head_dim: int, K: int) -> bool:
     """True when the QKV projection [M, 3*n_heads*head_dim] x K runs on the 256x256 tile with the fused RoPE epilogue."""
     hd = n_heads * head_dim
-    return (head_dim == 128 and hd % 256 == 0 and K >= 128 and
+    return (rope_epilogue_ok(n_heads, head_dim, K) and
             load_library().icl_gemm_select_tile(M, 3 * hd, K, 1, 1) == 3)
 
 
 def attn_fwd(q, k, v, out, cu_seqlens, max_seqlen: int, n_heads: int, head_dim: int, scale: float, *,
-             causal=False, kv_lens=None, rel_bias=None, rel_gate=None, rel_span: int = 0, kv_cache_max_len: int = 0):
-    """``kv_cache_max_len`` > 0: k / v are KV-cache tensors [n_seqs, n_heads, max_len, head_dim] (read in place)."""
-    _require_gpu(q, k, v, out, cu_seqlens, kv_lens, rel_bias, rel_gate)
+             causal=False, kv_lens=None, rel_bias=None, rel_gate=None, rel_span: int = 0, kv_cache_max_len: int = 0, cu_q=None):
+    """``kv_cache_max_len`` > 0: k / v are KV-cache tensors [n_seqs, n_heads, max_len, head_dim] (read in place).
+    ``cu_q`` (int32 [n_seqs + 1]): the suffix-query form (icl_attn_fwd_suffix_bf16) — ``q`` / ``out`` hold only the last
+    cu_q[s+1] - cu_q[s] queries of each sequence, packed by ``cu_q``; ``cu_seqlens`` / ``max_seqlen`` describe k / v."""
+    _require_gpu(q, k, v, out, cu_seqlens, kv_lens, rel_bias, rel_gate, cu_q)
     lib = load_library()
     a = AttnArgs()
     a.Q, a.K, a.V, a.O = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
@@ -357,6 +367,10 @@ def attn_fwd(q, k, v, out, cu_seqlens, max_seqlen: int, n_heads: int, head_dim: 
     a.max_seqlen, a.n_heads, a.head_dim = max_seqlen, n_heads, head_dim
     a.causal, a.rel_span, a.scale = int(causal), rel_span, scale
     assert cu_seqlens.dtype == torch.int32
+    if cu_q is not None:
+        assert cu_q.dtype == torch.int32 and cu_q.numel() == cu_seqlens.numel()
+        _check(lib.icl_attn_fwd_suffix_bf16(ctypes.byref(a), cu_q.data_ptr(), _stream()), "icl_attn_fwd_suffix_bf16")
+        return out
     _check(lib.icl_attn_fwd_bf16(ctypes.byref(a), _stream()), "icl_attn_fwd_bf16")
     return out
 
@@ -678,11 +692,14 @@ def beats_posconv_pack(x, cu_rows, valid_rows, n_audio: int, total_rows: int, gr
 
 
 def gather_rows(src, idx, out, N=None):
+    """out[r, :N] = src[idx[r], :N]; f32 or bf16 (both tensors alike)."""
     _require_gpu(src, idx, out)
-    assert src.dtype == torch.float32 and out.dtype == torch.float32 and idx.dtype == torch.int32
-    _check(load_library().icl_gather_rows_f32(src.data_ptr(), src.stride(0), idx.data_ptr(), out.data_ptr(),
-                                              out.stride(0), idx.numel(), src.shape[1] if N is None else N,
-                                              _stream()), "icl_gather_rows_f32")
+    assert src.dtype == out.dtype and src.dtype in (torch.float32, torch.bfloat16) and idx.dtype == torch.int32
+    lib = load_library()
+    fn, what = ((lib.icl_gather_rows_f32, "icl_gather_rows_f32") if src.dtype == torch.float32 else
+                (lib.icl_gather_rows_bf16, "icl_gather_rows_bf16"))
+    _check(fn(src.data_ptr(), src.stride(0), idx.data_ptr(), out.data_ptr(), out.stride(0), idx.numel(),
+              src.shape[1] if N is None else N, _stream()), what)
     return out
 
 

@@ -485,6 +485,18 @@ class LlamaHIP:
     # on the 256 tile as well (split 12) — all four.  ICL_DECODE_T256 = comma list of qkv / o / gu / down overrides ("" = decode tile only).
     decode_t256 = tuple(x for x in os.environ.get("ICL_DECODE_T256", "qkv,o,gu,down").split(",") if x)
 
+    # Generation reads the last position of every prompt only, so the LAST decoder layer of a prefill runs its q projection,
+    # attention, o_proj, norm and MLP on those rows alone (``prefill(last_rows_only=True)``; bit-identical).
+    # ICL_PREFILL_LAST_ROWS=0 restores the full-height last layer + a gather, for A/B.
+    prefill_last_rows = os.environ.get("ICL_PREFILL_LAST_ROWS", "1") != "0"
+    # f32 [n_seqs, hidden] or None: set by ``want_last_rows``, consumed by the next ``prefill`` call
+    _last_rows_out: Optional[torch.Tensor] = None
+
+    def want_last_rows(self, out: torch.Tensor) -> None:
+        """The NEXT ``prefill`` call runs as ``prefill(..., last_rows_only=True, last_out=out)``.  The request travels on the
+        object, not in the call, so that ``prefill`` keeps its (ws, h, seq_lens, cache) call form for code that wraps it."""
+        self._last_rows_out = out
+
     def _t256_split(self, N: int, K: int) -> int:
         return t256_split(N, K, self.n_cu)
 
@@ -615,8 +627,17 @@ class LlamaHIP:
         return False
 
     # ---- K10: prefill over ragged packed sequences ------------------------------------------------
-    def prefill(self, ws: Workspace, h: torch.Tensor, seq_lens: List[int], cache: Optional["KVCache"] = None) -> torch.Tensor:
-        """h f32 [sum S_b, hidden] (modified in place) -> same buffer holding the final hidden states."""
+    def prefill(self, ws: Workspace, h: torch.Tensor, seq_lens: List[int], cache: Optional["KVCache"] = None,
+                last_rows_only: bool = False, last_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """h f32 [sum S_b, hidden] (modified in place) -> same buffer holding the final hidden states.
+
+        ``last_rows_only`` (needs a cache): return only the final hidden state of the LAST row of every sequence, f32
+        [len(seq_lens), hidden] (written into ``last_out`` when given) — what generation feeds to the final norm and the LM
+        head.  Every layer's K / V still reach the cache for all rows; ``h`` is then NOT the final hidden states (the last
+        layer leaves its other rows untouched, ``_last_layer_rows``).  The rows returned are bit-identical to the same rows of
+        the full prefill."""
+        if self._last_rows_out is not None:        # a request left by want_last_rows: this call serves it
+            last_rows_only, last_out, self._last_rows_out = True, self._last_rows_out, None
         c = self.w.cfg
         dev = h.device
         M = sum(seq_lens)
@@ -624,6 +645,7 @@ class LlamaHIP:
         for s in seq_lens:
             cu_h.append(cu_h[-1] + s)
         assert max(seq_lens) <= c.max_pos
+        assert cache is not None or not last_rows_only, "prefill(last_rows_only=True) needs a KV cache"
         pos = _i32([p for s in seq_lens for p in range(s)], dev)
         sid = _i32([b for b, s in enumerate(seq_lens) for _ in range(s)], dev)
         cu = _i32(cu_h, dev)
@@ -637,13 +659,25 @@ class LlamaHIP:
         # buffer) and one icl_kv_append_fp8 pass rounds them into the cache before the attention.
         fp8 = cache is not None and cache.dtype == "fp8"
         kv_from_cache = cache is not None and not fp8 and B.rope_fusable(M, H, D, self.w.k_aug)
+        # the trimmed last layer is built on the 256-tile's fused RoPE epilogue (head_dim 128) and a bf16 cache; other models
+        # and the FP8 KV mode (whose prefill attends to unrounded packed k / v) keep the full-height layer and gather after it
+        trim = last_rows_only and self.prefill_last_rows and not fp8 and B.rope_epilogue_ok(H, D, self.w.k_aug)
 
         def attn(qkv, att):
             B.attn_fwd(qkv[:, :hd], qkv[:, hd:2 * hd], qkv[:, 2 * hd:], att, cu, maxS, H, D, D ** -0.5, causal=True)
 
+        last_idx = _i32([e - 1 for e in cu_h[1:]], dev) if last_rows_only else None
+
+        def last_rows(src):
+            out = last_out if last_out is not None else ws.get("pfl_h", (len(seq_lens), hd), F32)
+            return B.gather_rows(src, last_idx, out)
+
+        n_layers = len(self.w.layers)
         for i, L in enumerate(self.w.layers):
             kc = cache.k[i] if cache is not None else None
             vc = cache.v[i] if cache is not None else None
+            if trim and i == n_layers - 1:
+                return self._last_layer_rows(ws, L, h, M, seq_lens, pos, sid, cu, kc, vc, cache.max_len, last_idx, last_rows)
             fn = attn
             if fp8:
                 def fn(qkv, att, i=i):
@@ -657,7 +691,47 @@ class LlamaHIP:
                     B.attn_fwd(qkv[:, :hd], kc, vc, att, cu, maxS, H, D, D ** -0.5, causal=True, kv_cache_max_len=cache.max_len)
             self._layer(ws, L, h, M, "pf_", fn, pos, sid, kc, vc, cache.max_len if cache is not None else 0,
                         kv_rows_to_c=not kv_from_cache)
-        return h
+        return last_rows(h) if last_rows_only else h
+
+    def _last_layer_rows(self, ws: Workspace, L, h, M: int, seq_lens: List[int], pos, sid, cu, kc, vc, max_len: int,
+                         last_idx, last_rows) -> torch.Tensor:
+        """The last decoder layer of a prefill whose caller reads the last row of every sequence only: the layer's k / v are
+        projected (and appended to the cache) for all M rows; q, the attention, o_proj, the post-attention norm and the MLP run
+        on the len(seq_lens) gathered rows.  Exact, not approximate: every kernel here computes a row independently of its
+        neighbours, and each gathered row goes through the arithmetic the full-height layer gives it — the 256x256 tile's K
+        order (tiles 1 - 3 agree, so the small launches are pinned to tile 3 instead of the library's small-M choice), the same
+        fused RoPE epilogue at the row's position, and the full attention launch's wave, lane and 64-key tile sequence
+        (icl_attn_fwd_suffix_bf16, q_len = 1).  The gathered buffers have names of their own (pfl_*): the full-height ones
+        keep their size.  Returns the rows' final hidden states, f32 [len(seq_lens), hidden]."""
+        c, w = self.w.cfg, self.w
+        hd, I, D, H = c.hidden, c.ffn, c.head_dim, c.n_heads
+        Bn, dev = len(seq_lens), h.device
+        xn = ws.get("pf_xn", (M, w.k_aug), BF16, zero=True)
+        B.rmsnorm(h, L.rms1, xn, c.rms_eps, N=hd)
+        if L.lora_a is not None:
+            r2 = L.lora_a.shape[0]
+            B.gemm(xn, L.lora_a, xn[:, hd:hd + r2], K=hd, tile=2)
+        rope = (w.rope_cos, w.rope_sin)
+        # k | v rows of wqkv, all M rows, into the cache only: C is never written (kv_rows_to_c = 0)
+        qkv = ws.get("pf_qkv", (M, 3 * hd), BF16)
+        B.gemm(xn, L.wqkv[hd:], qkv, bias=L.bqkv[hd:] if L.bqkv is not None else None, tile=3,
+               rope=(0, hd, *rope, pos, sid, kc, vc, H, D, max_len, False))
+        hg = last_rows(h)
+        xg = ws.get("pfl_xn", (Bn, w.k_aug), BF16)              # whole augmented rows: the LoRA columns and the zero tail come along
+        B.gather_rows(xn, last_idx, xg)
+        # q rows of wqkv on the gathered rows, rotated at each row's own (last) position
+        q = ws.get("pfl_q", (Bn, hd), BF16)
+        B.gemm(xg, L.wqkv[:hd], q, bias=L.bqkv[:hd] if L.bqkv is not None else None, tile=3,
+               rope=(hd, hd, *rope, _i32([s - 1 for s in seq_lens], dev), None, None, None, H, D, max_len))
+        att = ws.get("pfl_att", (Bn, hd), BF16)
+        B.attn_fwd(q, kc, vc, att, cu, max(seq_lens), H, D, D ** -0.5, causal=True, kv_cache_max_len=max_len,
+                   cu_q=_i32(list(range(Bn + 1)), dev))
+        B.gemm(att, L.wo, hg, residual=hg, tile=3, N=hd, K=hd)
+        B.rmsnorm(hg, L.rms2, xg, c.rms_eps, N=hd)
+        act = ws.get("pfl_act", (Bn, I), BF16)
+        B.gemm(xg, L.wgu, act, swiglu=True, tile=3, N=2 * I, K=hd)
+        B.gemm(act, L.wdown, hg, residual=hg, tile=3, N=hd, K=I)
+        return hg
 
     def logits(self, ws: Workspace, h_rows: torch.Tensor, name: str = "ll_logits", xn_ready: bool = False) -> torch.Tensor:
         """h_rows f32 [R, hidden] -> logits f32 [R, vocab] (final RMSNorm + lm_head).  ``xn_ready``: the final norm has been

@@ -221,22 +221,20 @@ class CausalLMRuntimeMixin:
         # weights once per step whatever the row count (256 rows cost 0.84 us each against 1.06 at 128), while the prefill
         # GEMMs measured 1.3 % faster per utterance at 128 sequences than at 256.  A sequence's arithmetic does not depend on
         # its neighbours in either phase, so the split changes no result.
+        # Only the last position of every prompt is read from here on (final norm, LM head; decode reads the K/V cache): the
+        # prefill writes those rows into ``gen_last`` and trims its last layer to them (LlamaHIP.want_last_rows / prefill).
+        last = ws.get("gen_last", (Bn, c.hidden), F32)
         if Bn <= self.prefill_chunk:
+            self.llama.want_last_rows(last)
             self.llama.prefill(ws, h, lens, cache)
         else:
             r0 = 0
             for b0 in range(0, Bn, self.prefill_chunk):
                 b1 = min(Bn, b0 + self.prefill_chunk)
                 r1 = r0 + sum(lens[b0:b1])
+                self.llama.want_last_rows(last[b0:b1])
                 self.llama.prefill(ws, h[r0:r1], lens[b0:b1], cache.rows(b0, b1))
                 r0 = r1
-        cu_last = []
-        acc = 0
-        for s in lens:
-            acc += s
-            cu_last.append(acc - 1)
-        last = ws.get("gen_last", (Bn, c.hidden), F32)
-        B.gather_rows(h, _i32(cu_last, dev), last)
         logits = self.llama.logits(ws, last, name="gen_logits")
         first = logits.clone() if want_first_logits else None
         trace = ws.get("gen_logits_trace", (max_new_tokens, Bn, c.vocab), F32) if want_step_logits else None
@@ -414,18 +412,14 @@ class CausalLMRuntimeMixin:
         assert max_len <= c.max_pos, f"prompt + new tokens ({need}) exceeds max_pos {c.max_pos}"   # validated by generate()
         whole = self._cache(BK + Bn, max_len)                  # beams' sequences first, then the rows the prompts prefill into
         cache, pre = whole.rows(0, BK), whole.rows(BK, BK + Bn)
+        last = ws.get("gen_last", (Bn, c.hidden), F32)
         r0 = 0
         for b0 in range(0, Bn, self.prefill_chunk):
             b1 = min(Bn, b0 + self.prefill_chunk)
             r1 = r0 + sum(lens[b0:b1])
+            self.llama.want_last_rows(last[b0:b1])
             self.llama.prefill(ws, h[r0:r1], lens[b0:b1], pre.rows(b0, b1))
             r0 = r1
-        cu_last, acc = [], 0
-        for s in lens:
-            acc += s
-            cu_last.append(acc - 1)
-        last = ws.get("gen_last", (Bn, c.hidden), F32)
-        B.gather_rows(h, _i32(cu_last, dev), last)
         logits = self.llama.logits(ws, last, name="gen_logits")
         first = logits.clone() if want_first_logits else None
         st = B.BeamState(ws.get, Bn, K, T, pad)

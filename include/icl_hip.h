@@ -177,6 +177,15 @@ typedef struct icl_attn_args {
 
 int icl_attn_fwd_bf16(const icl_attn_args* args, void* stream);
 
+/* The suffix-query form of icl_attn_fwd_bf16 (head_dim 128, causal, no bias, no kv_lens): sequence s attends with only its LAST
+ * q_len(s) = cu_q[s+1] - cu_q[s] queries, 0 <= q_len(s) <= kv_len(s) = cu_seqlens[s+1] - cu_seqlens[s].  Q and O are packed by
+ * cu_q (int32 [n_seqs+1], device): query i of sequence s is row cu_q[s] + i and sits at position kv_len(s) - q_len(s) + i.
+ * K / V are addressed by cu_seqlens as in icl_attn_fwd_bf16 (packed rows, or the cache layout); max_seqlen bounds kv_len.
+ * Every query runs in the wave, lane and K/V tile sequence it has in the full launch: O rows are bit-identical to the rows
+ * icl_attn_fwd_bf16 writes at the same positions.  The last decoder layer of a prefill uses it with q_len = 1.
+ */
+int icl_attn_fwd_suffix_bf16(const icl_attn_args* args, const int32_t* cu_q, void* stream);
+
 /* ---- K11: single-token decode attention over the KV cache --------------------------------
  * One new query per sequence against cache rows [0, lens[b]) (the new token's K/V must
  * already be in the cache).  Cache layout: [n_seqs][n_heads][max_len][head_dim] bf16.
@@ -242,8 +251,10 @@ int icl_rope_kv_bf16(void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const 
  * are not read back from HBM.  Bit-identical to the two-call sequence (same rounding points).
  * args: batch 1, bf16 output, epilogue 0 or ICL_EPI_BIAS, N = 3*n_heads*128 with q|k|v column
  * blocks at 0 | k_off | v_off, n_heads*128 a multiple of 256; the problem must resolve to the
- * 256x256 tile (icl_gemm_select_tile(...) == 3 and K >= 128) — otherwise ICL_EINVAL, and the
- * caller issues the two calls.  Remaining arguments as icl_rope_kv_bf16.  kv_rows_to_c = 0 (needs a cache): the k / v
+ * 256x256 tile (icl_gemm_select_tile(...) == 3 and K >= 128, or args->tile = 3) — otherwise ICL_EINVAL, and the
+ * caller issues the two calls.  A section may be EMPTY: a launch over the k | v rows of the weight alone has k_off = 0,
+ * v_off = n_heads*128, N = 2*n_heads*128; one over its q rows alone has k_off = v_off = N = n_heads*128 (the last decoder
+ * layer of a prefill projects k / v for every row and q for the last row of each sequence only).  Remaining arguments as icl_rope_kv_bf16.  kv_rows_to_c = 0 (needs a cache): the k / v
  * column blocks of C are NOT written — they exist only in the cache, where icl_attn_fwd_bf16 can read them
  * (kv_seq_stride / kv_head_stride); q is always written.
  * Replaces q_proj/k_proj/v_proj + apply_rotary_pos_emb + DynamicCache.update of transformers'
@@ -388,7 +399,8 @@ int icl_lora_down_bf16(void* X, int64_t ldx, int32_t K0, const void* A, int64_t 
  *   the image [groups][T_a + 128][channels/groups] with 64 zero rows in front / 64 behind, located at
  *   element offset (cu_rows[a] + 128*a)*channels: row t of group g then sees the 128x48 taps of
  *   Conv1d(768,768,k=128,pad=64,groups=16) as ONE contiguous K = 6144 run (lda = 48).
- * icl_gather_rows_f32: out[r][:] = src[idx[r]][:]  (last-token rows for the LM head).
+ * icl_gather_rows_f32 / icl_gather_rows_bf16: out[r][:] = src[idx[r]][:]  (last-token rows for the LM head; the rows the last
+ *   decoder layer of a prefill keeps).  16-byte moves: N and the leading dimensions are multiples of 4 (f32) / 8 (bf16).
  */
 int icl_beats_patchify(const float* fbank, int32_t max_frames, const int32_t* cu_rows, int32_t n_audio,
                        int32_t total_rows, void* out, void* stream);
@@ -396,6 +408,8 @@ int icl_beats_posconv_pack(float* x, const int32_t* cu_rows, const int32_t* vali
                            int32_t total_rows, int32_t channels, int32_t groups, void* xg, void* stream);
 int icl_gather_rows_f32(const float* src, int64_t ld_src, const int32_t* idx, float* out, int64_t ld_out,
                         int32_t rows, int32_t N, void* stream);
+int icl_gather_rows_bf16(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out,
+                         int32_t rows, int32_t N, void* stream);
 
 /* ---- K11 (beam search): one step of HF's static-shaped beam search + the cache reorder ------------------------------
  * icl_beam_step, per batch row b (num_beams K <= 8, max_new_tokens T <= 64, V >= 2K): log-softmax of the K beams' logits
