@@ -75,7 +75,7 @@ __device__ __forceinline__ float max_xhalf(float v) {
 // key 0, ascending) and the interior / masked form of every tile: its output is the full launch's, bit for bit.  Blocks and waves
 // whose positions hold no query drop out (a wave still stages its share of each tile and keeps the barriers).
 template <int D, bool CAUSAL, bool BIAS, bool SUFFIX = false>
-__global__ __launch_bounds__(256, (D == 64 && BIAS) ? 3 : 2) void attn_fwd_kernel(AttnParams p, const int* cu_q) {
+__global__ __launch_bounds__(256, (D == 64 && BIAS && !CAUSAL) ? 3 : 2) void attn_fwd_kernel(AttnParams p, const int* cu_q) {
   // 32-query blocks per wave.  D = 64 without bias runs attn_fwd_il64_kernel below (two blocks per wave sharing every K / V
   // fragment, stages interleaved by hand); this kernel serves D = 128 and the gated-bias variant, one block per wave
   // (measured for the bias variant: its longer per-score sequence wants the third wave per SIMD more than the sharing,
@@ -88,7 +88,10 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS) ? 3 : 2) void attn_fwd_kerne
   // 3.7e-3 (relative L2) from the oracle — measured by rounding P inside the ORACLE — against the north star's 1e-3; with the
   // split they sit at the level of the other, mirrored, rounding points.  The D = 64 encoder kernels keep one term: they
   // meet ~1e-3 already and are vector-issue-bound, where the extra conversions would cost 15-20 %.
-  constexpr bool P2 = (D == 128);
+  // CAUSAL at D = 64 (no model here runs it: every decoder has head_dim 128) takes the split too: a causal query near the start
+  // of its sequence sees a handful of keys, nothing averages the roundings of P, and one-term P (unit roundoff 2^-8) then
+  // misses the per-element bound of tests/test_gpu_attention_exact.py (measured 1.08 x the bound at 3 visible keys).
+  constexpr bool P2 = (D == 128) || CAUSAL;
   constexpr int BQ = 128 * QB;      // queries per workgroup
   constexpr int ROWB = D * 2;       // bytes per K / V row in LDS (unpadded: LDS-DMA writes lane-linear)
   constexpr int KS = D / 16;        // QK^T k-steps
@@ -539,7 +542,8 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS) ? 3 : 2) void attn_fwd_kerne
 // K and V fragments are read once per tile into registers (the V fragments take over the K fragments' registers) and feed
 // both blocks, exactly as above; the scalar (non-packed) score math keeps the shadow usable.  Arithmetic per query is that of
 // the generic kernel operation for operation (k-step order per accumulator, softmax formulas, sequential row sum).
-// (the causal form is not on any model's path here: it gets the registers it asks for instead of spilling at two waves per SIMD)
+// (the causal form is not on any model's path here and is no longer launched: D = 64 causal runs attn_fwd_kernel<64, true, *>
+// with the two-term P; the CAUSAL = true body below is kept as the form the generic kernel was checked against)
 constexpr int IL64_NW = 4;   // waves per workgroup of the interleaved kernel (64 queries each).  An 8-wave form (512 queries share a
                              // staged K / V tile, half the LDS-DMA instructions per wave) was bit-identical and 2-3.5 % SLOWER on both
                              // encoder shapes (profiles/r02_attn_ablations.log); it is gone: one instantiation, its invariants asserted
@@ -853,12 +857,11 @@ __global__ __launch_bounds__(64 * NW, CAUSAL ? 1 : 2) void attn_fwd_il64_kernel(
 
 template <int D>
 int launch_attn(const AttnParams& p, const icl_attn_args* a, const int* cu_q, hipStream_t stream) {
-  const int bq = (D == 64 && !a->rel_bias) ? IL64_NW * 64 : 128;   // queries per workgroup
+  const int bq = (D == 64 && !a->rel_bias && !a->causal) ? IL64_NW * 64 : 128;   // queries per workgroup
   dim3 grid(((a->max_seqlen + bq - 1) / bq) * a->n_heads * a->n_seqs, 1, 1);
   const bool bias = a->rel_bias != nullptr;
-  if (D == 64 && !bias) {
-    if (a->causal) hipLaunchKernelGGL((attn_fwd_il64_kernel<true, IL64_NW>), grid, dim3(64 * IL64_NW), 0, stream, p);
-    else hipLaunchKernelGGL((attn_fwd_il64_kernel<false, IL64_NW>), grid, dim3(64 * IL64_NW), 0, stream, p);
+  if (D == 64 && !bias && !a->causal) {     // the causal form runs the generic kernel below, with its two-term P
+    hipLaunchKernelGGL((attn_fwd_il64_kernel<false, IL64_NW>), grid, dim3(64 * IL64_NW), 0, stream, p);
     ICL_CHECK_LAUNCH("icl_attn_fwd_bf16");
     return ICL_OK;
   }
@@ -913,7 +916,7 @@ static int attn_fwd_impl(const icl_attn_args* a, const int32_t* cu_q, void* stre
   p.kv_seq_stride = a->kv_seq_stride; p.kv_head_stride = a->kv_head_stride;
   p.n_heads = a->n_heads;
   p.rel_span = a->rel_span;
-  const int bq = (a->head_dim == 64 && !a->rel_bias) ? IL64_NW * 64 : 128;
+  const int bq = (a->head_dim == 64 && !a->rel_bias && !a->causal) ? IL64_NW * 64 : 128;
   p.n_qblocks = (a->max_seqlen + bq - 1) / bq;
   p.scale_log2e = a->scale * LOG2E;
   return a->head_dim == 64 ? launch_attn<64>(p, a, cu_q, (hipStream_t)stream) : launch_attn<128>(p, a, cu_q, (hipStream_t)stream);

@@ -154,6 +154,15 @@ int icl_gemm_select_tile(int32_t M, int32_t N, int32_t K, int32_t batch, int32_t
  *                   (BEATs gated relative position bias, K5).
  * head_dim must be 64 or 128.  Q/K/V row strides are in elements (so a fused QKV buffer can
  * be addressed in place); head h lives at column h*head_dim of its row.
+ * Contracts the tests rely on (tests/test_gpu_attention_exact.py):
+ *   - max_seqlen must bound every sequence length (the grid is sized from it: queries at positions
+ *     >= max_seqlen would not be computed).
+ *   - An empty sequence (cu_seqlens[s+1] == cu_seqlens[s]) is allowed anywhere in a pack: it owns no
+ *     row and its kv_lens entry is not read.
+ *   - With kv_lens, the K and V rows in [kv_lens[s], len) must hold FINITE values.  They are staged
+ *     with their 64-key tile; their scores are replaced (any finite K gives the same bits as zeros) and
+ *     their weight is exactly 0, but 0 * NaN or 0 * Inf in the PV product is NaN.  Rows past len (cache
+ *     layout: up to max_len) are never read and may hold anything.
  */
 typedef struct icl_attn_args {
   const void* Q; const void* K; const void* V; /* bf16 */
