@@ -508,15 +508,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_bf16_kernel(GemmParams p_in, R
 template <bool ROPE, int EPI>
 int launch256(const GemmParams& p, const dim3& grid, hipStream_t stream, const RopeFuse& rf) {
   auto kern = gemm256_bf16_kernel<ROPE, EPI>;
-  static bool attr_set = false;      // one flag per instantiation
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, T256_SMEM);
-    if (e != hipSuccess) {
-      icl_set_error("icl_gemm_bf16: hipFuncSetAttribute(%d) failed: %s", T256_SMEM, hipGetErrorString(e));
-      return ICL_ELAUNCH;
-    }
-    attr_set = true;
-  }
+  if (const int rc = allow_dynamic_lds<gemm256_bf16_kernel<ROPE, EPI>>(T256_SMEM)) return rc;
   hipLaunchKernelGGL(kern, grid, dim3(512), T256_SMEM, stream, p, rf);
   ICL_CHECK_LAUNCH("icl_gemm_bf16(256)");
   return ICL_OK;

@@ -1,4 +1,5 @@
-// gemm_common.h — parameter block and epilogue helpers shared by the GEMM translation units (gemm.hip, gemm256.hip).
+// gemm_common.h — parameter block and epilogue helpers shared by the GEMM translation units (gemm.hip, gemm256.hip,
+// gemm_decode.hip).
 #pragma once
 #include "common.h"
 #include <algorithm>
@@ -189,7 +190,28 @@ struct RopeFuse {
   int kv_rows_to_c;   // 0: k / v go to the cache only (the prefill attention reads them there)
 };
 
+// Raise the dynamic-LDS limit of the kernel instantiation KERN to `bytes`: once per process, one flag per instantiation.
+template <auto KERN>
+int allow_dynamic_lds(int bytes) {
+  static bool done = false;
+  if (!done) {
+    const hipError_t e = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) {
+      icl_set_error("icl_gemm_bf16: hipFuncSetAttribute(%d) failed: %s", bytes, hipGetErrorString(e));
+      return ICL_ELAUNCH;
+    }
+    done = true;
+  }
+  return ICL_OK;
+}
+
 // 256x256 rolling-pipeline tile (gemm256.hip): one kernel instantiation per epilogue kind, selected on the host
 int launch_tile256(GemmParams& p, int batch, hipStream_t stream, const RopeFuse* rope = nullptr);
+
+// decode kernels (gemm_decode.hip).  The skinny kernels (M <= 64, batch 1; one entry point for bf16 weights, one for fp8) read W in one of three forms: row-major (tile 4), the
+// decode-packed copy (tile 6), or the fp8 decode-packed copy with its row scales `wscale` (icl_gemm_fp8w)
+enum SkinnyW { SKINNY_W_ROW = 0, SKINNY_W_PACKED = 1, SKINNY_W_FP8 = 2 };
+int launch_skinny(const GemmParams& p, SkinnyW form, const float* wscale, hipStream_t stream);
+int launch_decode_tile(const GemmParams& p, hipStream_t stream);   // tile 5: M <= 256 on the decode-packed copy, split-K over grid.z
 
 }  // namespace iclg

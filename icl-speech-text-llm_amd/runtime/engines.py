@@ -428,6 +428,12 @@ def t256_split(N: int, K: int, n_cu: int) -> int:
     return split if split >= 2 and tiles * split >= 0.45 * n_cu else 0
 
 
+def site_shapes(cfg, k_aug: int) -> Dict[str, Tuple[int, int]]:
+    """(N, K) of the four GEMM sites of a decoder layer (``k_aug``: the QKV projection's K with its LoRA columns)."""
+    hd, I = cfg.hidden, cfg.ffn
+    return dict(qkv=(3 * hd, k_aug), o=(hd, hd), gu=(2 * I, hd), down=(hd, I))
+
+
 def decode_plan(Bn: int, cfg, k_aug: int, n_cu: int, weight_dtype: str = "bf16", decode_packed: bool = True,
                 decode_t256: Sequence[str] = DECODE_SITES, fuse_norms: bool = True) -> DecodePlan:
     """The GEMM launches of one decode step over ``Bn`` rows of a Llama-family decoder (``cfg``: LlamaCfg, ``k_aug``: the QKV
@@ -439,7 +445,6 @@ def decode_plan(Bn: int, cfg, k_aug: int, n_cu: int, weight_dtype: str = "bf16",
     block per CU) 115-167 -> 97-132 us at 128 rows, 214 us at 256 (0.84 vs 1.06 us per row: a weight byte serves twice the rows);
     above 256 the 64x64 LDS tile + split-K on the row-major weights."""
     hd, I = cfg.hidden, cfg.ffn
-    shapes = dict(qkv=(3 * hd, k_aug), o=(hd, hd), gu=(2 * I, hd), down=(hd, I))
 
     def sk(N, K):
         tiles = ((N + 63) // 64) * ((Bn + 63) // 64)
@@ -449,7 +454,7 @@ def decode_plan(Bn: int, cfg, k_aug: int, n_cu: int, weight_dtype: str = "bf16",
     def sk5(N, K):
         return max(1, min(n_cu // ((N + 127) // 128), K // 512))
     plan = {}
-    for name, (N, K) in shapes.items():
+    for name, (N, K) in site_shapes(cfg, k_aug).items():
         if Bn <= 8 and weight_dtype == "fp8":
             tile, split, weight = "fp8w", 1, "fp8"    # FP8 weight mode: the fp8-weight skinny kernel (tile 6's arithmetic on W')
         elif Bn <= 256 and decode_packed:
@@ -496,9 +501,6 @@ class LlamaHIP:
         """The NEXT ``prefill`` call runs as ``prefill(..., last_rows_only=True, last_out=out)``.  The request travels on the
         object, not in the call, so that ``prefill`` keeps its (ws, h, seq_lens, cache) call form for code that wraps it."""
         self._last_rows_out = out
-
-    def _t256_split(self, N: int, K: int) -> int:
-        return t256_split(N, K, self.n_cu)
 
     def decode_plan(self, Bn: int) -> DecodePlan:
         """The GEMM launches of a decode step over Bn rows on this device, in this runtime's weight mode (``decode_plan``)."""
@@ -571,21 +573,21 @@ class LlamaHIP:
         qkv = ws.get(tag + "qkv", (M, 3 * hd), BF16)
         att = ws.get(tag + "att", (M, hd), BF16)
         act = ws.get(tag + "act", (M, I), BF16)
-        site = split.sites if split is not None else {}
-        ps = {k: site[k] if k in site else GemmLaunch(0, 1, "row", 0, 0) for k in DECODE_SITES}
-
-        def tile_of(name):
-            return ps[name].tile
-
-        def weight_of(name, idx, row_major):       # the plan's weight form: row-major, decode-packed (tiles 5 / 6) or fp8 (fp8w)
-            if ps[name].weight == "fp8":           # FP8 weight mode, <= 8 rows: the fp8 decode-packed copy (+ its scales, scale_of)
-                return L.fp8[idx][0]
-            return L.decode_packed[idx] if ps[name].weight == "packed" else row_major
-
-        def scale_of(name, idx):
-            return L.fp8[idx][1] if ps[name].weight == "fp8" else None
-        sk = {k: p.split_k for k, p in ps.items()}
         wsk = ws.get(tag + "splitk", (split.workspace,), F32) if split is not None and split.workspace else None
+
+        def launch_of(name):                       # the plan's launch of this site; prefill: the library's tile on the row-major weight
+            return split.sites[name] if split is not None else GemmLaunch(0, 1, "row", *site_shapes(c, w.k_aug)[name])
+
+        def site_gemm(name, a, out, norm=None, **epilogue):
+            """The GEMM of site ``name`` on the weight form its launch names: row-major, decode-packed (tiles 5 / 6) or the fp8
+            decode-packed copy + row scales (FP8 weight mode, <= 8 rows).  ``norm`` = (gamma, xn): the RMSNorm fused behind it."""
+            p, idx = launch_of(name), DECODE_SITES.index(name)
+            q, scale = L.fp8[idx] if p.weight == "fp8" else (None, None)
+            wt = q if p.weight == "fp8" else L.decode_packed[idx] if p.weight == "packed" else (L.wqkv, L.wo, L.wgu, L.wdown)[idx]
+            kw = dict(split_k=p.split_k, workspace=wsk, tile=p.tile, N=p.N, K=p.K, w_scale=scale, **epilogue)
+            if norm is not None:
+                return B.gemm_rmsnorm(a, wt, out, norm[0], c.rms_eps, norm[1], **kw)
+            return B.gemm(a, wt, out, **kw)
         if not xn_ready:
             B.rmsnorm(h, L.rms1, xn, c.rms_eps, N=hd)
         if L.lora_a is not None:   # x_aug[:, hd:hd+2r] = x @ (s*A)^T : a skinny GEMM for prefill, a GEMV-style kernel for decode
@@ -602,28 +604,22 @@ class LlamaHIP:
             B.gemm(xn, L.wqkv, qkv, bias=L.bqkv, tile=3,
                    rope=(hd, 2 * hd, w.rope_cos, w.rope_sin, pos, seq_ids, kc, vc, H, D, max_len, kv_rows_to_c))
         else:
-            B.gemm(xn, weight_of("qkv", 0, L.wqkv), qkv, bias=L.bqkv, split_k=sk.get("qkv", 1),
-                   workspace=wsk, tile=tile_of("qkv"), N=3 * hd, K=w.k_aug, w_scale=scale_of("qkv", 0))
+            site_gemm("qkv", xn, qkv, bias=L.bqkv)
             if rope_fn is not None:
                 rope_fn(qkv)
             elif not attn_does_rope:    # decode: RoPE + cache append run inside the attention launch (icl_attn_decode_rope_bf16)
                 B.rope_kv(qkv, hd, 2 * hd, w.rope_cos, w.rope_sin, pos, seq_ids, kc, vc, H, D, max_len, M=M)
         attn_fn(qkv, att)
-        if ps["o"].fused_norm:     # decode: h += att Wo^T and the post-attention RMSNorm in one call (one kernel when the GEMM is split-K)
-            B.gemm_rmsnorm(att, weight_of("o", 1, L.wo), h, L.rms2, c.rms_eps, xn, residual=h, split_k=sk.get("o", 1),
-                           workspace=wsk, tile=tile_of("o"), N=hd, K=hd, w_scale=scale_of("o", 1))
+        if launch_of("o").fused_norm:   # decode: h += att Wo^T and the post-attention RMSNorm in one call (one kernel when the GEMM is split-K)
+            site_gemm("o", att, h, norm=(L.rms2, xn), residual=h)
         else:
-            B.gemm(att, weight_of("o", 1, L.wo), h, residual=h, split_k=sk.get("o", 1), workspace=wsk, tile=tile_of("o"),
-                   N=hd, K=hd, w_scale=scale_of("o", 1))
+            site_gemm("o", att, h, residual=h)
             B.rmsnorm(h, L.rms2, xn, c.rms_eps, N=hd)
-        B.gemm(xn, weight_of("gu", 2, L.wgu), act, swiglu=True, K=hd, split_k=sk.get("gu", 1), workspace=wsk,
-               tile=tile_of("gu"), N=2 * I, w_scale=scale_of("gu", 2))
-        if ps["down"].fused_norm and next_norm is not None:
-            B.gemm_rmsnorm(act, weight_of("down", 3, L.wdown), h, next_norm[0], c.rms_eps, next_norm[1], residual=h,
-                           split_k=sk.get("down", 1), workspace=wsk, tile=tile_of("down"), N=hd, K=I, w_scale=scale_of("down", 3))
+        site_gemm("gu", xn, act, swiglu=True)
+        if launch_of("down").fused_norm and next_norm is not None:
+            site_gemm("down", act, h, norm=next_norm, residual=h)
             return True
-        B.gemm(act, weight_of("down", 3, L.wdown), h, residual=h, split_k=sk.get("down", 1), workspace=wsk,
-               tile=tile_of("down"), N=hd, K=I, w_scale=scale_of("down", 3))
+        site_gemm("down", act, h, residual=h)
         return False
 
     # ---- K10: prefill over ragged packed sequences ------------------------------------------------

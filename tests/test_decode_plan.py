@@ -314,5 +314,5 @@ def test_plan_table_is_pinned_at_304_cus(model, Bn, dp):
     (12288, 4160, 256, 4),     # qkv at 7B: 48 N-tiles, min(8, 204 // 48 = 4)
 ])
 def test_t256_split_rules(N, K, n_cu, want):
-    """_t256_split: <= 0.8 * n_cu slices in all, >= 8 K-tiles per slice, >= 2 slices, >= 0.45 * n_cu blocks, else 0."""
+    """t256_split: <= 0.8 * n_cu slices in all, >= 8 K-tiles per slice, >= 2 slices, >= 0.45 * n_cu blocks, else 0."""
     assert E.t256_split(N, K, n_cu) == want

@@ -208,6 +208,58 @@ def test_fp8w_kernel_is_bit_identical_to_tile6_on_w_prime(model, epi):
         assert err < tol, (model, epi, M, err)
 
 
+@pytest.mark.parametrize("K", [64, 192, 576])
+def test_fp8w_tile6_tile4_bit_identical_on_small_shapes(K):
+    """The three weight forms of the skinny kernel (fp8 decode-packed, tile 6 on the decode-packed W', tile 4 on row-major W') at
+    the sizes where their K walks differ most: K = 64 / 192 / 576 gives waves an empty k-step range, a single half-pair, and ranges
+    that start or end inside a k-pair; N = 40 / 264 / 96 leaves the last n-tile ragged or absent; M covers 1, 2 and 4 row blocks.
+    Outputs start as NaN, and the fp8 form is held to test_gpu_decode_plan's per-element fp64 bound, so the three cannot agree
+    on a wrong answer."""
+    from test_gpu_decode_plan import C_DOT, U, _assert_within, _bf16_ulp, _dot
+    B = _B()
+    g = torch.Generator(device=DEV).manual_seed(77 + K)
+    for epi, Ns in (("plain", (16, 40, 264)), ("bias_res", (16, 40, 264)), ("swiglu", (32, 96))):
+        for N in Ns:
+            q, s, wd = B.pack_fp8_weights(_weights(N, K, seed=N + K))
+            dp = B.pack_decode_weights(wd)
+            w64 = wd.double()
+            w64a = w64.abs()
+            for M in (1, 17, 33, 64):
+                what = (K, epi, N, M)
+                a = torch.randn(M, K, device=DEV, generator=g).to(torch.bfloat16)
+                if epi == "plain":
+                    kw, odt, nout = {}, torch.bfloat16, N
+                    ref, mag = _dot(a, w64, w64a)
+                    bound = C_DOT * K * U * mag + U * ref.abs()
+                elif epi == "bias_res":
+                    bias = torch.randn(N, device=DEV, generator=g)
+                    r = torch.randn(M, N, device=DEV, generator=g)
+                    kw, odt, nout = dict(bias=bias, residual=r), torch.float32, N
+                    ref, mag = _dot(a, w64, w64a)
+                    ref = ref + bias.double() + r.double()
+                    bound = C_DOT * K * U * mag + U * ref.abs() + 2 * U * (bias.double().abs() + r.double().abs())
+                else:
+                    kw, odt, nout = dict(swiglu=True), torch.bfloat16, N // 2
+                    gv, uv = (w64.view(N // 32, 2, 16, K)[:, i].reshape(nout, K) for i in range(2))
+                    gate, gmag = _dot(a, gv, gv.abs())
+                    up, umag = _dot(a, uv, uv.abs())
+                    sg = gate * torch.sigmoid(gate)
+                    ref = sg * up
+                    eg = C_DOT * K * U * gmag + U * gate.abs()
+                    eu = C_DOT * K * U * umag + U * up.abs()
+                    bound = 1.1 * eg * (up.abs() + eu) + sg.abs() * eu + U * (16 + 4 * gate.abs()) * ref.abs()
+                o8, o6, o4 = (torch.full((M, nout), float("nan"), dtype=odt, device=DEV) for _ in range(3))
+                B.gemm(a, q, o8, w_scale=s, N=N, K=K, **kw)
+                B.gemm(a, dp, o6, tile=6, N=N, K=K, **kw)
+                B.gemm(a, wd, o4, tile=4, N=N, K=K, **kw)
+                if odt == torch.bfloat16:
+                    bound = bound + _bf16_ulp(torch.maximum(ref.abs(), o8.double().abs()))
+                _assert_within(o8, ref, bound, f"fp8w {what}")
+                bits = torch.int16 if odt == torch.bfloat16 else torch.int32
+                assert torch.equal(o8.view(bits), o6.view(bits)), ("fp8w != tile 6", what)
+                assert torch.equal(o4.view(bits), o6.view(bits)), ("tile 4 != tile 6", what)
+
+
 def test_fp8w_kernel_argument_checks():
     B = _B()
     q, s, wd, dp = _packed("llama7b", "o")
