@@ -20,10 +20,6 @@
 #include "common.h"
 #include <type_traits>
 
-#ifndef ICL_ATTN_V
-#define ICL_ATTN_V 1       // A/B switches of attn_fwd_kernel (tools/attn_ab.sh): bit 0 = no re-staging in the last AHEAD tiles, bit 1 = heavy-first causal q-blocks
-#endif
-
 namespace {
 
 struct AttnParams {
@@ -69,6 +65,106 @@ __device__ __forceinline__ float max_xhalf(float v) {
   return __builtin_fmaxf(__builtin_bit_cast(float, lo), __builtin_bit_cast(float, hi));
 }
 
+// ---- plumbing shared by the two prefill kernels (D = head_dim, NW = waves per workgroup) -------------------------------------
+// Sharing was accepted per piece on the resource figures of the nine kernels (no kernel above its VGPR count, LDS and occupancy
+// as before, no scratch) and on an interleaved A/B against the unshared build (profiles/r06_attn_refactor_ab.txt: output bit-identical;
+// whisper 1.096 -> 1.091 ms, beats_bias 0.872 -> 0.882, llama 0.550 -> 0.546, qwen 0.974 -> 0.969, the unshared build's own spread
+// 0.012-0.021 ms).  The tile loops compile as before; store_output costs 5-23 address instructions once per workgroup.
+// The staging state and stage_tile stay one copy per kernel: see the note in attn_fwd_kernel.
+
+// XCD-aware decode of a 1-D grid: consecutive block ids are dispatched round-robin over the 8 XCDs, each with its own L2.
+// Block b -> work item (b % 8) * ceil(n/8)-chunk + b / 8 (bijective), work items ordered q-block fastest: all q-blocks of
+// one (sequence, head) run on ONE XCD back to back, so its K/V (re-read by every q-block) is fetched into one L2 once.
+__device__ __forceinline__ int xcd_work_item() {
+  const int n_blocks = gridDim.x;
+  const int xcd = blockIdx.x & 7, q8 = n_blocks >> 3, r8 = n_blocks & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+}
+
+// source-side swizzles of the K / V tiles in LDS: slot s of row r holds global 16-B chunk s ^ swz(r) (see the top of the file)
+template <int D> __device__ __forceinline__ int swz_k(int row) { return D == 64 ? (row >> 1) & 7 : row & 15; }
+template <int D> __device__ __forceinline__ int swz_v(int row) { return D == 64 ? ((row >> 1) & 1) << 2 : (row & 3) << 2; }
+
+// Row 0 of K and of V for one (sequence, head): packed rows [cu[seq] + j][head*D ..] of the fused QKV buffer, or — when the strides
+// are given — rows [seq][head][j][..] of a KV cache (the prefill reads back what the QKV GEMM's epilogue appended)
+template <int D>
+__device__ __forceinline__ void kv_row0(const AttnParams& p, int seq, int head, int row0, const unsigned short*& kbase,
+                                        const unsigned short*& vbase) {
+  const int64_t kv_off = p.kv_seq_stride ? (int64_t)seq * p.kv_seq_stride + (int64_t)head * p.kv_head_stride : -1;
+  kbase = kv_off >= 0 ? p.K + kv_off : p.K + (int64_t)row0 * p.ldk + head * D;
+  vbase = kv_off >= 0 ? p.V + kv_off : p.V + (int64_t)row0 * p.ldv + head * D;
+}
+
+// Byte offsets, inside a staged tile, of this lane's fragment reads.
+// K (ds_read_b128): row kb*32 + ql, logical chunk 2*ks + hh -> physical chunk ^ swz_k(row) (swz_k(row + 32) = swz_k(row)).
+// V (transposed ds_read_b64_tr_b16): lane i of a 16-lane group reads row (i>>2) [+4*hh, +8 for the second read], logical chunk
+// 4*d + 2*((lane>>4)&1) + ((lane&3)>>1), half (lane&1); the rows' swz_v depends only on (i>>2).
+template <int D>
+__device__ __forceinline__ void frag_offsets(int (&k_off)[D / 16], int (&tr_off)[D / 32]) {
+  constexpr int ROWB = D * 2;
+  const int lane = threadIdx.x & 63, ql = lane & 31, hh = lane >> 5;
+#pragma unroll
+  for (int ks = 0; ks < D / 16; ++ks) k_off[ks] = ql * ROWB + (((2 * ks + hh) ^ swz_k<D>(ql)) << 4);
+  const int q = (lane & 15) >> 2;
+  const int c2 = ((lane >> 4) & 1) * 2 + ((lane & 3) >> 1);
+#pragma unroll
+  for (int d = 0; d < D / 32; ++d) tr_off[d] = (4 * hh + q) * ROWB + (((4 * d + c2) ^ swz_v<D>(q)) << 4) + (lane & 1) * 8;
+}
+
+// Epilogue: O[q][d] = O^T[d][q] / l for the wave's QB consecutive 32-query blocks (o_acc[QB][D / 32], l_run[QB]; the first
+// block starts at query qw0).  A lane owns one query ROW, so direct stores are 8-B pieces at a row stride: every store
+// instruction touches 64 cache lines.  The K/V ring is dead after the loop's last barrier: each wave transposes its rows through a
+// private LDS region and stores whole head-rows (D * 2 bytes = one or two full lines), 16 B per lane.  An O that is not
+// 16-byte aligned (base or row stride) takes the direct 8-B stores.  SUFFIX: query q goes to packed row qrow0 + q - qstart.
+template <int D, int QB, bool SUFFIX>
+__device__ __forceinline__ void store_output(const AttnParams& p, char* lds, const f32x16* o_acc, const float* l_run, int qw0,
+                                             int head, int row0, int len, int qrow0, int qstart) {
+  constexpr int DB = D / 32;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ql = lane & 31, hh = lane >> 5;
+  float inv[QB];
+#pragma unroll
+  for (int qi = 0; qi < QB; ++qi) {
+    const float l_tot = l_run[qi] + __shfl_xor(l_run[qi], 32, 64);
+    inv[qi] = l_tot > 0.f ? 1.f / l_tot : 0.f;
+  }
+  auto packed = [&](int qi, int d, int g) {      // O^T[d*32 + 8g + 4hh .. +3][this lane's query] as 4 bf16
+    const f32x16& o = o_acc[qi * DB + d];
+    return u32x2{pack_bf16x2(o[4 * g] * inv[qi], o[4 * g + 1] * inv[qi]), pack_bf16x2(o[4 * g + 2] * inv[qi], o[4 * g + 3] * inv[qi])};
+  };
+  const bool rows16 = (((uintptr_t)p.O | (uintptr_t)(p.ldo * 2)) & 15) == 0;
+  if (rows16) {
+    constexpr int PITCH = D * 2 + 16;
+    constexpr int LPR = D * 2 / 16, RPS = 64 / LPR;     // lanes per row, rows per store instruction
+    char* stg = lds + wave * (QB * 32 * PITCH);
+#pragma unroll
+    for (int qi = 0; qi < QB; ++qi)
+#pragma unroll
+      for (int d = 0; d < DB; ++d)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) *(u32x2*)(stg + (qi * 32 + ql) * PITCH + (d * 32 + 8 * g + 4 * hh) * 2) = packed(qi, d, g);
+    __builtin_amdgcn_wave_barrier();                    // same wave, in-order LDS queue
+#pragma unroll
+    for (int it = 0; it < QB * 32 / RPS; ++it) {
+      const int row = it * RPS + lane / LPR, cc = lane % LPR;
+      const int q = qw0 + row;
+      const u32x4 v = *(const u32x4*)(stg + row * PITCH + cc * 16);
+      if (q < len && (!SUFFIX || q >= qstart)) *(u32x4*)(p.O + (int64_t)(SUFFIX ? qrow0 + q - qstart : row0 + q) * p.ldo + head * D + cc * 8) = v;
+    }
+    return;
+  }
+#pragma unroll
+  for (int qi = 0; qi < QB; ++qi) {
+    const int q = qw0 + qi * 32 + ql;
+    if (q < len && (!SUFFIX || q >= qstart)) {
+      unsigned short* op = p.O + (int64_t)(SUFFIX ? qrow0 + q - qstart : row0 + q) * p.ldo + head * D;
+#pragma unroll
+      for (int d = 0; d < DB; ++d)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) *(u32x2*)(op + d * 32 + 8 * g + 4 * hh) = packed(qi, d, g);
+    }
+  }
+}
+
 // SUFFIX (icl_attn_fwd_suffix_bf16): sequence `seq` brings only its LAST q_len = cu_q[seq+1] - cu_q[seq] queries, packed at
 // row cu_q[seq] of Q / O; query i sits at position len - q_len + i of its `len` keys.  The grid, the q-blocks and the waves
 // are laid over POSITIONS exactly as in the full launch, so a query keeps its wave, its lane, its K/V tiles (the 64-key grid from
@@ -76,12 +172,11 @@ __device__ __forceinline__ float max_xhalf(float v) {
 // whose positions hold no query drop out (a wave still stages its share of each tile and keeps the barriers).
 template <int D, bool CAUSAL, bool BIAS, bool SUFFIX = false>
 __global__ __launch_bounds__(256, (D == 64 && BIAS && !CAUSAL) ? 3 : 2) void attn_fwd_kernel(AttnParams p, const int* cu_q) {
-  // 32-query blocks per wave.  D = 64 without bias runs attn_fwd_il64_kernel below (two blocks per wave sharing every K / V
-  // fragment, stages interleaved by hand); this kernel serves D = 128 and the gated-bias variant, one block per wave
-  // (measured for the bias variant: its longer per-score sequence wants the third wave per SIMD more than the sharing,
-  // 407 vs 385 TF/s on the BEATs shape).  The QB > 1 paths are kept: they are the reference the il64 kernel was checked
-  // against bit for bit.
-  constexpr int QB = 1;
+  // The generic kernel: 4 waves, ONE 32-query block per wave, a tile = QK^T -> softmax -> PV in sequence.  It serves D = 128, the
+  // gated-bias variant and D = 64 causal.  D = 64 without bias or mask runs attn_fwd_il64_kernel below (two blocks per wave sharing
+  // every K / V fragment, stages interleaved by hand); the bias variant stays here (measured: its longer per-score sequence wants
+  // the third wave per SIMD more than the sharing, 407 vs 385 TF/s on the BEATs shape).
+  static_assert(D == 128 || BIAS || CAUSAL, "D = 64 without bias or causal mask is attn_fwd_il64_kernel's: this form is never launched");
   // D = 128 (the decoders' prefill / teacher-forced attention): P enters the PV product as a TWO-term bf16 split,
   // P = hi + lo with hi = bf16(P), lo = bf16(P - hi) (16 mantissa bits instead of 8), at the price of a second PV MFMA.
   // The oracle's softmax weights are f32: with one-term bf16 P this single rounding point alone put the decoder logits
@@ -92,7 +187,7 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS && !CAUSAL) ? 3 : 2) void att
   // of its sequence sees a handful of keys, nothing averages the roundings of P, and one-term P (unit roundoff 2^-8) then
   // misses the per-element bound of tests/test_gpu_attention_exact.py (measured 1.08 x the bound at 3 visible keys).
   constexpr bool P2 = (D == 128) || CAUSAL;
-  constexpr int BQ = 128 * QB;      // queries per workgroup
+  constexpr int BQ = 128;           // queries per workgroup
   constexpr int ROWB = D * 2;       // bytes per K / V row in LDS (unpadded: LDS-DMA writes lane-linear)
   constexpr int KS = D / 16;        // QK^T k-steps
   constexpr int DB = D / 32;        // output d-blocks
@@ -103,22 +198,15 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS && !CAUSAL) ? 3 : 2) void att
   constexpr int NBUF = D == 64 ? 3 : 2;   // ring depth: tiles are staged NBUF-1 iterations ahead (D=128: 2 x 32 KiB keeps 2 blocks/CU)
   constexpr int AHEAD = NBUF - 1;
   __shared__ __attribute__((aligned(16))) char lds[NBUF * BUF];   // ONE barrier per KV tile
-  // gated relative-position bias: per tile and q-block the 95 table entries a wave can touch (rel = key - query over
-  // 64 keys x 32 queries) are staged once into a wave-private LDS window; a score then costs one ds_read_b32 at
-  // base + immediate instead of clamp + 64-bit address + global gather
-  __shared__ float bias_win[BIAS ? 4 * QB * 128 : 1];
+  // gated relative-position bias: per tile the 95 table entries a wave can touch (rel = key - query over 64 keys x 32 queries)
+  // are staged once into a wave-private LDS window; a score then costs one ds_read_b32 at base + immediate instead of
+  // clamp + 64-bit address + global gather
+  __shared__ float bias_win[BIAS ? 4 * 128 : 1];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ql = lane & 31, hh = lane >> 5;
-  // XCD-aware decode of a 1-D grid: consecutive block ids are dispatched round-robin over the 8 XCDs, each with its own L2.
-  // Block b -> work item (b % 8) * ceil(n/8)-chunk + b / 8 (bijective), work items ordered q-block fastest: all q-blocks of
-  // one (sequence, head) run on ONE XCD back to back, so its K/V (re-read by every q-block) is fetched into one L2 once.
-  const int n_blocks = gridDim.x;
-  const int xcd = blockIdx.x & 7, q8 = n_blocks >> 3, r8 = n_blocks & 7;
-  const int item = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  // causal: the q-blocks of a (sequence, head) are dealt last-first — block j walks j + 1 K/V tile pairs, so the long blocks of
-  // the launch start first and its tail is made of short ones
-  const int qblk = (CAUSAL && (ICL_ATTN_V & 2)) ? p.n_qblocks - 1 - item % p.n_qblocks : item % p.n_qblocks;
+  const int item = xcd_work_item();
+  const int qblk = item % p.n_qblocks;
   const int head = (item / p.n_qblocks) % p.n_heads, seq = item / (p.n_qblocks * p.n_heads);
   const int row0 = p.cu[seq];
   const int len = p.cu[seq + 1] - row0;
@@ -135,36 +223,31 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS && !CAUSAL) ? 3 : 2) void att
   if (p.kv_lens) kvlen = min(max(p.kv_lens[seq], 1), len);
   const int kv_end = CAUSAL ? min(kvlen, qb + BQ) : kvlen;
   const int n_tiles = (kv_end + 63) >> 6;
-  const bool wave_has_q = !SUFFIX || qb + wave * (32 * QB) + 32 * QB > qstart;   // wave-uniform
 
-  int qw[QB], qpos[QB];           // first query of each of this wave's q-blocks / this lane's query in it
-  bf16x8 qf[QB][KS];              // Q fragments (B operand of S^T = K Q^T): lane (q, hh) holds Q[q][16ks + 8hh .. +7]
-  float gate[QB];
+  const int qw = qb + wave * 32;   // first query of this wave's block
+  const int qpos = qw + ql;        // this lane's query
+  const bool wave_has_q = !SUFFIX || qw + 32 > qstart;   // wave-uniform
+  bf16x8 qf[KS];                   // Q fragments (B operand of S^T = K Q^T): lane (q, hh) holds Q[q][16ks + 8hh .. +7]
+  float gate = 0.f;
   const float* bias_row = nullptr;
-#pragma unroll
-  for (int qi = 0; qi < QB; ++qi) {
-    qw[qi] = qb + (wave * QB + qi) * 32;
-    qpos[qi] = qw[qi] + ql;
-    const int qrow = min(qpos[qi], len - 1);
+  {
+    const int qrow = min(qpos, len - 1);
     const unsigned short* qp = p.Q + (int64_t)(SUFFIX ? qrow0 + max(qrow - qstart, 0) : row0 + qrow) * p.ldq + head * D + hh * 8;
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[qi][ks] = *(const bf16x8*)(qp + ks * 16);
-    gate[qi] = 0.f;
-    if (BIAS) gate[qi] = p.rel_gate[(int64_t)(row0 + qrow) * p.n_heads + head] * LOG2E;
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const bf16x8*)(qp + ks * 16);
+    if (BIAS) gate = p.rel_gate[(int64_t)(row0 + qrow) * p.n_heads + head] * LOG2E;
   }
   if (BIAS) bias_row = p.rel_bias + (int64_t)head * (2 * p.rel_span - 1) + (p.rel_span - 1);
 
   // ---- staging: LDS-DMA with source-side swizzle --------------------------------------------------------
+  // (Two copies, here and in attn_fwd_il64_kernel, on purpose.  As one struct templated on D and the wave count — members kbase /
+  // vbase / kptr / vptr / srow / kch / vch, a tile(t, buf) method — the code is the same after inlining, yet hipcc's allocation
+  // moved: attn_fwd_kernel<128, 1, 0, suffix> went from 252 to 254 VGPRs, and three variants of the struct gave the same 254.)
   // DMA instruction j = wave * NCH + i of a tensor covers rows RPI*j .. RPI*j + RPI-1; lane l lands in row RPI*j + l / CPR,
   // slot l % CPR, and fetches global chunk slot ^ f(row).  Row pointers advance by one tile per iteration; only a tile that
   // crosses the end of the sequence takes the clamped form (rows past the end are masked, the read must stay in bounds).
-  auto f_k = [](int row) { return D == 64 ? (row >> 1) & 7 : row & 15; };
-  auto f_v = [](int row) { return D == 64 ? ((row >> 1) & 1) << 2 : (row & 3) << 2; };
-  // row 0 of this (sequence, head): packed rows [cu[seq] + j][head*D ..] of the fused QKV buffer, or — when the strides are
-  // given — rows [seq][head][j][..] of a KV cache (the prefill reads back what the QKV GEMM's epilogue appended)
-  const int64_t kv_off = p.kv_seq_stride ? (int64_t)seq * p.kv_seq_stride + (int64_t)head * p.kv_head_stride : -1;
-  const unsigned short* kbase = kv_off >= 0 ? p.K + kv_off : p.K + (int64_t)row0 * p.ldk + head * D;
-  const unsigned short* vbase = kv_off >= 0 ? p.V + kv_off : p.V + (int64_t)row0 * p.ldv + head * D;
+  const unsigned short *kbase, *vbase;      // row 0 of this (sequence, head)
+  kv_row0<D>(p, seq, head, row0, kbase, vbase);
   const unsigned short* kptr[NCH];
   const unsigned short* vptr[NCH];
   int srow[NCH], kch[NCH], vch[NCH];
@@ -172,8 +255,8 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS && !CAUSAL) ? 3 : 2) void att
   for (int i = 0; i < NCH; ++i) {
     const int j = wave * NCH + i;
     srow[i] = RPI * j + lane / CPR;
-    kch[i] = (lane % CPR) ^ f_k(srow[i]);
-    vch[i] = (lane % CPR) ^ f_v(srow[i]);
+    kch[i] = (lane % CPR) ^ swz_k<D>(srow[i]);
+    vch[i] = (lane % CPR) ^ swz_v<D>(srow[i]);
     kptr[i] = kbase + (int64_t)srow[i] * p.ldk + kch[i] * 8;
     vptr[i] = vbase + (int64_t)srow[i] * p.ldv + vch[i] * 8;
   }
@@ -200,32 +283,15 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS && !CAUSAL) ? 3 : 2) void att
     }
   };
 
-  f32x16 o_acc[QB][DB];
-  float m_run[QB], l_run[QB];
+  f32x16 o_acc[DB];
+  float m_run = NEG_BIG, l_run = 0.f;
 #pragma unroll
-  for (int qi = 0; qi < QB; ++qi) {
-    m_run[qi] = NEG_BIG;
-    l_run[qi] = 0.f;
+  for (int d = 0; d < DB; ++d)
 #pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o_acc[qi][d][r] = 0.f;
-  }
+    for (int r = 0; r < 16; ++r) o_acc[d][r] = 0.f;
 
-  // K fragment reads: row kb*32 + ql, logical chunk 2*ks + hh -> physical chunk ^ f_k(row) (f_k(row + 32) = f_k(row))
-  int k_off[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) k_off[ks] = ql * ROWB + (((2 * ks + hh) ^ f_k(ql)) << 4);
-  // transposed V reads: lane i of a 16-lane group reads row (i>>2) [+4*hh, +8 for the second read], logical chunk
-  // 4*d + 2*((lane>>4)&1) + ((lane&3)>>1), half (lane&1); the rows' f_v depends only on (i>>2)
-  int tr_off[DB];
-  {
-    const int q = (lane & 15) >> 2;
-    const int c2 = ((lane >> 4) & 1) * 2 + ((lane & 3) >> 1);
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-      tr_off[d] = (4 * hh + q) * ROWB + (((4 * d + c2) ^ f_v(q)) << 4) + (lane & 1) * 8;
-  }
+  int k_off[KS], tr_off[DB];
+  frag_offsets<D>(k_off, tr_off);
 
   // counted waits: the AHEAD-1 youngest tiles (2*NCH LDS-DMA instructions each) stay in flight across the barrier
   auto wait_oldest_tile = [&]() {
@@ -240,8 +306,8 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS && !CAUSAL) ? 3 : 2) void att
   int cur = 0;            // ring slot of tile t
 
   // One KV tile.  MAYMASK = false is the interior form: every key of the tile is visible to every query of the wave, so
-  // the body carries no mask, no per-q-block branch and none of the key-index arithmetic hipcc otherwise hoists above the
-  // "need_mask" test and executes on every tile (35 vector instructions per iteration of the D = 64 kernel).
+  // the body carries no mask and none of the key-index arithmetic hipcc otherwise hoists above the "need_mask" test and
+  // executes on every tile (35 vector instructions per iteration of the D = 64 kernel).
   auto tile = [&](const int t, auto maymask_c, auto last_c) {
     constexpr bool MAYMASK = decltype(maymask_c)::value;
     constexpr bool LAST = decltype(last_c)::value;      // one of the last AHEAD tiles: nothing left to stage
@@ -255,29 +321,20 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS && !CAUSAL) ? 3 : 2) void att
     const int k0 = t * 64;
     const char* k_lds = lds + cur * BUF;
     const char* v_lds = k_lds + 64 * ROWB;
-    // wave-uniform: which of this wave's q-blocks see a key of this tile?
-    bool active[QB];
-    bool any_active = false;
+    // wave-uniform: does this wave's block see a key of this tile (and, SUFFIX, hold a query at all)?
+    const bool active = (!MAYMASK || !CAUSAL || (k0 <= qw + 31)) && wave_has_q;
+    if (active) {
+      // ---- S^T = K Q^T ------------------------------------------------------------------------------------------
+      f32x16 s_acc[2];
 #pragma unroll
-    for (int qi = 0; qi < QB; ++qi) {
-      active[qi] = !MAYMASK || !CAUSAL || (k0 <= qw[qi] + 31);
-      if constexpr (SUFFIX) active[qi] = active[qi] && wave_has_q;
-      any_active |= active[qi];
-    }
-    if (any_active) {
-      // ---- S^T = K Q^T: every K fragment is read once and feeds all q-blocks --------------------------------
-      f32x16 s_acc[QB][2];
+      for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-      for (int qi = 0; qi < QB; ++qi)
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) s_acc[qi][kb][r] = 0.f;
+        for (int r = 0; r < 16; ++r) s_acc[kb][r] = 0.f;
       // K fragments by inline-asm ds_read_b128 with hand-counted waits, LA k-steps ahead of the MFMAs that consume them
       // (same reason as the V reads below: a compiler-visible LDS read makes hipcc wait for every LDS-DMA in flight).
       // k-step outer, key-half inner: each accumulator still sums its k-steps in ascending order.
       {
-        constexpr int LA = QB == 2 ? 1 : 2;
+        constexpr int LA = 2;
         bf16x8 kf[LA + 1][2];
         auto read_k = [&](int ks, int slot) {
 #pragma unroll
@@ -298,111 +355,93 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS && !CAUSAL) ? 3 : 2) void att
           else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kf[slot][0]), "+v"(kf[slot][1]));
 #pragma unroll
           for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int qi = 0; qi < QB; ++qi)
-              if (active[qi])
-                s_acc[qi][kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[slot][kb], qf[qi][ks], s_acc[qi][kb], 0, 0, 0);
+            s_acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[slot][kb], qf[ks], s_acc[kb], 0, 0, 0);
         }
       }
-      // ---- scores -> base-2 logits, bias, mask, online softmax; per q-block ---------------------------------------
-      bf16x8 pf[QB][2][2];
-      bf16x8 pl[P2 ? QB : 1][2][2];      // low halves of the two-term bf16 split of P (D = 128 only)
+      // ---- scores -> base-2 logits, bias, mask, online softmax --------------------------------------------------
+      bf16x8 pf[2][2];
+      bf16x8 pl[2][2];      // low halves of the two-term bf16 split of P (P2 only)
+      // need_mask is wave-uniform: interior tiles take the branch-free fast path (raw v_exp_f32, one FMA per score)
+      const bool need_mask =
+          MAYMASK && __builtin_amdgcn_readfirstlane((int)((k0 + 64 > kvlen) || (CAUSAL && (k0 + 63 > qw))));
+      float psum = 0.f, alpha;
+      if (!BIAS && !need_mask) {
+        float tmax = max32(s_acc[0], s_acc[1]);
+        tmax = max_xhalf(tmax) * p.scale_log2e;   // scale > 0: max commutes with the scaling
+        const float m_new = __builtin_fmaxf(m_run, tmax);
+        alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        m_run = m_new;
+        // two scores per vector instruction where the ISA has a packed f32 form (v_pk_fma_f32, v_pk_add_f32: the
+        // accumulator registers are consecutive, so pairs are free); the row sum runs as two partial sums
+        const f32x2 sc2 = {p.scale_log2e, p.scale_log2e}, nm2 = {-m_new, -m_new};
+        f32x2 ps2 = {0.f, 0.f};
 #pragma unroll
-      for (int qi = 0; qi < QB; ++qi) {
-        if (!active[qi]) {
+        for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-          for (int kb = 0; kb < 2; ++kb)
+          for (int r = 0; r < 16; r += 2) {
+            const f32x2 x = f32x2{s_acc[kb][r], s_acc[kb][r + 1]} * sc2 + nm2;
+            const f32x2 e = {__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1])};
+            ps2 += e;
 #pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2)
+            for (int h = 0; h < 2; ++h) {
+              pf[kb][r >> 3][(r & 7) + h] = (__bf16)e[h];
+              if (P2) pl[kb][r >> 3][(r & 7) + h] = (__bf16)(e[h] - (float)pf[kb][r >> 3][(r & 7) + h]);
+            }
+          }
+        psum = ps2[0] + ps2[1];
+      } else {
+        float tmax;
+        const float* win = nullptr;
+        if (BIAS) {
+          float* w = bias_win + wave * 128;
+          const int base_rel = k0 - qw - 31;          // window index i <-> rel = base_rel + i, i in [0, 95)
 #pragma unroll
-              for (int e = 0; e < 8; ++e) {
-                pf[qi][kb][h2][e] = (__bf16)0.f;
-                if (P2) pl[qi][kb][h2][e] = (__bf16)0.f;
-              }
-          continue;
+          for (int i = 0; i < 2; ++i) {
+            const int rel = max(-(p.rel_span - 1), min(p.rel_span - 1, base_rel + lane + 64 * i));
+            w[lane + 64 * i] = bias_row[rel];
+          }
+          __builtin_amdgcn_wave_barrier();                 // same wave, in-order LDS queue: the reads below see the writes
+          win = w + (4 * hh - ql + 31);
         }
-        // need_mask is wave-uniform: interior tiles take the branch-free fast path (raw v_exp_f32, one FMA per score)
-        const bool need_mask =
-            MAYMASK && __builtin_amdgcn_readfirstlane((int)((k0 + 64 > kvlen) || (CAUSAL && (k0 + 63 > qw[qi]))));
-        float psum = 0.f, alpha;
-        if (!BIAS && !need_mask) {
-          float tmax = max32(s_acc[qi][0], s_acc[qi][1]);
-          tmax = max_xhalf(tmax) * p.scale_log2e;   // scale > 0: max commutes with the scaling
-          const float m_new = __builtin_fmaxf(m_run[qi], tmax);
-          alpha = __builtin_amdgcn_exp2f(m_run[qi] - m_new);
-          m_run[qi] = m_new;
-          // two scores per vector instruction where the ISA has a packed f32 form (v_pk_fma_f32, v_pk_add_f32: the
-          // accumulator registers are consecutive, so pairs are free); the row sum runs as two partial sums
-          const f32x2 sc2 = {p.scale_log2e, p.scale_log2e}, nm2 = {-m_new, -m_new};
-          f32x2 ps2 = {0.f, 0.f};
 #pragma unroll
-          for (int kb = 0; kb < 2; ++kb)
+        for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-              const f32x2 x = f32x2{s_acc[qi][kb][r], s_acc[qi][kb][r + 1]} * sc2 + nm2;
-              const f32x2 e = {__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1])};
-              ps2 += e;
-#pragma unroll
-              for (int h = 0; h < 2; ++h) {
-                pf[qi][kb][r >> 3][(r & 7) + h] = (__bf16)e[h];
-                if (P2) pl[qi][kb][r >> 3][(r & 7) + h] = (__bf16)(e[h] - (float)pf[qi][kb][r >> 3][(r & 7) + h]);
-              }
+          for (int r = 0; r < 16; ++r) {
+            const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+            float v = s_acc[kb][r] * p.scale_log2e;
+            if (BIAS) v = fmaf(gate, win[kb * 32 + (r & 3) + 8 * (r >> 2)], v);
+            if (need_mask) {
+              const bool ok = (key < kvlen) && (!CAUSAL || key <= qpos);
+              v = ok ? v : NEG_BIG;
             }
-          psum = ps2[0] + ps2[1];
-        } else {
-          float tmax;
-          const float* win = nullptr;
-          if (BIAS) {
-            float* w = bias_win + (wave * QB + qi) * 128;
-            const int base_rel = k0 - qw[qi] - 31;          // window index i <-> rel = base_rel + i, i in [0, 95)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-              const int rel = max(-(p.rel_span - 1), min(p.rel_span - 1, base_rel + lane + 64 * i));
-              w[lane + 64 * i] = bias_row[rel];
-            }
-            __builtin_amdgcn_wave_barrier();                 // same wave, in-order LDS queue: the reads below see the writes
-            win = w + (4 * hh - ql + 31);
-          }
-#pragma unroll
-          for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-              float v = s_acc[qi][kb][r] * p.scale_log2e;
-              if (BIAS) v = fmaf(gate[qi], win[kb * 32 + (r & 3) + 8 * (r >> 2)], v);
-              if (need_mask) {
-                const bool ok = (key < kvlen) && (!CAUSAL || key <= qpos[qi]);
-                v = ok ? v : NEG_BIG;
-              }
-              s_acc[qi][kb][r] = v;
-            }
-          }
-          tmax = max_xhalf(max32(s_acc[qi][0], s_acc[qi][1]));
-          const float m_new = __builtin_fmaxf(m_run[qi], tmax);
-          alpha = __builtin_amdgcn_exp2f(m_run[qi] - m_new);
-          m_run[qi] = m_new;
-#pragma unroll
-          for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              float e = __builtin_amdgcn_exp2f(s_acc[qi][kb][r] - m_new);
-              if (need_mask) e = (s_acc[qi][kb][r] <= NEG_BIG * 0.5f) ? 0.f : e;
-              psum += e;
-              pf[qi][kb][r >> 3][r & 7] = (__bf16)e;
-              if (P2) pl[qi][kb][r >> 3][r & 7] = (__bf16)(e - (float)pf[qi][kb][r >> 3][r & 7]);
-            }
+            s_acc[kb][r] = v;
           }
         }
-        l_run[qi] = l_run[qi] * alpha + psum;
-        // the running maximum settles after the first tiles: skip the rescale when no query of the wave moved (x * 1.0f is exact)
-        if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
+        tmax = max_xhalf(max32(s_acc[0], s_acc[1]));
+        const float m_new = __builtin_fmaxf(m_run, tmax);
+        alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        m_run = m_new;
 #pragma unroll
-          for (int d = 0; d < DB; ++d)
+        for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) o_acc[qi][d][r] *= alpha;
+          for (int r = 0; r < 16; ++r) {
+            float e = __builtin_amdgcn_exp2f(s_acc[kb][r] - m_new);
+            if (need_mask) e = (s_acc[kb][r] <= NEG_BIG * 0.5f) ? 0.f : e;
+            psum += e;
+            pf[kb][r >> 3][r & 7] = (__bf16)e;
+            if (P2) pl[kb][r >> 3][r & 7] = (__bf16)(e - (float)pf[kb][r >> 3][r & 7]);
+          }
         }
       }
-      // ---- O^T += V^T P^T: every transposed V fragment is read once and feeds all q-blocks ----------------------------
+      l_run = l_run * alpha + psum;
+      // the running maximum settles after the first tiles: skip the rescale when no query of the wave moved (x * 1.0f is exact)
+      if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
+#pragma unroll
+        for (int d = 0; d < DB; ++d)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) o_acc[d][r] *= alpha;
+      }
+      // ---- O^T += V^T P^T ---------------------------------------------------------------------------------------
       // The transposed reads are inline asm with hand-counted lgkmcnt waits: through the builtin, hipcc's waitcnt pass cannot
       // tell the read from the LDS-DMA writes in flight (the tiles staged AHEAD) and puts s_waitcnt vmcnt(0) in front of the
       // first one, which turns the ring back into "wait for everything you just issued".  Tile t itself is known to have
@@ -435,12 +474,8 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS && !CAUSAL) ? 3 : 2) void att
           for (int s = 0; s < 2; ++s) {
             const s16x8 both = __builtin_shufflevector(vr[slot][s][0], vr[slot][s][1], 0, 1, 2, 3, 4, 5, 6, 7);
             const bf16x8 vf = __builtin_bit_cast(bf16x8, both);
-#pragma unroll
-            for (int qi = 0; qi < QB; ++qi)
-              if (active[qi]) {
-                o_acc[qi][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[qi][kb][s], o_acc[qi][d], 0, 0, 0);
-                if (P2) o_acc[qi][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pl[qi][kb][s], o_acc[qi][d], 0, 0, 0);
-              }
+            o_acc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[kb][s], o_acc[d], 0, 0, 0);
+            if (P2) o_acc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pl[kb][s], o_acc[d], 0, 0, 0);
           }
         }
       }
@@ -455,76 +490,19 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS && !CAUSAL) ? 3 : 2) void att
   };
   // interior tiles first (whole tile inside kv_len and, when causal, at or below the wave's first query), then the rest;
   // the split is per wave, every wave still passes one barrier per tile
-  // (with the gated bias too: its interior body is the general path minus the mask and the key-index arithmetic)
+  // (with the gated bias too: its interior body is the general path minus the mask and the key-index arithmetic).
+  // The last AHEAD tiles run the general (may-mask) body without staging; need_mask is evaluated per tile there anyway
   int t = 0;
-  if constexpr (ICL_ATTN_V & 1) {
-    // the last AHEAD tiles run the general (may-mask) body without staging; need_mask is evaluated per tile there anyway
-    const int n_staged = max(n_tiles - AHEAD, 0);
-    const int n_plain = min(n_staged, CAUSAL ? min(kvlen, qw[0] + 1) >> 6 : kvlen >> 6);
-    for (; t < n_plain; ++t) tile(t, std::false_type{}, std::false_type{});
-    for (; t < n_staged; ++t) tile(t, std::true_type{}, std::false_type{});
-    for (; t < n_tiles; ++t) tile(t, std::true_type{}, std::true_type{});
-  } else {
-    const int n_plain = min(n_tiles, CAUSAL ? min(kvlen, qw[0] + 1) >> 6 : kvlen >> 6);
-    for (; t < n_plain; ++t) tile(t, std::false_type{}, std::false_type{});
-    for (; t < n_tiles; ++t) tile(t, std::true_type{}, std::false_type{});
-  }
+  const int n_staged = max(n_tiles - AHEAD, 0);
+  const int n_plain = min(n_staged, CAUSAL ? min(kvlen, qw + 1) >> 6 : kvlen >> 6);
+  for (; t < n_plain; ++t) tile(t, std::false_type{}, std::false_type{});
+  for (; t < n_staged; ++t) tile(t, std::true_type{}, std::false_type{});
+  for (; t < n_tiles; ++t) tile(t, std::true_type{}, std::true_type{});
   // ring slots are about to be reused by the epilogue: every wave's LDS-DMA must have landed
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  // ---- epilogue: O[q][d] = O^T[d][q] / l -------------------------------------------------------------
-  // A lane owns one query ROW, so direct stores are 8-B pieces at a row stride: every store instruction touches 64 cache
-  // lines.  The K/V ring is dead after the loop's last barrier: each wave transposes its rows through a private LDS region
-  // and stores whole head-rows (D * 2 bytes = one or two full lines), 16 B per lane.
-  float inv[QB];
-#pragma unroll
-  for (int qi = 0; qi < QB; ++qi) {
-    const float l_tot = l_run[qi] + __shfl_xor(l_run[qi], 32, 64);
-    inv[qi] = l_tot > 0.f ? 1.f / l_tot : 0.f;
-  }
-  const bool rows16 = (((uintptr_t)p.O | (uintptr_t)(p.ldo * 2)) & 15) == 0;
-  if (rows16) {
-    constexpr int PITCH = D * 2 + 16;
-    constexpr int LPR = D * 2 / 16, RPI = 64 / LPR;     // lanes per row, rows per store instruction
-    char* stg = lds + wave * (QB * 32 * PITCH);
-#pragma unroll
-    for (int qi = 0; qi < QB; ++qi)
-#pragma unroll
-      for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int d0 = d * 32 + 8 * g + 4 * hh;
-          *(u32x2*)(stg + (qi * 32 + ql) * PITCH + d0 * 2) =
-              u32x2{pack_bf16x2(o_acc[qi][d][4 * g] * inv[qi], o_acc[qi][d][4 * g + 1] * inv[qi]),
-                    pack_bf16x2(o_acc[qi][d][4 * g + 2] * inv[qi], o_acc[qi][d][4 * g + 3] * inv[qi])};
-        }
-    __builtin_amdgcn_wave_barrier();                    // same wave, in-order LDS queue
-#pragma unroll
-    for (int it = 0; it < QB * 32 / RPI; ++it) {
-      const int row = it * RPI + lane / LPR, cc = lane % LPR;
-      const int q = qw[row >> 5] + (row & 31);
-      const u32x4 v = *(const u32x4*)(stg + row * PITCH + cc * 16);
-      if (q < len && (!SUFFIX || q >= qstart)) *(u32x4*)(p.O + (int64_t)(SUFFIX ? qrow0 + q - qstart : row0 + q) * p.ldo + head * D + cc * 8) = v;
-    }
-    return;
-  }
-#pragma unroll
-  for (int qi = 0; qi < QB; ++qi) {
-    if (qpos[qi] < len && (!SUFFIX || qpos[qi] >= qstart)) {
-      unsigned short* op = p.O + (int64_t)(SUFFIX ? qrow0 + qpos[qi] - qstart : row0 + qpos[qi]) * p.ldo + head * D;
-#pragma unroll
-      for (int d = 0; d < DB; ++d) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int d0 = d * 32 + 8 * g + 4 * hh;
-          u32x2 pk = {pack_bf16x2(o_acc[qi][d][4 * g] * inv[qi], o_acc[qi][d][4 * g + 1] * inv[qi]),
-                      pack_bf16x2(o_acc[qi][d][4 * g + 2] * inv[qi], o_acc[qi][d][4 * g + 3] * inv[qi])};
-          *(u32x2*)(op + d0) = pk;
-        }
-      }
-    }
-  }
+  store_output<D, 1, SUFFIX>(p, lds, o_acc, &l_run, qw, head, row0, len, qrow0, qstart);
 }
 
 // =====================================================================================================================
@@ -542,14 +520,12 @@ __global__ __launch_bounds__(256, (D == 64 && BIAS && !CAUSAL) ? 3 : 2) void att
 // K and V fragments are read once per tile into registers (the V fragments take over the K fragments' registers) and feed
 // both blocks, exactly as above; the scalar (non-packed) score math keeps the shadow usable.  Arithmetic per query is that of
 // the generic kernel operation for operation (k-step order per accumulator, softmax formulas, sequential row sum).
-// (the causal form is not on any model's path here and is no longer launched: D = 64 causal runs attn_fwd_kernel<64, true, *>
-// with the two-term P; the CAUSAL = true body below is kept as the form the generic kernel was checked against)
+// Non-causal only: D = 64 causal runs attn_fwd_kernel<64, true, *> with its two-term P.
 constexpr int IL64_NW = 4;   // waves per workgroup of the interleaved kernel (64 queries each).  An 8-wave form (512 queries share a
                              // staged K / V tile, half the LDS-DMA instructions per wave) was bit-identical and 2-3.5 % SLOWER on both
                              // encoder shapes (profiles/r02_attn_ablations.log); it is gone: one instantiation, its invariants asserted
-template <bool CAUSAL, int NW>
-__global__ __launch_bounds__(64 * NW, CAUSAL ? 1 : 2) void attn_fwd_il64_kernel(AttnParams p) {
-  constexpr int D = 64, QB = 2, BQ = 32 * NW * QB, ROWB = D * 2, KS = D / 16, DB = D / 32, CPR = D / 8;
+__global__ __launch_bounds__(64 * IL64_NW, 2) void attn_fwd_il64_kernel(AttnParams p) {
+  constexpr int NW = IL64_NW, D = 64, QB = 2, BQ = 32 * NW * QB, ROWB = D * 2, KS = D / 16, DB = D / 32, CPR = D / 8;
   constexpr int NCH = 64 * CPR / (64 * NW), RPI = 64 / CPR, BUF = 2 * 64 * ROWB, NBUF = 3;
   constexpr int EPI = NW * QB * 32 * (D * 2 + 16);       // the epilogue's per-wave transposition buffers reuse the ring
   static_assert(NW == 4 && NCH == 2, "the counted waits below (vmcnt(4) = one tile of 2 K + 2 V LDS-DMA per wave in flight) are for 4 waves");
@@ -558,9 +534,7 @@ __global__ __launch_bounds__(64 * NW, CAUSAL ? 1 : 2) void attn_fwd_il64_kernel(
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ql = lane & 31, hh = lane >> 5;
-  const int n_blocks = gridDim.x;                       // XCD-aware decode, as above
-  const int xcd = blockIdx.x & 7, q8 = n_blocks >> 3, r8 = n_blocks & 7;
-  const int item = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+  const int item = xcd_work_item();
   const int qblk = item % p.n_qblocks;
   const int head = (item / p.n_qblocks) % p.n_heads, seq = item / (p.n_qblocks * p.n_heads);
   const int row0 = p.cu[seq];
@@ -569,27 +543,22 @@ __global__ __launch_bounds__(64 * NW, CAUSAL ? 1 : 2) void attn_fwd_il64_kernel(
   if (qb >= len) return;
   int kvlen = len;
   if (p.kv_lens) kvlen = min(max(p.kv_lens[seq], 1), len);
-  const int kv_end = CAUSAL ? min(kvlen, qb + BQ) : kvlen;
-  const int n_tiles = (kv_end + 63) >> 6;
+  const int n_tiles = (kvlen + 63) >> 6;
 
-  int qw[QB], qpos[QB];
+  int qw[QB];                     // first query of each of this wave's two blocks
   bf16x8 qf[QB][KS];
 #pragma unroll
   for (int qi = 0; qi < QB; ++qi) {
     qw[qi] = qb + (wave * QB + qi) * 32;
-    qpos[qi] = qw[qi] + ql;
-    const int qrow = min(qpos[qi], len - 1);
+    const int qrow = min(qw[qi] + ql, len - 1);
     const unsigned short* qp = p.Q + (int64_t)(row0 + qrow) * p.ldq + head * D + hh * 8;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) qf[qi][ks] = *(const bf16x8*)(qp + ks * 16);
   }
 
-  // ---- staging: LDS-DMA with source-side swizzle (identical to the kernel above) ---------------------------------------
-  auto f_k = [](int row) { return (row >> 1) & 7; };
-  auto f_v = [](int row) { return ((row >> 1) & 1) << 2; };
-  const int64_t kv_off = p.kv_seq_stride ? (int64_t)seq * p.kv_seq_stride + (int64_t)head * p.kv_head_stride : -1;
-  const unsigned short* kbase = kv_off >= 0 ? p.K + kv_off : p.K + (int64_t)row0 * p.ldk + head * D;
-  const unsigned short* vbase = kv_off >= 0 ? p.V + kv_off : p.V + (int64_t)row0 * p.ldv + head * D;
+  // ---- staging: LDS-DMA with source-side swizzle (the generic kernel's, for NW waves: see the note there) -----------------
+  const unsigned short *kbase, *vbase;      // row 0 of this (sequence, head)
+  kv_row0<D>(p, seq, head, row0, kbase, vbase);
   const unsigned short* kptr[NCH];
   const unsigned short* vptr[NCH];
   int srow[NCH], kch[NCH], vch[NCH];
@@ -597,8 +566,8 @@ __global__ __launch_bounds__(64 * NW, CAUSAL ? 1 : 2) void attn_fwd_il64_kernel(
   for (int i = 0; i < NCH; ++i) {
     const int j = wave * NCH + i;
     srow[i] = RPI * j + lane / CPR;
-    kch[i] = (lane % CPR) ^ f_k(srow[i]);
-    vch[i] = (lane % CPR) ^ f_v(srow[i]);
+    kch[i] = (lane % CPR) ^ swz_k<D>(srow[i]);
+    vch[i] = (lane % CPR) ^ swz_v<D>(srow[i]);
     kptr[i] = kbase + (int64_t)srow[i] * p.ldk + kch[i] * 8;
     vptr[i] = vbase + (int64_t)srow[i] * p.ldv + vch[i] * 8;
   }
@@ -636,23 +605,14 @@ __global__ __launch_bounds__(64 * NW, CAUSAL ? 1 : 2) void attn_fwd_il64_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) o_acc[qi][d][r] = 0.f;
   }
-  int k_off[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) k_off[ks] = ql * ROWB + (((2 * ks + hh) ^ f_k(ql)) << 4);
-  int tr_off[DB];
-  {
-    const int q = (lane & 15) >> 2;
-    const int c2 = ((lane >> 4) & 1) * 2 + ((lane & 3) >> 1);
-#pragma unroll
-    for (int d = 0; d < DB; ++d) tr_off[d] = (4 * hh + q) * ROWB + (((4 * d + c2) ^ f_v(q)) << 4) + (lane & 1) * 8;
-  }
+  int k_off[KS], tr_off[DB];
+  frag_offsets<D>(k_off, tr_off);
 
   // softmax of one 32-query block in two parts: head = row maximum, alpha, rescale of O (its wave-uniform branch closes a
   // basic block, so it sits BEFORE the stretch that holds MFMAs); tail = exponentials -> P fragments, row sum
   auto sm_head = [&](const int qi, f32x16 (&s)[2], const int k0, auto maymask_c) -> bool {
     constexpr bool MAYMASK = decltype(maymask_c)::value;
-    const bool need_mask =
-        MAYMASK && __builtin_amdgcn_readfirstlane((int)((k0 + 64 > kvlen) || (CAUSAL && (k0 + 63 > qw[qi]))));
+    const bool need_mask = MAYMASK && __builtin_amdgcn_readfirstlane((int)(k0 + 64 > kvlen));
     float tmax;
     if (!need_mask) {
       tmax = max_xhalf(max32(s[0], s[1])) * p.scale_log2e;   // scale > 0: max commutes with the scaling
@@ -662,8 +622,7 @@ __global__ __launch_bounds__(64 * NW, CAUSAL ? 1 : 2) void attn_fwd_il64_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-          const bool ok = (key < kvlen) && (!CAUSAL || key <= qpos[qi]);
-          s[kb][r] = ok ? s[kb][r] * p.scale_log2e : NEG_BIG;
+          s[kb][r] = key < kvlen ? s[kb][r] * p.scale_log2e : NEG_BIG;
         }
       tmax = max_xhalf(max32(s[0], s[1]));
     }
@@ -798,89 +757,41 @@ __global__ __launch_bounds__(64 * NW, CAUSAL ? 1 : 2) void attn_fwd_il64_kernel(
     cur = cur + 1 == NBUF ? 0 : cur + 1;
   };
   int t = 0;
-  {
-    const int n_plain = min(n_tiles, CAUSAL ? min(kvlen, qw[0] + 1) >> 6 : kvlen >> 6);
-    for (; t < n_plain; ++t) tile(t, std::false_type{});
-  }
+  for (; t < (kvlen >> 6); ++t) tile(t, std::false_type{});      // whole tiles: no mask
   for (; t < n_tiles; ++t) tile(t, std::true_type{});
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  // ---- epilogue (as above) -----------------------------------------------------------------------------------------------
-  float inv[QB];
-#pragma unroll
-  for (int qi = 0; qi < QB; ++qi) {
-    const float l_tot = l_run[qi] + __shfl_xor(l_run[qi], 32, 64);
-    inv[qi] = l_tot > 0.f ? 1.f / l_tot : 0.f;
-  }
-  const bool rows16 = (((uintptr_t)p.O | (uintptr_t)(p.ldo * 2)) & 15) == 0;
-  if (rows16) {
-    constexpr int PITCH = D * 2 + 16;
-    constexpr int LPR = D * 2 / 16, RPS = 64 / LPR;
-    char* stg = lds + wave * (QB * 32 * PITCH);
-#pragma unroll
-    for (int qi = 0; qi < QB; ++qi)
-#pragma unroll
-      for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int d0 = d * 32 + 8 * g + 4 * hh;
-          *(u32x2*)(stg + (qi * 32 + ql) * PITCH + d0 * 2) =
-              u32x2{pack_bf16x2(o_acc[qi][d][4 * g] * inv[qi], o_acc[qi][d][4 * g + 1] * inv[qi]),
-                    pack_bf16x2(o_acc[qi][d][4 * g + 2] * inv[qi], o_acc[qi][d][4 * g + 3] * inv[qi])};
-        }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int it = 0; it < QB * 32 / RPS; ++it) {
-      const int row = it * RPS + lane / LPR, cc = lane % LPR;
-      const int q = qw[row >> 5] + (row & 31);
-      const u32x4 v = *(const u32x4*)(stg + row * PITCH + cc * 16);
-      if (q < len) *(u32x4*)(p.O + (int64_t)(row0 + q) * p.ldo + head * D + cc * 8) = v;
-    }
-    return;
-  }
-#pragma unroll
-  for (int qi = 0; qi < QB; ++qi) {
-    if (qpos[qi] < len) {
-      unsigned short* op = p.O + (int64_t)(row0 + qpos[qi]) * p.ldo + head * D;
-#pragma unroll
-      for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int d0 = d * 32 + 8 * g + 4 * hh;
-          *(u32x2*)(op + d0) = u32x2{pack_bf16x2(o_acc[qi][d][4 * g] * inv[qi], o_acc[qi][d][4 * g + 1] * inv[qi]),
-                                     pack_bf16x2(o_acc[qi][d][4 * g + 2] * inv[qi], o_acc[qi][d][4 * g + 3] * inv[qi])};
-        }
-    }
-  }
+  store_output<D, QB, false>(p, lds, &o_acc[0][0], l_run, qw[0], head, row0, len, row0, 0);
 }
+
+// Only the forms that can be launched are instantiated: attn_fwd_il64_kernel, attn_fwd_kernel<64, 0|1, 1>, <64, 1, 0>,
+// <128, 0|1, 0|1> and the suffix form <128, 1, 0, suffix> — nine kernels.
+inline bool runs_il64(const icl_attn_args* a) { return a->head_dim == 64 && !a->rel_bias && !a->causal; }
+inline int queries_per_block(const icl_attn_args* a) { return runs_il64(a) ? IL64_NW * 64 : 128; }
 
 template <int D>
 int launch_attn(const AttnParams& p, const icl_attn_args* a, const int* cu_q, hipStream_t stream) {
-  const int bq = (D == 64 && !a->rel_bias && !a->causal) ? IL64_NW * 64 : 128;   // queries per workgroup
-  dim3 grid(((a->max_seqlen + bq - 1) / bq) * a->n_heads * a->n_seqs, 1, 1);
-  const bool bias = a->rel_bias != nullptr;
-  if (D == 64 && !bias && !a->causal) {     // the causal form runs the generic kernel below, with its two-term P
-    hipLaunchKernelGGL((attn_fwd_il64_kernel<false, IL64_NW>), grid, dim3(64 * IL64_NW), 0, stream, p);
-    ICL_CHECK_LAUNCH("icl_attn_fwd_bf16");
-    return ICL_OK;
+  const bool bias = a->rel_bias != nullptr, causal = a->causal != 0;
+  const dim3 grid(p.n_qblocks * a->n_heads * a->n_seqs, 1, 1);
+  if constexpr (D == 64) {
+    if (runs_il64(a)) {
+      hipLaunchKernelGGL(attn_fwd_il64_kernel, grid, dim3(64 * IL64_NW), 0, stream, p);
+      ICL_CHECK_LAUNCH("icl_attn_fwd_bf16");
+      return ICL_OK;
+    }
   }
-  if (cu_q) {       // D = 128, causal, no bias: checked by the caller
-    if constexpr (D == 128) hipLaunchKernelGGL((attn_fwd_kernel<128, true, false, true>), grid, dim3(256), 0, stream, p, cu_q);
+  auto go = [&](void (*kernel)(AttnParams, const int*)) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, p, cu_q); };
+  if (cu_q) {       // causal, no bias: checked by the caller
+    ICL_CHECK_ARG(D == 128, "icl_attn_fwd_suffix_bf16: head_dim=%d (only 128)", D);
+    if constexpr (D == 128) go(attn_fwd_kernel<128, true, false, true>);
     ICL_CHECK_LAUNCH("icl_attn_fwd_suffix_bf16");
     return ICL_OK;
   }
-  if (a->causal) {
-    if (bias)
-      hipLaunchKernelGGL((attn_fwd_kernel<D, true, true>), grid, dim3(256), 0, stream, p, nullptr);
-    else
-      hipLaunchKernelGGL((attn_fwd_kernel<D, true, false>), grid, dim3(256), 0, stream, p, nullptr);
-  } else {
-    if (bias)
-      hipLaunchKernelGGL((attn_fwd_kernel<D, false, true>), grid, dim3(256), 0, stream, p, nullptr);
-    else
-      hipLaunchKernelGGL((attn_fwd_kernel<D, false, false>), grid, dim3(256), 0, stream, p, nullptr);
-  }
+  if (causal && bias) go(attn_fwd_kernel<D, true, true>);
+  else if (causal) go(attn_fwd_kernel<D, true, false>);
+  else if (bias) go(attn_fwd_kernel<D, false, true>);
+  else if constexpr (D == 128) go(attn_fwd_kernel<128, false, false>);
   ICL_CHECK_LAUNCH("icl_attn_fwd_bf16");
   return ICL_OK;
 }
@@ -916,8 +827,7 @@ static int attn_fwd_impl(const icl_attn_args* a, const int32_t* cu_q, void* stre
   p.kv_seq_stride = a->kv_seq_stride; p.kv_head_stride = a->kv_head_stride;
   p.n_heads = a->n_heads;
   p.rel_span = a->rel_span;
-  const int bq = (a->head_dim == 64 && !a->rel_bias && !a->causal) ? IL64_NW * 64 : 128;
-  p.n_qblocks = (a->max_seqlen + bq - 1) / bq;
+  p.n_qblocks = (a->max_seqlen + queries_per_block(a) - 1) / queries_per_block(a);
   p.scale_log2e = a->scale * LOG2E;
   return a->head_dim == 64 ? launch_attn<64>(p, a, cu_q, (hipStream_t)stream) : launch_attn<128>(p, a, cu_q, (hipStream_t)stream);
 }

@@ -30,12 +30,13 @@ without bias runs attn_fwd_kernel<64, true, false> in place of the interleaved k
 
 Which test reaches which instantiation (each with a count probe and a peak probe, H = 3 and H = 4: with 128- or 256-query blocks
 one grid is a multiple of 8 workgroups and the other is not, the r8 branch of the XCD remap):
-  test_prefill[D=64, no bias, causal 0]              attn_fwd_il64_kernel<false, 4>             (+ a 513-key sequence: third q-block)
+  test_prefill[D=64, no bias, causal 0]              attn_fwd_il64_kernel                       (+ a 513-key sequence: third q-block)
   test_prefill[D=64, no bias, causal 1]              attn_fwd_kernel<64, true, false>           (+ a 513-key sequence: fifth q-block)
   test_prefill[D=64, bias, causal 0|1]               attn_fwd_kernel<64, false|true, true>      (BEATs: kv_lens + bias)
   test_prefill[D=128, bias 0|1, causal 0|1]          attn_fwd_kernel<128, false|true, false|true>
   ... each with kv_lens none | given, packed rows and the cache layout (NaN past each length)
   test_suffix                                        attn_fwd_kernel<128, true, false, true>
+  test_prefill_unaligned_out                         the 8-byte store path of store_output (O not 16-byte aligned): il64, <128, true, false>, suffix
   test_decode[attn_decode, D, few|many]              attn_decode_kernel<D, 16|4, false, false, 8>
   test_decode[attn_decode_bf16_epl16, D, few|many]   attn_decode_kernel<D, 8|4, false, false, 16>   (anchors the fp8 kernels, tied to it bit for bit)
   test_decode[attn_decode_rope, D, few|many]         attn_decode_kernel<D, 16|4, true, false, 8>    (target = the appended position)
@@ -187,6 +188,33 @@ def test_suffix(B, H):
         R = oa.prefill_ref(q, k, v, lens, H, D, scale, causal=True).rows(idx)
         _report(f"attn_fwd_suffix H={H}", data, oa.assert_bound(out, R, D, oa.R_P["prefill128"], f"suffix {data}"))
         assert torch.equal(out, _fwd(B, q, k, v, lens, H, D, causal=True)[idx])
+
+
+def test_prefill_unaligned_out(B):
+    """O only 8-byte aligned (a column slice, at column 4, of a NaN-filled [rows, H * D + 12] buffer: ldo * 2 = 8 mod 16): the
+    kernels leave the 16-byte row stores for the 8-byte fallback epilogue.  Same bits as the aligned launch, nothing outside O."""
+    H, lens = 3, list(oa.PREFILL_LENS)
+    cu = oa.cu_of(lens)
+    cu_t = torch.tensor(cu, dtype=torch.int32, device=DEV)
+    qlens = [min(L, (0, 1, 33, L)[s % 4]) for s, L in enumerate(lens)]          # those of test_suffix
+    idx = torch.cat([torch.arange(cu[s + 1] - ql, cu[s + 1]) for s, ql in enumerate(qlens)]).to(DEV)
+    cu_q = torch.tensor(oa.cu_of(qlens), dtype=torch.int32, device=DEV)
+    for D, causal, sfx in ((64, False, False), (128, True, False), (128, True, True)):
+        q, k, v = _dev(*oa.random_data(lens, H, D))
+        rows, hd = (sum(qlens), H * D) if sfx else (sum(lens), H * D)
+        kw = dict(causal=causal, cu_q=cu_q) if sfx else dict(causal=causal)
+        if sfx:
+            q = q[idx].contiguous()
+        name = f"attn_fwd D={D} causal={int(causal)} suffix={int(sfx)}"
+        want = torch.full((rows, hd), float("nan"), dtype=torch.bfloat16, device=DEV)
+        B.attn_fwd(q, k, v, want, cu_t, max(lens), H, D, D ** -0.5, **kw)
+        assert not bool(torch.isnan(want.float()).any()), name
+        buf = torch.full((rows, hd + 12), float("nan"), dtype=torch.bfloat16, device=DEV)
+        out = buf[:, 4:4 + hd]
+        assert out.stride(0) % 4 == 0 and out.data_ptr() % 16 == 8 and out.stride(0) * 2 % 16 == 8
+        B.attn_fwd(q, k, v, out, cu_t, max(lens), H, D, D ** -0.5, **kw)
+        assert torch.equal(out, want), f"{name}: 8-byte-aligned O != 16-byte-aligned O"
+        assert bool(torch.isnan(buf[:, :4].float()).all()) and bool(torch.isnan(buf[:, 4 + hd:].float()).all()), f"{name}: wrote outside O"
 
 
 # ------------------------------------------------------------------------------------------------------------------
