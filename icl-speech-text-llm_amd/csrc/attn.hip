@@ -35,6 +35,7 @@ struct AttnParams {
   int64_t kv_seq_stride, kv_head_stride;   // != 0: K/V live in a [seq][head][pos][D]-style cache (row stride ldk / ldv)
   int n_heads, rel_span, n_qblocks;
   float scale_log2e;
+  int kv_group;   // query heads per K/V head (grouped-query attention, head_dim 128 only; 1 = multi-head)
 };
 
 constexpr float NEG_BIG = -1.0e30f;
@@ -86,10 +87,12 @@ template <int D> __device__ __forceinline__ int swz_k(int row) { return D == 64 
 template <int D> __device__ __forceinline__ int swz_v(int row) { return D == 64 ? ((row >> 1) & 1) << 2 : (row & 3) << 2; }
 
 // Row 0 of K and of V for one (sequence, head): packed rows [cu[seq] + j][head*D ..] of the fused QKV buffer, or — when the strides
-// are given — rows [seq][head][j][..] of a KV cache (the prefill reads back what the QKV GEMM's epilogue appended)
+// are given — rows [seq][head][j][..] of a KV cache (the prefill reads back what the QKV GEMM's epilogue appended).
+// Grouped-query attention (D = 128, kv_group > 1): query head `head` reads K/V head head / kv_group — one division per workgroup.
 template <int D>
 __device__ __forceinline__ void kv_row0(const AttnParams& p, int seq, int head, int row0, const unsigned short*& kbase,
                                         const unsigned short*& vbase) {
+  if constexpr (D == 128) head = p.kv_group > 1 ? head / p.kv_group : head;
   const int64_t kv_off = p.kv_seq_stride ? (int64_t)seq * p.kv_seq_stride + (int64_t)head * p.kv_head_stride : -1;
   kbase = kv_off >= 0 ? p.K + kv_off : p.K + (int64_t)row0 * p.ldk + head * D;
   vbase = kv_off >= 0 ? p.V + kv_off : p.V + (int64_t)row0 * p.ldv + head * D;
@@ -826,6 +829,10 @@ static int attn_fwd_impl(const icl_attn_args* a, const int32_t* cu_q, void* stre
                 "icl_attn_fwd_bf16: kv_seq_stride / kv_head_stride must both be 0 or both positive multiples of 8");
   p.kv_seq_stride = a->kv_seq_stride; p.kv_head_stride = a->kv_head_stride;
   p.n_heads = a->n_heads;
+  const int n_kv = a->n_kv_heads ? a->n_kv_heads : a->n_heads;
+  ICL_CHECK_ARG(n_kv > 0 && a->n_heads % n_kv == 0 && (n_kv == a->n_heads || a->head_dim == 128),
+                "icl_attn_fwd_bf16: n_kv_heads=%d must divide n_heads=%d, and differ from it only at head_dim 128", n_kv, a->n_heads);
+  p.kv_group = a->n_heads / n_kv;
   p.rel_span = a->rel_span;
   p.n_qblocks = (a->max_seqlen + queries_per_block(a) - 1) / queries_per_block(a);
   p.scale_log2e = a->scale * LOG2E;

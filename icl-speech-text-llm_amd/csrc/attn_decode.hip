@@ -254,6 +254,124 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
   }
 }
 
+// Grouped-query decode (icl_attn_decode_gqa_bf16): NG query heads share one K/V head, head_dim 128.  One workgroup per (sequence,
+// KV head) with attn_decode_kernel<128, ., false, false, 8>'s lane mapping — 16 lanes per 256-B row, a wave-load = 4 consecutive
+// keys, 4 waves, 16 streams — but every lane holds NG query chunks and NG online-softmax states (m, l, o[8]) and uses the 16-B K
+// chunk and V chunk it loaded for all NG heads: a cache row is read once per workgroup, a decode step streams 1 / NG of the bytes
+// the multi-head kernel reads from the expanded cache.  Query head kvh * NG + g's stream folds the keys attn_decode_kernel gives
+// that stream, in its order and its groups of four, with the same expressions: the result is that kernel's on the expanded cache
+// up to the compiler's FMA contraction.  The 16 streams of a head are merged through LDS as there, one head after the other
+// through the one buffer.  UNR (key rounds in flight) shrinks as NG grows: the state is 18 VGPRs per head.
+template <int NG, int UNR>
+__global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const unsigned short* Q, int64_t ldq, const unsigned short* Kc,
+                                                               const unsigned short* Vc, unsigned short* O, int64_t ldo,
+                                                               const int* lens, int n_kv_heads, int max_len, float scale_log2e) {
+  constexpr int D = 128, EPL = 8, NW = EPL / 2, LPR = D / EPL, KPW = 64 / LPR, NSTREAM = 4 * KPW;
+  __shared__ float sm[NSTREAM][D + 2];  // per stream of ONE head: o[D], m, l
+  const int kvh = blockIdx.x, b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int dc = lane % LPR, sub = lane / LPR;
+  const int len = min(lens[b], max_len);
+  const int64_t base = ((int64_t)b * n_kv_heads + kvh) * (int64_t)max_len * D;
+  const unsigned short* kp = Kc + base + dc * EPL;
+  const unsigned short* vp = Vc + base + dc * EPL;
+
+  float q[NG][EPL], m[NG], l[NG], o[NG][EPL];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const u32x4 q_raw = *(const u32x4*)(Q + (int64_t)b * ldq + (kvh * NG + g) * D + dc * EPL);
+#pragma unroll
+    for (int t = 0; t < NW; ++t) {
+      q[g][2 * t] = __uint_as_float(q_raw[t] << 16) * scale_log2e;
+      q[g][2 * t + 1] = __uint_as_float(q_raw[t] & 0xffff0000u) * scale_log2e;
+    }
+    m[g] = NEG_BIG;
+    l[g] = 0.f;
+#pragma unroll
+    for (int t = 0; t < EPL; ++t) o[g][t] = 0.f;
+  }
+
+  constexpr int G = 4;                 // keys folded together, as in attn_decode_kernel
+  static_assert(UNR % G == 0, "key rounds are consumed in groups of four");
+  for (int j0 = wave * KPW; j0 < len; j0 += 4 * KPW * UNR) {
+    u32x4 kr[UNR], vr[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int key = min(j0 + u * 4 * KPW + sub, len - 1);
+      kr[u] = *(const u32x4*)(kp + (int64_t)key * D);
+      vr[u] = *(const u32x4*)(vp + (int64_t)key * D);
+    }
+#pragma unroll
+    for (int gk = 0; gk < UNR / G; ++gk) {
+      bool ok[G];
+#pragma unroll
+      for (int i = 0; i < G; ++i) ok[i] = j0 + (gk * G + i) * 4 * KPW + sub < len;
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        float s[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+          const u32x4 kw = kr[gk * G + i];
+          float d = 0.f;
+#pragma unroll
+          for (int t = 0; t < NW; ++t) {
+            d += q[g][2 * t] * __uint_as_float(kw[t] << 16);
+            d += q[g][2 * t + 1] * __uint_as_float(kw[t] & 0xffff0000u);
+          }
+#pragma unroll
+          for (int x = 1; x < LPR; x <<= 1) d += __shfl_xor(d, x, 64);
+          s[i] = ok[i] ? d : NEG_BIG;
+        }
+        const float m_new = fmaxf(fmaxf(m[g], fmaxf(s[0], s[1])), fmaxf(s[2], s[3]));
+        const float alpha = __builtin_amdgcn_exp2f(m[g] - m_new);
+        float pe[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) pe[i] = ok[i] ? __builtin_amdgcn_exp2f(s[i] - m_new) : 0.f;
+        m[g] = m_new;
+        l[g] = l[g] * alpha + ((pe[0] + pe[1]) + (pe[2] + pe[3]));
+#pragma unroll
+        for (int t = 0; t < NW; ++t) {
+          float a0 = o[g][2 * t] * alpha, a1 = o[g][2 * t + 1] * alpha;
+#pragma unroll
+          for (int i = 0; i < G; ++i) {
+            const unsigned vw = vr[gk * G + i][t];
+            a0 = fmaf(pe[i], __uint_as_float(vw << 16), a0);
+            a1 = fmaf(pe[i], __uint_as_float(vw & 0xffff0000u), a1);
+          }
+          o[g][2 * t] = a0;
+          o[g][2 * t + 1] = a1;
+        }
+      }
+    }
+  }
+  const int stream = wave * KPW + sub;
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {       // one head at a time through the one merge buffer
+    if (g) __syncthreads();            // the previous head's readers are done
+#pragma unroll
+    for (int t = 0; t < EPL; ++t) sm[stream][dc * EPL + t] = o[g][t];
+    if (dc == 0) {
+      sm[stream][D] = m[g];
+      sm[stream][D + 1] = l[g];
+    }
+    __syncthreads();
+    if (threadIdx.x < D) {
+      const int d = threadIdx.x;
+      float M = NEG_BIG;
+#pragma unroll
+      for (int s = 0; s < NSTREAM; ++s) M = fmaxf(M, sm[s][D]);
+      float L = 0.f, acc = 0.f;
+#pragma unroll
+      for (int s = 0; s < NSTREAM; ++s) {
+        const float w = __builtin_amdgcn_exp2f(sm[s][D] - M);
+        L += sm[s][D + 1] * w;
+        acc += sm[s][d] * w;
+      }
+      O[(int64_t)b * ldo + (kvh * NG + g) * D + d] = f32_to_bf16_bits(L > 0.f ? acc / L : 0.f);
+    }
+  }
+}
+
 }  // namespace
 
 // epl: 8 = the production bf16 kernel; 16 = the fp8 kernel (Ks != NULL) or its bf16 reference instantiation
@@ -321,6 +439,42 @@ extern "C" int icl_attn_decode_fp8(const void* Q, int64_t ldq, const void* kq, c
   ICL_CHECK_ARG(((uintptr_t)kscale & 3) == 0 && ((uintptr_t)vscale & 3) == 0, "icl_attn_decode_fp8: misaligned operands");
   return launch_attn_decode(Q, ldq, kq, vq, kscale, vscale, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, nullptr, 16,
                             stream, "icl_attn_decode_fp8");
+}
+
+extern "C" int icl_attn_decode_gqa_bf16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O, int64_t ldo,
+                                        const int32_t* lens, int32_t n_seqs, int32_t n_heads, int32_t n_kv_heads,
+                                        int32_t head_dim, int32_t max_len, float scale, void* stream) {
+  ICL_DECODE_CHECKS("icl_attn_decode_gqa_bf16");
+  ICL_CHECK_ARG(n_kv_heads > 0 && n_kv_heads <= 65535 && n_heads % n_kv_heads == 0,
+                "icl_attn_decode_gqa_bf16: n_heads=%d is not a multiple of n_kv_heads=%d", n_heads, n_kv_heads);
+  const int group = n_heads / n_kv_heads;
+  if (group == 1)     // multi-head attention: the multi-head kernel
+    return launch_attn_decode(Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, nullptr, 8,
+                              stream, "icl_attn_decode_gqa_bf16");
+  ICL_CHECK_ARG(group <= 8, "icl_attn_decode_gqa_bf16: %d query heads per K/V head (at most 8)", group);
+  ICL_CHECK_ARG(head_dim == 128, "icl_attn_decode_gqa_bf16: head_dim=%d (grouped-query attention: only 128)", head_dim);
+  ICL_CHECK_ARG(ldo % 8 == 0 && ldq >= (int64_t)n_heads * head_dim && ldo >= (int64_t)n_heads * head_dim,
+                "icl_attn_decode_gqa_bf16: ldq / ldo must hold n_heads * head_dim columns (ldo %% 8 == 0)");
+  const dim3 grid(n_kv_heads, n_seqs);
+  // key rounds in flight per group size: 8 (64 VGPRs of loads) next to two heads of state, 4 from three heads on
+#define ICL_GQA_CASE(GG, UU)                                                                                                   \
+  case GG:                                                                                                                     \
+    hipLaunchKernelGGL((attn_decode_gqa_kernel<GG, UU>), grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short*)Q,   \
+                       ldq, (const unsigned short*)Kc, (const unsigned short*)Vc, (unsigned short*)O, ldo, lens, n_kv_heads,   \
+                       max_len, scale * LOG2E);                                                                                \
+    break
+  switch (group) {
+    ICL_GQA_CASE(2, 8);
+    ICL_GQA_CASE(3, 4);
+    ICL_GQA_CASE(4, 4);
+    ICL_GQA_CASE(5, 4);
+    ICL_GQA_CASE(6, 4);
+    ICL_GQA_CASE(7, 4);
+    ICL_GQA_CASE(8, 4);
+  }
+#undef ICL_GQA_CASE
+  ICL_CHECK_LAUNCH("icl_attn_decode_gqa_bf16");
+  return ICL_OK;
 }
 #undef ICL_DECODE_CHECKS
 

@@ -57,7 +57,7 @@ class QwenModule(PackedTreeModule):
         super().__init__()
         self.cfg = cfg
         self.llm_weight_dtype = check_llm_weight_dtype(llm_weight_dtype)
-        self.llm_kv_dtype = check_llm_kv_dtype(llm_kv_dtype)
+        self.llm_kv_dtype = check_llm_kv_dtype(llm_kv_dtype, cfg.llm)
         self._init_tree(device, synth.qwen_audio_state(cfg, seed=seed, device=torch.device(device), dtype=torch.bfloat16))
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):

@@ -116,11 +116,12 @@ def build_labels(prompt_len: int, target_ids: torch.Tensor, target_mask: torch.T
 LLM_WEIGHT_DTYPES = ("bf16", "fp8")
 
 
-def check_llm_kv_dtype(value: str) -> str:
+def check_llm_kv_dtype(value: str, cfg=None) -> str:
     """``llm_kv_dtype`` of the plugins: "bf16" (default) or "fp8" — the opt-in FP8 KV cache of the LLM decoder
-    (runtime/engines.py KVCache, include/icl_hip.h "FP8 KV cache").  Anything else is a ValueError."""
+    (runtime/engines.py KVCache, include/icl_hip.h "FP8 KV cache").  Anything else is a ValueError, and so is "fp8" for a
+    grouped-query decoder (``cfg``: its LlamaCfg)."""
     from ..runtime.engines import check_kv_dtype
-    return check_kv_dtype(value)
+    return check_kv_dtype(value, cfg)
 
 
 def check_llm_weight_dtype(value: str) -> str:
@@ -215,7 +216,7 @@ class SalmonnModule(PackedTreeModule):
         super().__init__()
         self.cfg = cfg
         self.llm_weight_dtype = check_llm_weight_dtype(llm_weight_dtype)
-        self.llm_kv_dtype = check_llm_kv_dtype(llm_kv_dtype)
+        self.llm_kv_dtype = check_llm_kv_dtype(llm_kv_dtype, cfg.llama)
         self._init_tree(device, synth.salmonn_state(cfg, seed=seed, device=torch.device(device), dtype=torch.bfloat16))
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):

@@ -48,7 +48,7 @@ class AttnArgs(Structure):
         ("cu_seqlens", c_void_p), ("kv_lens", c_void_p), ("rel_bias", c_void_p), ("rel_gate", c_void_p),
         ("ldq", c_int64), ("ldk", c_int64), ("ldv", c_int64), ("ldo", c_int64),
         ("n_seqs", c_int32), ("max_seqlen", c_int32), ("n_heads", c_int32), ("head_dim", c_int32),
-        ("causal", c_int32), ("rel_span", c_int32), ("scale", c_float), ("reserved", c_int32),
+        ("causal", c_int32), ("rel_span", c_int32), ("scale", c_float), ("n_kv_heads", c_int32),
         ("kv_seq_stride", c_int64), ("kv_head_stride", c_int64),
     ]
 
@@ -65,6 +65,8 @@ _SIGNATURES = {
     "icl_attn_fwd_suffix_bf16": (c_int, [POINTER(AttnArgs), c_void_p, c_void_p]),
     "icl_attn_decode_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                      c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "icl_attn_decode_gqa_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                         c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
     "icl_attn_decode_rope_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float,
                                           c_void_p]),
@@ -74,6 +76,8 @@ _SIGNATURES = {
                             c_int32, c_int32, c_void_p]),
     "icl_rope_kv_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "icl_rope_kv_gqa_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "icl_gemm_rope_kv_bf16": (c_int, [POINTER(GemmArgs), c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "icl_pack_decode_weights": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
@@ -346,8 +350,10 @@ def rope_fusable(M: int, n_heads: int, head_dim: int, K: int) -> bool:
 
 
 def attn_fwd(q, k, v, out, cu_seqlens, max_seqlen: int, n_heads: int, head_dim: int, scale: float, *,
-             causal=False, kv_lens=None, rel_bias=None, rel_gate=None, rel_span: int = 0, kv_cache_max_len: int = 0, cu_q=None):
+             causal=False, kv_lens=None, rel_bias=None, rel_gate=None, rel_span: int = 0, kv_cache_max_len: int = 0, cu_q=None,
+             n_kv_heads: int = 0):
     """``kv_cache_max_len`` > 0: k / v are KV-cache tensors [n_seqs, n_heads, max_len, head_dim] (read in place).
+    ``n_kv_heads`` (0 = n_heads): grouped-query attention, head_dim 128 — k / v (packed rows or cache) hold that many heads.
     ``cu_q`` (int32 [n_seqs + 1]): the suffix-query form (icl_attn_fwd_suffix_bf16) — ``q`` / ``out`` hold only the last
     cu_q[s+1] - cu_q[s] queries of each sequence, packed by ``cu_q``; ``cu_seqlens`` / ``max_seqlen`` describe k / v."""
     _require_gpu(q, k, v, out, cu_seqlens, kv_lens, rel_bias, rel_gate, cu_q)
@@ -357,10 +363,10 @@ def attn_fwd(q, k, v, out, cu_seqlens, max_seqlen: int, n_heads: int, head_dim: 
     a.cu_seqlens, a.kv_lens = cu_seqlens.data_ptr(), _ptr(kv_lens)
     a.rel_bias, a.rel_gate = _ptr(rel_bias), _ptr(rel_gate)
     a.ldq, a.ldk, a.ldv, a.ldo = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
-    a.reserved = 0
+    a.n_kv_heads = n_kv_heads
     if kv_cache_max_len > 0:
         a.ldk = a.ldv = head_dim
-        a.kv_seq_stride, a.kv_head_stride = n_heads * kv_cache_max_len * head_dim, kv_cache_max_len * head_dim
+        a.kv_seq_stride, a.kv_head_stride = (n_kv_heads or n_heads) * kv_cache_max_len * head_dim, kv_cache_max_len * head_dim
     else:
         a.kv_seq_stride = a.kv_head_stride = 0
     a.n_seqs = cu_seqlens.numel() - 1
@@ -382,6 +388,18 @@ def attn_decode(q, kcache, vcache, out, lens, n_heads: int, head_dim: int, max_l
                                                out.data_ptr(), out.stride(0), lens.data_ptr(), q.shape[0],
                                                n_heads, head_dim, max_len, scale, _stream()),
            "icl_attn_decode_bf16")
+    return out
+
+
+def attn_decode_gqa(q, kcache, vcache, out, lens, n_heads: int, n_kv_heads: int, head_dim: int, max_len: int, scale: float):
+    """``attn_decode`` for grouped-query attention (icl_attn_decode_gqa_bf16): q / out hold ``n_heads`` heads per row, the caches
+    [n_seqs, n_kv_heads, max_len, head_dim]; every cache row is read once for the query heads that share it."""
+    _require_gpu(q, kcache, vcache, out, lens)
+    assert lens.dtype == torch.int32
+    _check(load_library().icl_attn_decode_gqa_bf16(q.data_ptr(), q.stride(0), kcache.data_ptr(), vcache.data_ptr(),
+                                                   out.data_ptr(), out.stride(0), lens.data_ptr(), q.shape[0],
+                                                   n_heads, n_kv_heads, head_dim, max_len, scale, _stream()),
+           "icl_attn_decode_gqa_bf16")
     return out
 
 
@@ -487,6 +505,17 @@ def rope_kv(qkv, k_off: int, v_off: int, cos, sin, pos, seq_ids, kcache, vcache,
                                            sin.data_ptr(), pos.data_ptr(), _ptr(seq_ids), _ptr(kcache),
                                            _ptr(vcache), M, n_heads, head_dim, max_len, _stream()),
            "icl_rope_kv_bf16")
+
+
+def rope_kv_gqa(qkv, k_off: int, v_off: int, cos, sin, pos, seq_ids, kcache, vcache, n_heads: int, n_kv_heads: int,
+                head_dim: int, max_len: int, M=None):
+    """``rope_kv`` with ``n_heads`` heads in the q block and ``n_kv_heads`` in the k / v blocks and the caches."""
+    _require_gpu(qkv, cos, sin, pos, seq_ids, kcache, vcache)
+    M = qkv.shape[0] if M is None else M
+    _check(load_library().icl_rope_kv_gqa_bf16(qkv.data_ptr(), qkv.stride(0), k_off, v_off, cos.data_ptr(),
+                                               sin.data_ptr(), pos.data_ptr(), _ptr(seq_ids), _ptr(kcache),
+                                               _ptr(vcache), M, n_heads, n_kv_heads, head_dim, max_len, _stream()),
+           "icl_rope_kv_gqa_bf16")
 
 
 def embed_gather_interleave(src_idx, table, speech, out):

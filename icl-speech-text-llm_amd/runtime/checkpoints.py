@@ -63,11 +63,15 @@ def read_config(path: str) -> Optional[dict]:
 # ---- Llama / Vicuna -----------------------------------------------------------------------------------------------
 def llama_cfg_from_hf(cfg_json: dict, base: LlamaCfg) -> LlamaCfg:
     """``config.json`` of a HF Llama folder → LlamaCfg (vocab grows by the ``[PAD]`` token SALMONN adds)."""
-    kv = cfg_json.get("num_key_value_heads", cfg_json["num_attention_heads"])
-    if kv != cfg_json["num_attention_heads"]:
-        raise NotImplementedError("grouped-query attention checkpoints are not supported by the decode kernels yet")
+    heads = cfg_json["num_attention_heads"]
+    kv = cfg_json.get("num_key_value_heads") or heads
+    hd = cfg_json.get("head_dim")
+    if hd is not None and hd * heads != cfg_json["hidden_size"]:
+        raise NotImplementedError(f"head_dim={hd} differs from hidden_size / num_attention_heads = "
+                                  f"{cfg_json['hidden_size']}/{heads}: not supported")
+    # grouped-query attention (kv != heads) is validated by LlamaCfg itself: head_dim 128, at most 8 query heads per K/V head
     return replace(base, hidden=cfg_json["hidden_size"], n_layers=cfg_json["num_hidden_layers"],
-                   n_heads=cfg_json["num_attention_heads"], ffn=cfg_json["intermediate_size"],
+                   n_heads=heads, n_kv_heads=None if kv == heads else kv, ffn=cfg_json["intermediate_size"],
                    vocab=cfg_json["vocab_size"] + 1, rms_eps=cfg_json.get("rms_norm_eps", base.rms_eps),
                    rope_theta=float((cfg_json.get("rope_parameters") or {}).get("rope_theta", cfg_json.get("rope_theta", base.rope_theta))),
                    max_pos=cfg_json.get("max_position_embeddings", base.max_pos),

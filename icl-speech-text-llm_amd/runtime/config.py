@@ -53,6 +53,21 @@ class QFormerCfg:
     second_stride: float = 0.333333
 
 
+MAX_GQA_GROUP = 8   # query heads per K/V head the GQA decode kernel is instantiated for (csrc/attn_decode.hip)
+
+
+def check_gqa(cfg: "LlamaCfg") -> None:
+    """The head counts a decoder may have: ``n_heads`` a multiple of ``kv_heads``, at most MAX_GQA_GROUP query heads per K/V
+    head (ValueError), and grouped-query attention only at head_dim 128 (NotImplementedError: the GQA kernels are built for it)."""
+    kv = cfg.kv_heads
+    if kv <= 0 or cfg.n_heads % kv != 0:
+        raise ValueError(f"n_heads={cfg.n_heads} is not a multiple of n_kv_heads={kv}")
+    if cfg.group > MAX_GQA_GROUP:
+        raise ValueError(f"{cfg.group} query heads per K/V head: the grouped-query kernels take at most {MAX_GQA_GROUP}")
+    if cfg.group > 1 and cfg.head_dim != 128:
+        raise NotImplementedError(f"grouped-query attention is built for head_dim 128, not {cfg.head_dim}")
+
+
 @dataclass(frozen=True)
 class LlamaCfg:
     hidden: int = 4096
@@ -70,10 +85,23 @@ class LlamaCfg:
     lora_alpha: float = 32.0  # config/inference_config.py:36 (class default is 16, custom_salmon.py:45)
     lora_targets: tuple = ("q_proj", "v_proj")   # peft's Llama default (SALMONN); Qwen path: ("q_proj", "k_proj"), custom_qwen.py:75
     qkv_bias: bool = False    # Qwen2 attention has q/k/v biases
+    n_kv_heads: Optional[int] = None   # grouped-query attention: K/V heads (None = n_heads); head_dim 128 only
+
+    def __post_init__(self):
+        check_gqa(self)
 
     @property
     def head_dim(self) -> int:
         return self.hidden // self.n_heads
+
+    @property
+    def kv_heads(self) -> int:
+        return self.n_heads if self.n_kv_heads is None else self.n_kv_heads
+
+    @property
+    def group(self) -> int:
+        """Query heads per K/V head (1 = multi-head attention)."""
+        return self.n_heads // self.kv_heads
 
     @property
     def lora_scale(self) -> float:

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import binding as B
-from .packing import PackedBeats, PackedLlama, PackedQFormer, PackedWhisper
+from .packing import PackedBeats, PackedLlama, PackedQFormer, PackedWhisper, qkv_offsets, qkv_width
 
 BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
@@ -431,7 +431,7 @@ def t256_split(N: int, K: int, n_cu: int) -> int:
 def site_shapes(cfg, k_aug: int) -> Dict[str, Tuple[int, int]]:
     """(N, K) of the four GEMM sites of a decoder layer (``k_aug``: the QKV projection's K with its LoRA columns)."""
     hd, I = cfg.hidden, cfg.ffn
-    return dict(qkv=(3 * hd, k_aug), o=(hd, hd), gu=(2 * I, hd), down=(hd, I))
+    return dict(qkv=(qkv_width(cfg), k_aug), o=(hd, hd), gu=(2 * I, hd), down=(hd, I))
 
 
 def decode_plan(Bn: int, cfg, k_aug: int, n_cu: int, weight_dtype: str = "bf16", decode_packed: bool = True,
@@ -472,7 +472,7 @@ def decode_plan(Bn: int, cfg, k_aug: int, n_cu: int, weight_dtype: str = "bf16",
         plan[name] = GemmLaunch(tile, split, weight, N, K, fused_norm=fuse_norms and name in ("o", "down"))
     plan["lm_head"] = GemmLaunch(lm_head_tile(Bn), 1, "row", cfg.vocab, hd)
     nsplit = max(p.split_k for p in plan.values())
-    return DecodePlan(Bn, plan, nsplit * Bn * max(3 * hd, 2 * I) if nsplit > 1 else 0)
+    return DecodePlan(Bn, plan, nsplit * Bn * max(qkv_width(cfg), 2 * I) if nsplit > 1 else 0)
 
 
 # ================================================================================================
@@ -569,8 +569,9 @@ class LlamaHIP:
         step's GEMM plan (``decode_plan``); None = prefill (the library's tile choice, no split-K)."""
         c, w = self.w.cfg, self.w
         hd, I, D, H = c.hidden, c.ffn, c.head_dim, c.n_heads
+        k_off, v_off = qkv_offsets(c)
         xn = ws.get(tag + "xn", (M, w.k_aug), BF16, zero=True)   # augmentation tail stays zero
-        qkv = ws.get(tag + "qkv", (M, 3 * hd), BF16)
+        qkv = ws.get(tag + "qkv", (M, qkv_width(c)), BF16)
         att = ws.get(tag + "att", (M, hd), BF16)
         act = ws.get(tag + "act", (M, I), BF16)
         wsk = ws.get(tag + "splitk", (split.workspace,), F32) if split is not None and split.workspace else None
@@ -599,16 +600,18 @@ class LlamaHIP:
                 B.lora_down(xn, hd, L.lora_a, r2, 1.0, M=M)      # the LoRA scale is folded into lora_a at pack time
             else:
                 B.gemm(xn, L.lora_a, xn[:, hd:hd + r2], K=hd, tile=4 if split is not None else 2)
-        if split is None and B.rope_fusable(M, H, D, L.wqkv.shape[1]):
+        if split is None and c.group == 1 and B.rope_fusable(M, H, D, L.wqkv.shape[1]):
             # prefill on the 256x256 tile: RoPE + cache append run in the GEMM's staged epilogue (same bits as the two calls)
             B.gemm(xn, L.wqkv, qkv, bias=L.bqkv, tile=3,
-                   rope=(hd, 2 * hd, w.rope_cos, w.rope_sin, pos, seq_ids, kc, vc, H, D, max_len, kv_rows_to_c))
+                   rope=(k_off, v_off, w.rope_cos, w.rope_sin, pos, seq_ids, kc, vc, H, D, max_len, kv_rows_to_c))
         else:
             site_gemm("qkv", xn, qkv, bias=L.bqkv)
             if rope_fn is not None:
                 rope_fn(qkv)
+            elif c.group > 1:           # grouped-query attention: the plain route, RoPE + append in a launch of their own
+                B.rope_kv_gqa(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, seq_ids, kc, vc, H, c.kv_heads, D, max_len, M=M)
             elif not attn_does_rope:    # decode: RoPE + cache append run inside the attention launch (icl_attn_decode_rope_bf16)
-                B.rope_kv(qkv, hd, 2 * hd, w.rope_cos, w.rope_sin, pos, seq_ids, kc, vc, H, D, max_len, M=M)
+                B.rope_kv(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, seq_ids, kc, vc, H, D, max_len, M=M)
         attn_fn(qkv, att)
         if launch_of("o").fused_norm:   # decode: h += att Wo^T and the post-attention RMSNorm in one call (one kernel when the GEMM is split-K)
             site_gemm("o", att, h, norm=(L.rms2, xn), residual=h)
@@ -647,6 +650,8 @@ class LlamaHIP:
         cu = _i32(cu_h, dev)
         maxS = max(seq_lens)
         H, D, hd = c.n_heads, c.head_dim, c.hidden
+        k_off, v_off = qkv_offsets(c)
+        gqa = c.group > 1      # grouped-query attention: no fused RoPE epilogue, so k / v stay packed next to q and no trimming
 
         # With a cache and the fused QKV epilogue, k / v are written ONCE — into the cache — and the attention reads them
         # there ([seq][head][pos][D]: 256-B rows at a 256-B stride instead of a 3*hidden stride); the k / v columns of the QKV
@@ -654,13 +659,14 @@ class LlamaHIP:
         # FP8 KV cache: prefill attends to its own unrounded k / v, so the layer runs as without a cache (k / v rows into the QKV
         # buffer) and one icl_kv_append_fp8 pass rounds them into the cache before the attention.
         fp8 = cache is not None and cache.dtype == "fp8"
-        kv_from_cache = cache is not None and not fp8 and B.rope_fusable(M, H, D, self.w.k_aug)
+        kv_from_cache = cache is not None and not fp8 and not gqa and B.rope_fusable(M, H, D, self.w.k_aug)
         # the trimmed last layer is built on the 256-tile's fused RoPE epilogue (head_dim 128) and a bf16 cache; other models
         # and the FP8 KV mode (whose prefill attends to unrounded packed k / v) keep the full-height layer and gather after it
-        trim = last_rows_only and self.prefill_last_rows and not fp8 and B.rope_epilogue_ok(H, D, self.w.k_aug)
+        trim = last_rows_only and self.prefill_last_rows and not fp8 and not gqa and B.rope_epilogue_ok(H, D, self.w.k_aug)
 
         def attn(qkv, att):
-            B.attn_fwd(qkv[:, :hd], qkv[:, hd:2 * hd], qkv[:, 2 * hd:], att, cu, maxS, H, D, D ** -0.5, causal=True)
+            B.attn_fwd(qkv[:, :k_off], qkv[:, k_off:v_off], qkv[:, v_off:], att, cu, maxS, H, D, D ** -0.5, causal=True,
+                       n_kv_heads=c.kv_heads if gqa else 0)
 
         last_idx = _i32([e - 1 for e in cu_h[1:]], dev) if last_rows_only else None
 
@@ -677,7 +683,7 @@ class LlamaHIP:
             fn = attn
             if fp8:
                 def fn(qkv, att, i=i):
-                    B.kv_append_fp8(qkv, hd, 2 * hd, pos, sid, cache.k[i], cache.v[i], cache.ks[i], cache.vs[i], H, D, cache.max_len,
+                    B.kv_append_fp8(qkv, k_off, v_off, pos, sid, cache.k[i], cache.v[i], cache.ks[i], cache.vs[i], H, D, cache.max_len,
                                     M=M)
                     attn(qkv, att)
                 self._layer(ws, L, h, M, "pf_", fn, pos, sid, None, None, 0)
@@ -709,7 +715,7 @@ class LlamaHIP:
             B.gemm(xn, L.lora_a, xn[:, hd:hd + r2], K=hd, tile=2)
         rope = (w.rope_cos, w.rope_sin)
         # k | v rows of wqkv, all M rows, into the cache only: C is never written (kv_rows_to_c = 0)
-        qkv = ws.get("pf_qkv", (M, 3 * hd), BF16)
+        qkv = ws.get("pf_qkv", (M, qkv_width(c)), BF16)
         B.gemm(xn, L.wqkv[hd:], qkv, bias=L.bqkv[hd:] if L.bqkv is not None else None, tile=3,
                rope=(0, hd, *rope, pos, sid, kc, vc, H, D, max_len, False))
         hg = last_rows(h)
@@ -748,6 +754,7 @@ class LlamaHIP:
         Bn = next_ids.numel()
         h = self.embed(ws, next_ids, None, name="dc_h")
         H, D = c.n_heads, c.head_dim
+        k_off, v_off = qkv_offsets(c)
         split = self.decode_plan(Bn)
         if any(p.weight == "packed" for p in split.sites.values()):
             self.ensure_decode_packed()
@@ -765,26 +772,30 @@ class LlamaHIP:
             # Same-box A/B (tools/ab_decode_rope.sh, profiles/r04_decode_rope_ab.txt): at 256 rows decode 143.2 -> 142.5 ms; at ONE
             # sequence 58.4 -> 59.6 ms per utterance — the rotation's dependent loads (pos -> cos / sin, q, k) sit in front of a
             # latency-bound attention and cost more than the 5-us launch they replace — so small batches keep the two launches.
-            fuse_rope = self.fuse_decode_rope and Bn > 8
+            # Grouped-query attention: two launches at every batch size, RoPE + append (_layer) and the GQA decode attention.
+            fuse_rope = self.fuse_decode_rope and Bn > 8 and c.group == 1
             rope_fn = None
-            if fp8 and fuse_rope:       # FP8 KV cache: the same two forms, rounding the appended row to x' (icl_hip.h)
+            if c.group > 1:
+                def attn(qkv, att, kc=kc, vc=vc):
+                    B.attn_decode_gqa(qkv[:, :k_off], kc, vc, att, lens, H, c.kv_heads, D, cache.max_len, D ** -0.5)
+            elif fp8 and fuse_rope:       # FP8 KV cache: the same two forms, rounding the appended row to x' (icl_hip.h)
                 def attn(qkv, att, kc=kc, vc=vc, ks=ks, vs=vs):
-                    B.attn_decode_rope_fp8(qkv, c.hidden, 2 * c.hidden, self.w.rope_cos, self.w.rope_sin, pos, sid, kc, vc, ks, vs,
+                    B.attn_decode_rope_fp8(qkv, k_off, v_off, self.w.rope_cos, self.w.rope_sin, pos, sid, kc, vc, ks, vs,
                                            att, lens, H, D, cache.max_len, D ** -0.5)
             elif fp8:
                 def rope_fn(qkv, ks=ks, vs=vs, kc=kc, vc=vc):
-                    B.rope_kv_fp8(qkv, c.hidden, 2 * c.hidden, self.w.rope_cos, self.w.rope_sin, pos, sid, kc, vc, ks, vs, H, D,
+                    B.rope_kv_fp8(qkv, k_off, v_off, self.w.rope_cos, self.w.rope_sin, pos, sid, kc, vc, ks, vs, H, D,
                                   cache.max_len, M=Bn)
 
                 def attn(qkv, att, kc=kc, vc=vc, ks=ks, vs=vs):
-                    B.attn_decode_fp8(qkv[:, :c.hidden], kc, vc, ks, vs, att, lens, H, D, cache.max_len, D ** -0.5)
+                    B.attn_decode_fp8(qkv[:, :k_off], kc, vc, ks, vs, att, lens, H, D, cache.max_len, D ** -0.5)
             elif fuse_rope:
                 def attn(qkv, att, kc=kc, vc=vc):
-                    B.attn_decode_rope(qkv, c.hidden, 2 * c.hidden, self.w.rope_cos, self.w.rope_sin, pos, sid, kc, vc, att, lens,
+                    B.attn_decode_rope(qkv, k_off, v_off, self.w.rope_cos, self.w.rope_sin, pos, sid, kc, vc, att, lens,
                                        H, D, cache.max_len, D ** -0.5)
             else:
                 def attn(qkv, att, kc=kc, vc=vc):
-                    B.attn_decode(qkv[:, :c.hidden], kc, vc, att, lens, H, D, cache.max_len, D ** -0.5)
+                    B.attn_decode(qkv[:, :k_off], kc, vc, att, lens, H, D, cache.max_len, D ** -0.5)
 
             nxt = (layers[i + 1].rms1, xn_next) if i + 1 < len(layers) else (self.w.norm, xn_final)
             ready = self._layer(ws, L, h, Bn, "dc_", attn, pos, sid, kc, vc, cache.max_len, split=split, xn_ready=ready,
@@ -795,15 +806,20 @@ class LlamaHIP:
 KV_DTYPES = ("bf16", "fp8")
 
 
-def check_kv_dtype(value: str) -> str:
-    """The KV-cache dtype of the LLM decoder: "bf16" (default) or "fp8" (the opt-in FP8 KV cache, include/icl_hip.h)."""
+def check_kv_dtype(value: str, cfg=None) -> str:
+    """The KV-cache dtype of the LLM decoder: "bf16" (default) or "fp8" (the opt-in FP8 KV cache, include/icl_hip.h).
+    ``cfg`` (the decoder's LlamaCfg, when known): the FP8 KV cache has no grouped-query kernels — "fp8" is then a ValueError."""
     if value not in KV_DTYPES:
         raise ValueError(f"llm_kv_dtype must be one of {KV_DTYPES}, not {value!r}")
+    if value == "fp8" and cfg is not None and getattr(cfg, "group", 1) > 1:
+        raise ValueError("llm_kv_dtype='fp8' is not available for a grouped-query decoder "
+                         f"({cfg.n_heads} query heads / {cfg.kv_heads} K/V heads): the FP8 KV kernels are multi-head only")
     return value
 
 
 class KVCache:
-    """K/V cache, per layer [n_seqs][n_heads][max_len][head_dim] (one contiguous stream per (seq, head)): a view of
+    """K/V cache, per layer [n_seqs][kv_heads][max_len][head_dim] (one contiguous stream per (seq, K/V head); kv_heads = n_heads
+    unless the decoder uses grouped-query attention): a view of
     the workspace's single ``kv_k`` / ``kv_v`` allocations, which grow to the largest (n_seqs x max_len) seen.
 
     ``dtype="fp8"`` (the opt-in FP8 KV cache, include/icl_hip.h): ``k`` / ``v`` hold the e4m3fn bytes of every row (uint8, the
@@ -811,8 +827,9 @@ class KVCache:
     so captured decode graphs are retired when they move (Workspace.GRAPH_VISIBLE)."""
 
     def __init__(self, cfg, n_seqs: int, max_len: int, ws: Workspace, dtype: str = "bf16"):
-        self.n_seqs, self.max_len, self.dtype = n_seqs, max_len, check_kv_dtype(dtype)
-        shape = (cfg.n_layers, n_seqs, cfg.n_heads, max_len, cfg.head_dim)
+        self.n_seqs, self.max_len, self.dtype = n_seqs, max_len, check_kv_dtype(dtype, cfg)
+        kv_heads = getattr(cfg, "kv_heads", cfg.n_heads)       # (a cfg-like object without grouped-query attention: n_heads)
+        shape = (cfg.n_layers, n_seqs, kv_heads, max_len, cfg.head_dim)
         if dtype == "fp8":
             self.k = ws.get("kv_k8", shape, torch.uint8)
             self.v = ws.get("kv_v8", shape, torch.uint8)

@@ -5,7 +5,8 @@ Takes ``state_dict`` tensors under the reference stack's key names (what
 way the kernels want them resident in HBM:
 
 * every GEMM weight as bf16 ``[N, K]`` (nn.Linear layout, K contiguous, 16-byte aligned rows);
-* q/k/v fused into one ``[3h, K]`` weight (one GEMM, one pass over the activations);
+* q/k/v fused into one ``[3h, K]`` weight (one GEMM, one pass over the activations); a grouped-query decoder's is
+  ``[(H + 2 Hkv) D, K]``: q rows, then the Hkv K heads, then the Hkv V heads (``qkv_offsets``);
 * Llama gate/up fused and row-interleaved in blocks of 16 for the in-register SwiGLU epilogue;
 * un-merged LoRA kept exact as a K-augmentation: ``W_aug = [W | B_q 0 / 0 0 / 0 B_v | 0]`` against
   ``x_aug = [x | s*A_q x | s*A_v x | 0]`` (K grows by 64) — same arithmetic as peft's
@@ -21,7 +22,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from .config import BeatsCfg, LlamaCfg, QFormerCfg, WhisperCfg
+from .config import BeatsCfg, LlamaCfg, QFormerCfg, WhisperCfg, check_gqa
 
 SD = Dict[str, torch.Tensor]
 LORA_PAD = 64  # K-augmentation columns (multiple of the GEMM's BK)
@@ -256,8 +257,8 @@ def pack_qformer(sd: SD, cfg: QFormerCfg, device, consume: bool = False) -> Pack
 @dataclass
 class LlamaLayer:
     rms1: torch.Tensor
-    bqkv: Optional[torch.Tensor]  # f32 [3h] (Qwen2) or None
-    wqkv: torch.Tensor           # [3h, K_aug]
+    bqkv: Optional[torch.Tensor]  # f32 [(H + 2 Hkv) D] (Qwen2) or None; = 3h for multi-head attention
+    wqkv: torch.Tensor           # [(H + 2 Hkv) D, K_aug]: q rows at 0, k at H D, v at (H + Hkv) D
     lora_a: Optional[torch.Tensor]  # [2r, h], pre-multiplied by alpha/r
     wo: torch.Tensor
     rms2: torch.Tensor
@@ -284,26 +285,47 @@ def llama_k_aug(cfg: LlamaCfg) -> int:
     return cfg.hidden + (LORA_PAD if cfg.lora_rank else 0)
 
 
+def qkv_offsets(cfg: LlamaCfg):
+    """(k_off, v_off): first column of the k and of the v block in a row of the fused QKV projection's output — q takes
+    n_heads * head_dim columns, k and v kv_heads * head_dim each (multi-head attention: hidden and 2 * hidden)."""
+    q, kv = cfg.n_heads * cfg.head_dim, cfg.kv_heads * cfg.head_dim
+    return q, q + kv
+
+
+def qkv_width(cfg: LlamaCfg) -> int:
+    """Columns of the fused QKV projection's output = rows of wqkv: (n_heads + 2 * kv_heads) * head_dim."""
+    return qkv_offsets(cfg)[1] + cfg.kv_heads * cfg.head_dim
+
+
+def qkv_row_blocks(cfg: LlamaCfg):
+    """((first row, rows) of q, of k, of v) in wqkv / bqkv."""
+    k_off, v_off = qkv_offsets(cfg)
+    return (0, k_off), (k_off, v_off - k_off), (v_off, v_off - k_off)
+
+
 def pack_llama(sd: SD, cfg: LlamaCfg, device, prefix: str = "llama_model.", consume: bool = False) -> PackedLlama:
     """HF causal-LM names under `prefix`: model.embed_tokens, model.layers.{i}.*, model.norm, lm_head (Llama and Qwen2 alike)."""
     h, I, r = cfg.hidden, cfg.ffn, cfg.lora_rank
     assert h % 64 == 0 and I % 64 == 0 and cfg.head_dim in (64, 128)
+    check_gqa(cfg)
     p = prefix + "model."
     k_aug = llama_k_aug(cfg)
     assert len(cfg.lora_targets) * r <= LORA_PAD and all(t in ("q_proj", "k_proj", "v_proj") for t in cfg.lora_targets)
+    rows = dict(zip(("q_proj", "k_proj", "v_proj"), qkv_row_blocks(cfg)))    # (first row, rows) of each projection in wqkv
+    n_qkv = qkv_width(cfg)
     layers = []
     for i in range(cfg.n_layers):
         lp = f"{p}layers.{i}."
-        wqkv = torch.zeros(3 * h, k_aug, dtype=torch.bfloat16, device=device)
-        for j, n in enumerate(("q_proj", "k_proj", "v_proj")):
-            wqkv[j * h:(j + 1) * h, :h] = _take(sd, lp + f"self_attn.{n}.weight", consume).to(device=device, dtype=torch.bfloat16)
+        wqkv = torch.zeros(n_qkv, k_aug, dtype=torch.bfloat16, device=device)
+        for n, (r0, nr) in rows.items():
+            wqkv[r0:r0 + nr, :h] = _take(sd, lp + f"self_attn.{n}.weight", consume).to(device=device, dtype=torch.bfloat16)
         lora_a = None
         if r:   # K-augmentation: target t (one of q/k/v) gets its B in column block [h + ti*r, h + (ti+1)*r) of its own rows
             a_rows = []
             for ti, tgt in enumerate(cfg.lora_targets):
-                j = ("q_proj", "k_proj", "v_proj").index(tgt)
+                r0, nr = rows[tgt]
                 a_rows.append(_take(sd, lp + f"self_attn.{tgt}.lora_A.weight", consume))
-                wqkv[j * h:(j + 1) * h, h + ti * r:h + (ti + 1) * r] = \
+                wqkv[r0:r0 + nr, h + ti * r:h + (ti + 1) * r] = \
                     _take(sd, lp + f"self_attn.{tgt}.lora_B.weight", consume).to(device=device, dtype=torch.bfloat16)
             # the LoRA scale (alpha/r) is folded into A here so the down-projection can run as a plain GEMM
             lora_a = _bf(torch.cat(a_rows, 0).float() * cfg.lora_scale, device)

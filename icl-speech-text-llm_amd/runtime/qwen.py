@@ -46,7 +46,7 @@ class QwenAudioRuntime(CausalLMRuntimeMixin):
         B.load_library()
         self.cfg, self.lm_cfg = cfg, cfg.llm
         self.device = torch.device(device)
-        self.kv_dtype = check_kv_dtype(llm_kv_dtype)
+        self.kv_dtype = check_kv_dtype(llm_kv_dtype, cfg.llm)       # "fp8" + grouped-query attention: ValueError, before any launch
         sd = state_dict if consume else normalize_qwen_keys(state_dict)
         self.ws = Workspace(self.device)
         self.logmel = LogMel(cfg.audio.n_mels, self.device)

@@ -446,7 +446,7 @@ class CausalLMRuntimeMixin:
             pos_all.copy_(torch.tensor([[s + t for s in lens_rep] for t in range(steps)], dtype=I32), non_blocking=True)
             len_all.copy_(torch.tensor([[s + t + 1 for s in lens_rep] for t in range(steps)], dtype=I32), non_blocking=True)
             sid.copy_(torch.arange(BK, dtype=I32), non_blocking=True)
-            tmp_k = ws.get("beam_tmp_k", (c.n_layers, BK, c.n_heads, steps, c.head_dim), cache.k.dtype)
+            tmp_k = ws.get("beam_tmp_k", (c.n_layers, BK, c.kv_heads, steps, c.head_dim), cache.k.dtype)
             tmp_v = ws.get("beam_tmp_v", tuple(tmp_k.shape), cache.k.dtype)
             tmp_ks = tmp_vs = None
             if cache.dtype == "fp8":                           # FP8 KV cache: the row scales travel with the row bytes
@@ -477,7 +477,7 @@ class SalmonnRuntime(CausalLMRuntimeMixin):
         self.cfg = cfg
         self.lm_cfg = cfg.llama
         self.device = torch.device(device)
-        self.kv_dtype = check_kv_dtype(llm_kv_dtype)
+        self.kv_dtype = check_kv_dtype(llm_kv_dtype, cfg.llama)     # "fp8" + grouped-query attention: ValueError, before any launch
         sd = normalize_keys(state_dict) if not consume else state_dict
         self.ws = Workspace(self.device)
         self.whisper = self.beats = self.qformer = self.llama = None

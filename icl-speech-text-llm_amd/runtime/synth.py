@@ -138,17 +138,19 @@ def llama_state(cfg: LlamaCfg, g: _Gen, prefix: str = "llama_model.", margin: bo
     p = prefix + "model."
     sd[p + "embed_tokens.weight"] = g.normal(cfg.vocab, h, std=1.0 if margin else 0.02)
     res_std = 0.001 if margin else 0.02
+    rows = {n: cfg.kv_heads * cfg.head_dim if n in ("k_proj", "v_proj") else h for n in ("q_proj", "k_proj", "v_proj", "o_proj")}
     for i in range(cfg.n_layers):
         lp = f"{p}layers.{i}."
         for n in ("q_proj", "k_proj", "v_proj", "o_proj"):
-            sd[lp + f"self_attn.{n}.weight"] = g.normal(h, h, std=res_std if n == "o_proj" else 0.02)
+            sd[lp + f"self_attn.{n}.weight"] = g.normal(rows[n], h, std=res_std if n == "o_proj" else 0.02)
         if cfg.qkv_bias:
             for n in ("q_proj", "k_proj", "v_proj"):
-                sd[lp + f"self_attn.{n}.bias"] = g.bias(h) if g.jitter else 0.02 * torch.randn(h, generator=g.g, device=g.device)
+                sd[lp + f"self_attn.{n}.bias"] = (g.bias(rows[n]) if g.jitter else
+                                                  0.02 * torch.randn(rows[n], generator=g.g, device=g.device))
         if cfg.lora_rank:
             for n in cfg.lora_targets:
                 sd[lp + f"self_attn.{n}.lora_A.weight"] = g.normal(cfg.lora_rank, h)
-                sd[lp + f"self_attn.{n}.lora_B.weight"] = g.normal(h, cfg.lora_rank, std=0.01)
+                sd[lp + f"self_attn.{n}.lora_B.weight"] = g.normal(rows[n], cfg.lora_rank, std=0.01)
         sd[lp + "mlp.gate_proj.weight"] = g.normal(cfg.ffn, h)
         sd[lp + "mlp.up_proj.weight"] = g.normal(cfg.ffn, h)
         sd[lp + "mlp.down_proj.weight"] = g.normal(h, cfg.ffn, std=res_std)

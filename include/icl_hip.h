@@ -175,7 +175,12 @@ typedef struct icl_attn_args {
   int32_t n_seqs, max_seqlen, n_heads, head_dim;
   int32_t causal, rel_span;
   float scale;
-  int32_t reserved;                            /* 0 */
+  int32_t n_kv_heads;                          /* grouped-query attention: K/V heads (0 = n_heads).  Must divide n_heads and
+                                                  may differ from it only at head_dim 128; query head h reads K/V head
+                                                  h / (n_heads / n_kv_heads): column block (h / G)*head_dim of packed K/V
+                                                  rows, or (h / G)*kv_head_stride in a cache whose kv_seq_stride describes
+                                                  n_kv_heads heads.  Same kernel and arithmetic as the launch with
+                                                  n_kv_heads = 0 on K/V expanded per group: bit-identical output            */
   int64_t kv_seq_stride, kv_head_stride;       /* both 0: K/V rows are packed like Q (row cu_seqlens[s] + j, head h at
                                                   column h*head_dim, row strides ldk / ldv).  Both > 0: K/V are read from a
                                                   cache, key j of (sequence s, head h) at K + s*kv_seq_stride +
@@ -204,6 +209,19 @@ int icl_attn_fwd_suffix_bf16(const icl_attn_args* args, const int32_t* cu_q, voi
 int icl_attn_decode_bf16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O,
                          int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads,
                          int32_t head_dim, int32_t max_len, float scale, void* stream);
+
+/* ---- K11: grouped-query decode attention ---------------------------------------------------------
+ * icl_attn_decode_bf16 for a decoder whose G = n_heads / n_kv_heads query heads share one K/V head (2 <= G <= 8, head_dim
+ * 128; G = 1 runs icl_attn_decode_bf16).  Q / O hold n_heads heads per row, the cache n_kv_heads:
+ * [n_seqs][n_kv_heads][max_len][head_dim] bf16; query head h attends over K/V head h / G.  One workgroup per (sequence,
+ * K/V head) loads every cache row ONCE and uses it for its G query heads, so a launch reads 1/G of the bytes
+ * icl_attn_decode_bf16 reads from the per-group expanded cache.  Every query head folds the keys of icl_attn_decode_bf16's
+ * streams in their order: the output is that call's on the expanded cache up to the compiler's FMA contraction.
+ * Replaces repeat_kv + the cached-key SDPA of transformers' LlamaAttention in a decode step.
+ */
+int icl_attn_decode_gqa_bf16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O, int64_t ldo,
+                             const int32_t* lens, int32_t n_seqs, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim,
+                             int32_t max_len, float scale, void* stream);
 
 /* ---- K11: the decode step's RoPE + KV-cache append + attention as ONE launch --------------------
  * icl_rope_kv_bf16 (M = n_seqs rows, one new position each) followed by icl_attn_decode_bf16, fused: qkv bf16 [n_seqs][ld] holds
@@ -252,6 +270,14 @@ int icl_rope_kv_bf16(void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const 
                      const float* sin, const int32_t* pos, const int32_t* seq_ids, void* kcache,
                      void* vcache, int32_t M, int32_t n_heads, int32_t head_dim, int32_t max_len,
                      void* stream);
+
+/* icl_rope_kv_bf16 for grouped-query attention: the q block has n_heads heads, the k / v blocks (at k_off / v_off) and the
+ * cache ([n_seqs][n_kv_heads][max_len][head_dim]) n_kv_heads.  The same kernel, rotation and rounding points; with
+ * n_kv_heads == n_heads it is icl_rope_kv_bf16.  The column blocks must be disjoint inside a row. */
+int icl_rope_kv_gqa_bf16(void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* cos,
+                         const float* sin, const int32_t* pos, const int32_t* seq_ids, void* kcache,
+                         void* vcache, int32_t M, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim,
+                         int32_t max_len, void* stream);
 
 /* ---- K10/K11: QKV projection with RoPE + KV-cache append fused into its epilogue -----------
  * icl_gemm_bf16(args) followed by icl_rope_kv_bf16 on its output, as ONE kernel: the 256x256 tile
