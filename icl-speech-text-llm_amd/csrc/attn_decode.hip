@@ -1,4 +1,5 @@
-// attn_decode.hip — single-token decode attention over the KV cache (HBM-bound KV stream).
+// attn_decode.hip — single-token decode attention over the KV cache (HBM-bound KV stream): ONE kernel,
+// attn_decode_kernel<D, UNR, FUSE, F8, EPL, NG>, behind every icl_attn_decode_* entry point.
 // Cache layout [n_seqs][n_heads][max_len][D] bf16: the keys of one (sequence, head) are one
 // contiguous stream, read with 16-B loads straight to VGPRs (no LDS round trip: guide §5 table row
 // "GEMV / M <= 16 decode").  D/8 lanes cover one key row, so a wave-instruction fetches 64/(D/8)
@@ -11,6 +12,7 @@ namespace {
 constexpr float NEG_BIG = -1.0e30f;
 constexpr float LOG2E = 1.4426950408889634f;
 
+// D = head_dim (64 or 128).
 // UNR = key rounds (4 * KPW keys each) whose K and V loads are issued before the first of them is consumed.  A stream's keys and
 // their order do not depend on it: few workgroups (a small decode batch: one block per (sequence, head), nothing else on the CU to
 // hide a 2-3 us round trip per loop iteration) take the deep unroll, a full chip 4.  (The instruction selection, and so FMA
@@ -30,6 +32,12 @@ constexpr float LOG2E = 1.4426950408889634f;
 // a bf16 cache of x'; against the production EPL = 8 kernel only the order of the d-chunk partial sums of each score differs.
 // FUSE rounds the appended key and value to x' in registers (kv_fp8_quant: the row maximum is a shuffle over the row's LPR lanes)
 // and serves the rounded row.
+// NG (icl_attn_decode_gqa_bf16) = query heads per K/V head; 1 = multi-head attention.  One workgroup per (sequence, K/V head): a
+// lane uses the K chunk and V chunk it loaded for all NG heads, so a cache row is read once for NG heads, a decode step streams
+// 1 / NG of the bytes NG = 1 reads from the per-group expanded cache, and the output is NG = 1's on that cache up to the compiler's
+// FMA contraction.  The state (q chunk, m, l, o[8]) is 18 VGPRs per head, so UNR shrinks as NG grows.  The K / V
+// conversions (kv_words) stay inside the per-head loop, next to their uses: the identity for bf16, and hoisted out of it they cost
+// the fp8 instantiations 43-85 VGPRs (196 -> 261 at <128, 8, false, true, 16>: a whole key group's converted rows live at once).
 struct DecodeRope {
   const float* cosT;
   const float* sinT;
@@ -64,7 +72,8 @@ __device__ __forceinline__ typename KvWords<EPL>::T kv_words(typename KvRaw<F8, 
   }
 }
 
-template <int D, int UNR, bool FUSE, bool F8, int EPL>
+// blockIdx.x = h, a head of the CACHE (n_heads of them); its query heads are h * NG + g.
+template <int D, int UNR, bool FUSE, bool F8, int EPL, int NG>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* Q, int64_t ldq, const void* Kc, const void* Vc,
                                                            const float* Ks, const float* Vs, unsigned short* O, int64_t ldo,
                                                            const int* lens, int n_heads, int max_len, float scale_log2e,
@@ -72,12 +81,13 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
   typedef typename KvRaw<F8, EPL>::T Raw;
   typedef typename KvWords<EPL>::T Wd;
   static_assert(!F8 || EPL == 16, "the fp8 cache is read 16 elements per lane");
+  static_assert(NG == 1 || (!FUSE && !F8 && D == 128 && EPL == 8), "grouped-query: the plain bf16 form at head_dim 128 only");
   constexpr int NW = EPL / 2;      // bf16 words per lane
   constexpr int EB = F8 ? 1 : 2;   // bytes per cache element
   constexpr int LPR = D / EPL;     // lanes per key row
   constexpr int KPW = 64 / LPR;    // keys per wave-instruction
   constexpr int NSTREAM = 4 * KPW;
-  __shared__ float sm[NSTREAM][D + 2];  // per stream: o[D], m, l
+  __shared__ float sm[NSTREAM][D + 2];  // per stream of ONE head: o[D], m, l
   const int h = blockIdx.x, b = blockIdx.y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int dc = lane % LPR, sub = lane / LPR;
@@ -88,7 +98,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
   const char* kp = (const char*)Kc + (base + dc * EPL) * EB;
   const char* vp = (const char*)Vc + (base + dc * EPL) * EB;
 
-  Wd q_raw;
+  Wd q_raw[NG];
   Raw k_new = {}, v_new = {};
   float ks_new = 1.f, vs_new = 1.f;
   int pos_new = -1;
@@ -114,7 +124,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
       const u32x4 ko = is_hi ? ohi : olo;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        q_raw[4 * c + t] = qo[t];
+        q_raw[0][4 * c + t] = qo[t];
         k_row[4 * c + t] = ko[t];
       }
     }
@@ -146,17 +156,22 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
       }
     }
   } else {
-    q_raw = *(const Wd*)(Q + (int64_t)b * ldq + h * D + dc * EPL);
-  }
-  float q[EPL];
 #pragma unroll
-  for (int t = 0; t < NW; ++t) {
-    q[2 * t] = __uint_as_float(q_raw[t] << 16) * scale_log2e;
-    q[2 * t + 1] = __uint_as_float(q_raw[t] & 0xffff0000u) * scale_log2e;
+    for (int g = 0; g < NG; ++g) q_raw[g] = *(const Wd*)(Q + (int64_t)b * ldq + (h * NG + g) * D + dc * EPL);
   }
-  float m = NEG_BIG, l = 0.f, o[EPL];
+  float q[NG][EPL], m[NG], l[NG], o[NG][EPL];
 #pragma unroll
-  for (int t = 0; t < EPL; ++t) o[t] = 0.f;
+  for (int g = 0; g < NG; ++g) {
+#pragma unroll
+    for (int t = 0; t < NW; ++t) {
+      q[g][2 * t] = __uint_as_float(q_raw[g][t] << 16) * scale_log2e;
+      q[g][2 * t + 1] = __uint_as_float(q_raw[g][t] & 0xffff0000u) * scale_log2e;
+    }
+    m[g] = NEG_BIG;
+    l[g] = 0.f;
+#pragma unroll
+    for (int t = 0; t < EPL; ++t) o[g][t] = 0.f;
+  }
 
   // A stream folds its keys in GROUPS of G = 4 (the same groups whatever UNR is): the four scores of a group are independent dot
   // products, ONE running-maximum update and ONE rescale serve all four, and their exponentials and the o / l updates are
@@ -186,132 +201,15 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
       }
     }
 #pragma unroll
-    for (int g = 0; g < UNR / G; ++g) {
-      float s[G];
-      bool ok[G];
-#pragma unroll
-      for (int i = 0; i < G; ++i) {
-        const int u = g * G + i;
-        const Wd kw = kv_words<F8, EPL>(kr[u], ksr[u]);
-        float d = 0.f;
-#pragma unroll
-        for (int t = 0; t < NW; ++t) {
-          d += q[2 * t] * __uint_as_float(kw[t] << 16);
-          d += q[2 * t + 1] * __uint_as_float(kw[t] & 0xffff0000u);
-        }
-#pragma unroll
-        for (int x = 1; x < LPR; x <<= 1) d += __shfl_xor(d, x, 64);
-        ok[i] = j0 + u * 4 * KPW + sub < len;
-        s[i] = ok[i] ? d : NEG_BIG;
-      }
-      const float m_new = fmaxf(fmaxf(m, fmaxf(s[0], s[1])), fmaxf(s[2], s[3]));
-      const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-      float pe[G];
-#pragma unroll
-      for (int i = 0; i < G; ++i) pe[i] = ok[i] ? __builtin_amdgcn_exp2f(s[i] - m_new) : 0.f;
-      m = m_new;
-      l = l * alpha + ((pe[0] + pe[1]) + (pe[2] + pe[3]));
-      Wd vw[G];
-#pragma unroll
-      for (int i = 0; i < G; ++i) vw[i] = kv_words<F8, EPL>(vr[g * G + i], vsr[g * G + i]);
-#pragma unroll
-      for (int t = 0; t < NW; ++t) {
-        float a0 = o[2 * t] * alpha, a1 = o[2 * t + 1] * alpha;
-#pragma unroll
-        for (int i = 0; i < G; ++i) {
-          a0 = fmaf(pe[i], __uint_as_float(vw[i][t] << 16), a0);
-          a1 = fmaf(pe[i], __uint_as_float(vw[i][t] & 0xffff0000u), a1);
-        }
-        o[2 * t] = a0;
-        o[2 * t + 1] = a1;
-      }
-    }
-  }
-  const int stream = wave * KPW + sub;
-#pragma unroll
-  for (int t = 0; t < EPL; ++t) sm[stream][dc * EPL + t] = o[t];
-  if (dc == 0) {
-    sm[stream][D] = m;
-    sm[stream][D + 1] = l;
-  }
-  __syncthreads();
-  if (threadIdx.x < D) {
-    const int d = threadIdx.x;
-    float M = NEG_BIG;
-#pragma unroll
-    for (int s = 0; s < NSTREAM; ++s) M = fmaxf(M, sm[s][D]);
-    float L = 0.f, acc = 0.f;
-#pragma unroll
-    for (int s = 0; s < NSTREAM; ++s) {
-      const float w = __builtin_amdgcn_exp2f(sm[s][D] - M);
-      L += sm[s][D + 1] * w;
-      acc += sm[s][d] * w;
-    }
-    // F8: a NaN cache row (a non-finite appended k / v) makes L NaN, and the output of this (sequence, head) NaN; the bf16
-    // kernel's L > 0 test would turn it into zeros.  Identical for every finite input.
-    const bool live = F8 ? !(L <= 0.f) : L > 0.f;
-    O[(int64_t)b * ldo + h * D + d] = f32_to_bf16_bits(live ? acc / L : 0.f);
-  }
-}
-
-// Grouped-query decode (icl_attn_decode_gqa_bf16): NG query heads share one K/V head, head_dim 128.  One workgroup per (sequence,
-// KV head) with attn_decode_kernel<128, ., false, false, 8>'s lane mapping — 16 lanes per 256-B row, a wave-load = 4 consecutive
-// keys, 4 waves, 16 streams — but every lane holds NG query chunks and NG online-softmax states (m, l, o[8]) and uses the 16-B K
-// chunk and V chunk it loaded for all NG heads: a cache row is read once per workgroup, a decode step streams 1 / NG of the bytes
-// the multi-head kernel reads from the expanded cache.  Query head kvh * NG + g's stream folds the keys attn_decode_kernel gives
-// that stream, in its order and its groups of four, with the same expressions: the result is that kernel's on the expanded cache
-// up to the compiler's FMA contraction.  The 16 streams of a head are merged through LDS as there, one head after the other
-// through the one buffer.  UNR (key rounds in flight) shrinks as NG grows: the state is 18 VGPRs per head.
-template <int NG, int UNR>
-__global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const unsigned short* Q, int64_t ldq, const unsigned short* Kc,
-                                                               const unsigned short* Vc, unsigned short* O, int64_t ldo,
-                                                               const int* lens, int n_kv_heads, int max_len, float scale_log2e) {
-  constexpr int D = 128, EPL = 8, NW = EPL / 2, LPR = D / EPL, KPW = 64 / LPR, NSTREAM = 4 * KPW;
-  __shared__ float sm[NSTREAM][D + 2];  // per stream of ONE head: o[D], m, l
-  const int kvh = blockIdx.x, b = blockIdx.y;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int dc = lane % LPR, sub = lane / LPR;
-  const int len = min(lens[b], max_len);
-  const int64_t base = ((int64_t)b * n_kv_heads + kvh) * (int64_t)max_len * D;
-  const unsigned short* kp = Kc + base + dc * EPL;
-  const unsigned short* vp = Vc + base + dc * EPL;
-
-  float q[NG][EPL], m[NG], l[NG], o[NG][EPL];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    const u32x4 q_raw = *(const u32x4*)(Q + (int64_t)b * ldq + (kvh * NG + g) * D + dc * EPL);
-#pragma unroll
-    for (int t = 0; t < NW; ++t) {
-      q[g][2 * t] = __uint_as_float(q_raw[t] << 16) * scale_log2e;
-      q[g][2 * t + 1] = __uint_as_float(q_raw[t] & 0xffff0000u) * scale_log2e;
-    }
-    m[g] = NEG_BIG;
-    l[g] = 0.f;
-#pragma unroll
-    for (int t = 0; t < EPL; ++t) o[g][t] = 0.f;
-  }
-
-  constexpr int G = 4;                 // keys folded together, as in attn_decode_kernel
-  static_assert(UNR % G == 0, "key rounds are consumed in groups of four");
-  for (int j0 = wave * KPW; j0 < len; j0 += 4 * KPW * UNR) {
-    u32x4 kr[UNR], vr[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const int key = min(j0 + u * 4 * KPW + sub, len - 1);
-      kr[u] = *(const u32x4*)(kp + (int64_t)key * D);
-      vr[u] = *(const u32x4*)(vp + (int64_t)key * D);
-    }
-#pragma unroll
     for (int gk = 0; gk < UNR / G; ++gk) {
-      bool ok[G];
-#pragma unroll
-      for (int i = 0; i < G; ++i) ok[i] = j0 + (gk * G + i) * 4 * KPW + sub < len;
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
         float s[G];
+        bool ok[G];
 #pragma unroll
         for (int i = 0; i < G; ++i) {
-          const u32x4 kw = kr[gk * G + i];
+          const int u = gk * G + i;
+          const Wd kw = kv_words<F8, EPL>(kr[u], ksr[u]);
           float d = 0.f;
 #pragma unroll
           for (int t = 0; t < NW; ++t) {
@@ -320,6 +218,7 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const unsigned sho
           }
 #pragma unroll
           for (int x = 1; x < LPR; x <<= 1) d += __shfl_xor(d, x, 64);
+          ok[i] = j0 + u * 4 * KPW + sub < len;
           s[i] = ok[i] ? d : NEG_BIG;
         }
         const float m_new = fmaxf(fmaxf(m[g], fmaxf(s[0], s[1])), fmaxf(s[2], s[3]));
@@ -329,14 +228,16 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const unsigned sho
         for (int i = 0; i < G; ++i) pe[i] = ok[i] ? __builtin_amdgcn_exp2f(s[i] - m_new) : 0.f;
         m[g] = m_new;
         l[g] = l[g] * alpha + ((pe[0] + pe[1]) + (pe[2] + pe[3]));
+        Wd vw[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) vw[i] = kv_words<F8, EPL>(vr[gk * G + i], vsr[gk * G + i]);
 #pragma unroll
         for (int t = 0; t < NW; ++t) {
           float a0 = o[g][2 * t] * alpha, a1 = o[g][2 * t + 1] * alpha;
 #pragma unroll
           for (int i = 0; i < G; ++i) {
-            const unsigned vw = vr[gk * G + i][t];
-            a0 = fmaf(pe[i], __uint_as_float(vw << 16), a0);
-            a1 = fmaf(pe[i], __uint_as_float(vw & 0xffff0000u), a1);
+            a0 = fmaf(pe[i], __uint_as_float(vw[i][t] << 16), a0);
+            a1 = fmaf(pe[i], __uint_as_float(vw[i][t] & 0xffff0000u), a1);
           }
           o[g][2 * t] = a0;
           o[g][2 * t + 1] = a1;
@@ -367,57 +268,87 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const unsigned sho
         L += sm[s][D + 1] * w;
         acc += sm[s][d] * w;
       }
-      O[(int64_t)b * ldo + (kvh * NG + g) * D + d] = f32_to_bf16_bits(L > 0.f ? acc / L : 0.f);
+      // F8: a NaN cache row (a non-finite appended k / v) makes L NaN, and the output of this (sequence, head) NaN; the bf16
+      // kernel's L > 0 test would turn it into zeros.  Identical for every finite input.
+      const bool live = F8 ? !(L <= 0.f) : L > 0.f;
+      O[(int64_t)b * ldo + (h * NG + g) * D + d] = f32_to_bf16_bits(live ? acc / L : 0.f);
     }
   }
 }
 
 }  // namespace
 
+// n_heads = heads of the cache, each serving `group` query heads (1: multi-head attention).
 // epl: 8 = the production bf16 kernel; 16 = the fp8 kernel (Ks != NULL) or its bf16 reference instantiation
 static int launch_attn_decode(const void* Q, int64_t ldq, const void* Kc, const void* Vc, const float* Ks, const float* Vs, void* O,
-                              int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads, int32_t head_dim, int32_t max_len,
-                              float scale, const DecodeRope* rope, int epl, void* stream, const char* who) {
+                              int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads, int group, int32_t head_dim,
+                              int32_t max_len, float scale, const DecodeRope* rope, int epl, void* stream, const char* who) {
   dim3 grid(n_heads, n_seqs);
   const bool few = (int64_t)n_seqs * n_heads <= 1024;      // at most four workgroups per CU: latency-bound, not bandwidth-bound
   const DecodeRope rp = rope ? *rope : DecodeRope{};
   const bool f8 = Ks != nullptr;
-#define ICL_DECODE_CASE(DD, UU, FF, F8_, EE)                                                                                   \
-  hipLaunchKernelGGL((attn_decode_kernel<DD, UU, FF, F8_, EE>), grid, dim3(256), 0, (hipStream_t)stream,                       \
+#define ICL_DECODE_CASE(DD, UU, FF, F8_, EE, GG)                                                                               \
+  hipLaunchKernelGGL((attn_decode_kernel<DD, UU, FF, F8_, EE, GG>), grid, dim3(256), 0, (hipStream_t)stream,                   \
                      (const unsigned short*)Q, ldq, Kc, Vc, Ks, Vs, (unsigned short*)O, ldo, lens, n_heads, max_len,          \
                      scale * LOG2E, rp)
   // few: 16 key rounds at 8 elements per lane, 8 at 16 (the same keys in flight per loop iteration); a full chip: 4
 #define ICL_DECODE_D(FF, F8_, EE)                                                                                              \
   do {                                                                                                                         \
     constexpr int UFEW = EE == 8 ? 16 : 8;                                                                                     \
-    if (head_dim == 64) { if (few) ICL_DECODE_CASE(64, UFEW, FF, F8_, EE); else ICL_DECODE_CASE(64, 4, FF, F8_, EE); }         \
-    else                { if (few) ICL_DECODE_CASE(128, UFEW, FF, F8_, EE); else ICL_DECODE_CASE(128, 4, FF, F8_, EE); }       \
+    if (head_dim == 64) { if (few) ICL_DECODE_CASE(64, UFEW, FF, F8_, EE, 1); else ICL_DECODE_CASE(64, 4, FF, F8_, EE, 1); }   \
+    else                { if (few) ICL_DECODE_CASE(128, UFEW, FF, F8_, EE, 1); else ICL_DECODE_CASE(128, 4, FF, F8_, EE, 1); } \
   } while (0)
-  if (f8) {
+  // key rounds in flight per group size: 8 (64 VGPRs of loads) next to two heads of state, 4 from three heads on (DESIGN.md §4)
+#define ICL_GQA_CASE(GG, UU) case GG: ICL_DECODE_CASE(128, UU, false, false, 8, GG); break
+  if (group > 1) {       // the caller has checked: plain bf16, head_dim 128, group <= 8
+    switch (group) {
+      ICL_GQA_CASE(2, 8);
+      ICL_GQA_CASE(3, 4);
+      ICL_GQA_CASE(4, 4);
+      ICL_GQA_CASE(5, 4);
+      ICL_GQA_CASE(6, 4);
+      ICL_GQA_CASE(7, 4);
+      ICL_GQA_CASE(8, 4);
+    }
+  } else if (f8) {
     if (rope) ICL_DECODE_D(true, true, 16); else ICL_DECODE_D(false, true, 16);
   } else if (epl == 16) {
     ICL_DECODE_D(false, false, 16);
   } else {
     if (rope) ICL_DECODE_D(true, false, 8); else ICL_DECODE_D(false, false, 8);
   }
+#undef ICL_GQA_CASE
 #undef ICL_DECODE_D
 #undef ICL_DECODE_CASE
   ICL_CHECK_LAUNCH(who);
   return ICL_OK;
 }
 
+#define ICL_DECODE_SIZE_CHECKS(who)                                                                                            \
+  ICL_CHECK_ARG(head_dim == 64 || head_dim == 128, who ": head_dim=%d (only 64 and 128)", head_dim);                           \
+  ICL_CHECK_ARG(n_seqs > 0 && n_seqs <= 65535 && n_heads > 0 && max_len > 0, who ": bad sizes")
 #define ICL_DECODE_CHECKS(who)                                                                                                 \
   ICL_CHECK_ARG(Q && Kc && Vc && O && lens, who ": NULL pointer");                                                           \
-  ICL_CHECK_ARG(head_dim == 64 || head_dim == 128, who ": head_dim=%d (only 64 and 128)", head_dim);                           \
-  ICL_CHECK_ARG(n_seqs > 0 && n_seqs <= 65535 && n_heads > 0 && max_len > 0, who ": bad sizes");                               \
+  ICL_DECODE_SIZE_CHECKS(who);                                                                                                 \
   ICL_CHECK_ARG(ldq % 8 == 0 && ((uintptr_t)Q & 15) == 0 && ((uintptr_t)Kc & 15) == 0 && ((uintptr_t)Vc & 15) == 0,            \
                 who ": misaligned operands")
+#define ICL_DECODE_SCALE_CHECKS(who)                                                                                           \
+  ICL_CHECK_ARG(kscale && vscale, who ": NULL pointer");                                                                       \
+  ICL_CHECK_ARG(((uintptr_t)kscale & 3) == 0 && ((uintptr_t)vscale & 3) == 0, who ": misaligned operands")
+#define ICL_DECODE_ROPE_CHECKS(who)                                                                                            \
+  ICL_CHECK_ARG(qkv && cosT && sinT && pos && kc && vc && O && lens, who ": NULL pointer");                                    \
+  ICL_DECODE_SIZE_CHECKS(who);                                                                                                 \
+  ICL_CHECK_ARG(ld % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0 && k_off >= (int64_t)n_heads * head_dim &&                     \
+                    v_off >= k_off + (int64_t)n_heads * head_dim && ld >= v_off + (int64_t)n_heads * head_dim,                 \
+                who ": q | k | v column blocks must be 8-element aligned and disjoint inside a row");                           \
+  ICL_CHECK_ARG(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)kc & 15) == 0 && ((uintptr_t)vc & 15) == 0 &&                        \
+                    ((uintptr_t)cosT & 15) == 0 && ((uintptr_t)sinT & 15) == 0, who ": misaligned operands")
 
 extern "C" int icl_attn_decode_bf16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O,
                                     int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads,
                                     int32_t head_dim, int32_t max_len, float scale, void* stream) {
   ICL_DECODE_CHECKS("icl_attn_decode_bf16");
-  return launch_attn_decode(Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, nullptr, 8,
+  return launch_attn_decode(Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, 1, head_dim, max_len, scale, nullptr, 8,
                             stream, "icl_attn_decode_bf16");
 }
 
@@ -425,19 +356,16 @@ extern "C" int icl_attn_decode_bf16_epl16(const void* Q, int64_t ldq, const void
                                           int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads,
                                           int32_t head_dim, int32_t max_len, float scale, void* stream) {
   ICL_DECODE_CHECKS("icl_attn_decode_bf16_epl16");
-  return launch_attn_decode(Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, nullptr, 16,
+  return launch_attn_decode(Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, 1, head_dim, max_len, scale, nullptr, 16,
                             stream, "icl_attn_decode_bf16_epl16");
 }
 
-extern "C" int icl_attn_decode_fp8(const void* Q, int64_t ldq, const void* kq, const void* vq, const float* kscale,
+extern "C" int icl_attn_decode_fp8(const void* Q, int64_t ldq, const void* Kc, const void* Vc, const float* kscale,
                                    const float* vscale, void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads,
                                    int32_t head_dim, int32_t max_len, float scale, void* stream) {
-  const void* Kc = kq;
-  const void* Vc = vq;
   ICL_DECODE_CHECKS("icl_attn_decode_fp8");
-  ICL_CHECK_ARG(kscale && vscale, "icl_attn_decode_fp8: NULL pointer");
-  ICL_CHECK_ARG(((uintptr_t)kscale & 3) == 0 && ((uintptr_t)vscale & 3) == 0, "icl_attn_decode_fp8: misaligned operands");
-  return launch_attn_decode(Q, ldq, kq, vq, kscale, vscale, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, nullptr, 16,
+  ICL_DECODE_SCALE_CHECKS("icl_attn_decode_fp8");
+  return launch_attn_decode(Q, ldq, Kc, Vc, kscale, vscale, O, ldo, lens, n_seqs, n_heads, 1, head_dim, max_len, scale, nullptr, 16,
                             stream, "icl_attn_decode_fp8");
 }
 
@@ -448,73 +376,45 @@ extern "C" int icl_attn_decode_gqa_bf16(const void* Q, int64_t ldq, const void* 
   ICL_CHECK_ARG(n_kv_heads > 0 && n_kv_heads <= 65535 && n_heads % n_kv_heads == 0,
                 "icl_attn_decode_gqa_bf16: n_heads=%d is not a multiple of n_kv_heads=%d", n_heads, n_kv_heads);
   const int group = n_heads / n_kv_heads;
-  if (group == 1)     // multi-head attention: the multi-head kernel
-    return launch_attn_decode(Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, nullptr, 8,
-                              stream, "icl_attn_decode_gqa_bf16");
-  ICL_CHECK_ARG(group <= 8, "icl_attn_decode_gqa_bf16: %d query heads per K/V head (at most 8)", group);
-  ICL_CHECK_ARG(head_dim == 128, "icl_attn_decode_gqa_bf16: head_dim=%d (grouped-query attention: only 128)", head_dim);
-  ICL_CHECK_ARG(ldo % 8 == 0 && ldq >= (int64_t)n_heads * head_dim && ldo >= (int64_t)n_heads * head_dim,
-                "icl_attn_decode_gqa_bf16: ldq / ldo must hold n_heads * head_dim columns (ldo %% 8 == 0)");
-  const dim3 grid(n_kv_heads, n_seqs);
-  // key rounds in flight per group size: 8 (64 VGPRs of loads) next to two heads of state, 4 from three heads on (DESIGN.md §4)
-#define ICL_GQA_CASE(GG, UU)                                                                                                   \
-  case GG:                                                                                                                     \
-    hipLaunchKernelGGL((attn_decode_gqa_kernel<GG, UU>), grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short*)Q,   \
-                       ldq, (const unsigned short*)Kc, (const unsigned short*)Vc, (unsigned short*)O, ldo, lens, n_kv_heads,   \
-                       max_len, scale * LOG2E);                                                                                \
-    break
-  switch (group) {
-    ICL_GQA_CASE(2, 8);
-    ICL_GQA_CASE(3, 4);
-    ICL_GQA_CASE(4, 4);
-    ICL_GQA_CASE(5, 4);
-    ICL_GQA_CASE(6, 4);
-    ICL_GQA_CASE(7, 4);
-    ICL_GQA_CASE(8, 4);
+  if (group > 1) {    // 1 is multi-head attention, under the multi-head entry points' conditions
+    ICL_CHECK_ARG(group <= 8, "icl_attn_decode_gqa_bf16: %d query heads per K/V head (at most 8)", group);
+    ICL_CHECK_ARG(head_dim == 128, "icl_attn_decode_gqa_bf16: head_dim=%d (grouped-query attention: only 128)", head_dim);
+    ICL_CHECK_ARG(ldo % 8 == 0 && ldq >= (int64_t)n_heads * head_dim && ldo >= (int64_t)n_heads * head_dim,
+                  "icl_attn_decode_gqa_bf16: ldq / ldo must hold n_heads * head_dim columns (ldo %% 8 == 0)");
   }
-#undef ICL_GQA_CASE
-  ICL_CHECK_LAUNCH("icl_attn_decode_gqa_bf16");
-  return ICL_OK;
+  return launch_attn_decode(Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_kv_heads, group, head_dim, max_len, scale,
+                            nullptr, 8, stream, "icl_attn_decode_gqa_bf16");
 }
-#undef ICL_DECODE_CHECKS
 
-#define ICL_DECODE_ROPE_CHECKS(who)                                                                                            \
-  ICL_CHECK_ARG(qkv && cosT && sinT && pos && kc && vc && O && lens, who ": NULL pointer");                                    \
-  ICL_CHECK_ARG(head_dim == 64 || head_dim == 128, who ": head_dim=%d (only 64 and 128)", head_dim);                           \
-  ICL_CHECK_ARG(n_seqs > 0 && n_seqs <= 65535 && n_heads > 0 && max_len > 0, who ": bad sizes");                               \
-  ICL_CHECK_ARG(ld % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0 && k_off >= (int64_t)n_heads * head_dim &&                     \
-                    v_off >= k_off + (int64_t)n_heads * head_dim && ld >= v_off + (int64_t)n_heads * head_dim,                 \
-                who ": q | k | v column blocks must be 8-element aligned and disjoint inside a row");                           \
-  ICL_CHECK_ARG(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)kc & 15) == 0 && ((uintptr_t)vc & 15) == 0 &&                        \
-                    ((uintptr_t)cosT & 15) == 0 && ((uintptr_t)sinT & 15) == 0, who ": misaligned operands")
+// the RoPE-fused forms: kscale / vscale NULL = the bf16 cache
+static int launch_attn_decode_rope(const void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* cosT, const float* sinT,
+                                   const int32_t* pos, const int32_t* seq_ids, void* kc, void* vc, float* kscale, float* vscale,
+                                   void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads, int32_t head_dim,
+                                   int32_t max_len, float scale, void* stream, const char* who) {
+  const DecodeRope rp = {cosT, sinT, pos, seq_ids, kc, vc, kscale, vscale, k_off, v_off};
+  return launch_attn_decode(qkv, ld, kc, vc, kscale, vscale, O, ldo, lens, n_seqs, n_heads, 1, head_dim, max_len, scale, &rp,
+                            kscale ? 16 : 8, stream, who);
+}
 
 extern "C" int icl_attn_decode_rope_bf16(const void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* cosT,
-                                         const float* sinT, const int32_t* pos, const int32_t* seq_ids, void* kcache, void* vcache,
+                                         const float* sinT, const int32_t* pos, const int32_t* seq_ids, void* kc, void* vc,
                                          void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads,
                                          int32_t head_dim, int32_t max_len, float scale, void* stream) {
-  void* kc = kcache;
-  void* vc = vcache;
   ICL_DECODE_ROPE_CHECKS("icl_attn_decode_rope_bf16");
-  DecodeRope rp;
-  rp.cosT = cosT; rp.sinT = sinT; rp.pos = pos; rp.seq_ids = seq_ids;
-  rp.kc = kcache; rp.vc = vcache; rp.ks = rp.vs = nullptr; rp.k_off = k_off; rp.v_off = v_off;
-  return launch_attn_decode(qkv, ld, kcache, vcache, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, &rp,
-                            8, stream, "icl_attn_decode_rope_bf16");
+  return launch_attn_decode_rope(qkv, ld, k_off, v_off, cosT, sinT, pos, seq_ids, kc, vc, nullptr, nullptr, O, ldo, lens, n_seqs,
+                                 n_heads, head_dim, max_len, scale, stream, "icl_attn_decode_rope_bf16");
 }
 
 extern "C" int icl_attn_decode_rope_fp8(const void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* cosT,
-                                        const float* sinT, const int32_t* pos, const int32_t* seq_ids, void* kq, void* vq,
+                                        const float* sinT, const int32_t* pos, const int32_t* seq_ids, void* kc, void* vc,
                                         float* kscale, float* vscale, void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs,
                                         int32_t n_heads, int32_t head_dim, int32_t max_len, float scale, void* stream) {
-  void* kc = kq;
-  void* vc = vq;
   ICL_DECODE_ROPE_CHECKS("icl_attn_decode_rope_fp8");
-  ICL_CHECK_ARG(kscale && vscale, "icl_attn_decode_rope_fp8: NULL pointer");
-  ICL_CHECK_ARG(((uintptr_t)kscale & 3) == 0 && ((uintptr_t)vscale & 3) == 0, "icl_attn_decode_rope_fp8: misaligned operands");
-  DecodeRope rp;
-  rp.cosT = cosT; rp.sinT = sinT; rp.pos = pos; rp.seq_ids = seq_ids;
-  rp.kc = kq; rp.vc = vq; rp.ks = kscale; rp.vs = vscale; rp.k_off = k_off; rp.v_off = v_off;
-  return launch_attn_decode(qkv, ld, kq, vq, kscale, vscale, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, &rp, 16, stream,
-                            "icl_attn_decode_rope_fp8");
+  ICL_DECODE_SCALE_CHECKS("icl_attn_decode_rope_fp8");
+  return launch_attn_decode_rope(qkv, ld, k_off, v_off, cosT, sinT, pos, seq_ids, kc, vc, kscale, vscale, O, ldo, lens, n_seqs,
+                                 n_heads, head_dim, max_len, scale, stream, "icl_attn_decode_rope_fp8");
 }
 #undef ICL_DECODE_ROPE_CHECKS
+#undef ICL_DECODE_SCALE_CHECKS
+#undef ICL_DECODE_CHECKS
+#undef ICL_DECODE_SIZE_CHECKS

@@ -37,9 +37,10 @@ one grid is a multiple of 8 workgroups and the other is not, the r8 branch of th
   ... each with kv_lens none | given, packed rows and the cache layout (NaN past each length)
   test_suffix                                        attn_fwd_kernel<128, true, false, true>
   test_prefill_unaligned_out                         the 8-byte store path of store_output (O not 16-byte aligned): il64, <128, true, false>, suffix
-  test_decode[attn_decode, D, few|many]              attn_decode_kernel<D, 16|4, false, false, 8>
-  test_decode[attn_decode_bf16_epl16, D, few|many]   attn_decode_kernel<D, 8|4, false, false, 16>   (anchors the fp8 kernels, tied to it bit for bit)
-  test_decode[attn_decode_rope, D, few|many]         attn_decode_kernel<D, 16|4, true, false, 8>    (target = the appended position)
+  test_decode[attn_decode, D, few|many]              attn_decode_kernel<D, 16|4, false, false, 8, 1>
+  test_decode[attn_decode_bf16_epl16, D, few|many]   attn_decode_kernel<D, 8|4, false, false, 16, 1>   (anchors the fp8 kernels, tied to it bit for bit)
+  test_decode[attn_decode_rope, D, few|many]         attn_decode_kernel<D, 16|4, true, false, 8, 1>    (target = the appended position)
+  (the sixth argument is the query heads per K/V head: 2..8 are tests/test_gpu_gqa.py::test_decode_gqa)
   test_qformer[win]                                  qformer_xattn_kernel
 """
 import itertools
