@@ -10,7 +10,11 @@ GEMM  (pre = a @ W^T + bias in float64, mag = |a| @ |W|^T, K the depth; every bo
   SwiGLU               = 1.1 e_g (|up| + e_u) + |silu(g)| e_u + u (16 + 4 |g|) |ref|,  e_g / e_u the e_pre of gate / up
   bf16 output          = the f32 bound + 1 bf16 ulp of max(|ref|, |out|)
 
-Norms: norm_bound() below, derived in the docstring of test_gpu_norm_exact.py."""
+Norms: norm_bound() below, derived in the docstring of test_gpu_norm_exact.py.
+
+Glue and audio front-end kernels (test_gpu_glue_exact.py, test_gpu_frontend_exact.py; on the CPU test_glue_bounds.py): the
+helpers of the last section, each with its derivation in its docstring.  Their bf16 outputs are judged by bf16_interval(): out
+must lie in [bf16(ref - e), bf16(ref + e)], which leaves a truncating or doubly rounding store no output ulp to hide in."""
 import math
 
 import torch
@@ -133,3 +137,162 @@ def norm_ref_bound(x, gamma, beta, eps, *, rms=False, res=None, alpha=1.0):
     rho = 0.5 * dt / t + 2 * U
     ref = d * rstd * g + b
     return ref, g.abs() * rstd * (e_d + (d.abs() + e_d) * (rho + 3 * U)) + U * ref.abs()
+
+
+# ---- glue and audio front-end kernels (tests/test_glue_bounds.py on the CPU, test_gpu_glue_exact.py / test_gpu_frontend_exact.py) --
+F64_SLACK = 2.0 ** -30     # the float64 slack of the front-end bounds: test_glue_bounds.py measures two independent float64
+#                            formulations (rfft; a direct DFT summed in reverse order) and asserts they differ by < F64_SLACK / 8
+
+
+def bf16_rne(x):
+    """float64 -> the nearest bf16 value (ties to even), returned as float64.  Done on the exponent / mantissa of the double
+    itself: a cast through float32 rounds twice.  Subnormals are spaced 2^-133; +-0 stay; no overflow handling (not needed)."""
+    _, ex = torch.frexp(x)                                   # |x| = m 2^ex, m in [0.5, 1)
+    ulp = torch.exp2((ex - 1).clamp_min(-126).double() - 7)
+    return torch.round(x / ulp) * ulp                        # the division is exact; torch.round is half-to-even
+
+
+def bf16_interval(ref, e):
+    """(lo, hi) = (bf16(ref - e), bf16(ref + e)) under round-to-nearest-even: rounding is monotone, so a kernel whose f32 value
+    is within e of ref and which rounds it once to bf16 lands in [lo, hi]; one that truncates, or rounds an ulp too far, does
+    not hide inside an added output ulp."""
+    return bf16_rne(ref - e), bf16_rne(ref + e)
+
+
+def in_interval(out, lo, hi):
+    """Mask of the bf16 outputs inside [lo, hi] (NaN counts as outside)."""
+    o = out.double()
+    return (lo <= o) & (o <= hi)
+
+
+def interval_ratio(out, ref, lo, hi):
+    """The err / bound figure of an interval check: max of |out - ref| / (the interval's reach on that side); > 1 iff outside."""
+    o = out.double()
+    err = (o - ref).abs()
+    reach = torch.where(o > ref, hi - ref, ref - lo)
+    r = torch.where(err == 0, torch.zeros_like(err), err / reach)
+    return float(torch.nan_to_num(r, nan=float("inf")).max())
+
+
+def rope_ref_bound(x, cos, sin):
+    """(ref, e) of the HF rotate-half RoPE of x [..., D] (bf16, taken as data) by cos / sin [..., D / 2] (f32, as data,
+    broadcastable): with a = x[..., :D/2], b = x[..., D/2:],  ref_lo = a c - b s,  ref_hi = b c + a s.
+    rope_rot8 (csrc/common.h) rounds each product and the sum once (__fmul_rn / __fsub_rn, no contraction):
+        e = U (|a c| + |b s|) + U |ref|        (the two products; the sum, whose ulp is that of ref to first order)."""
+    h = x.shape[-1] // 2
+    a, b = x[..., :h].double(), x[..., h:].double()
+    c, s = cos.double(), sin.double()
+    lo, hi = a * c - b * s, b * c + a * s
+    e_lo = U * ((a * c).abs() + (b * s).abs()) + U * lo.abs()
+    e_hi = U * ((b * c).abs() + (a * s).abs()) + U * hi.abs()
+    return torch.cat([lo, hi], -1), torch.cat([e_lo, e_hi], -1)
+
+
+def f32_scalar(v):
+    """The value a float argument has once the C ABI has made it an f32."""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+def axpby_ref_bound(x, alpha, add=None):
+    """(ref, e) of x alpha (+ add) as an f32 value; alpha is what the kernel receives (f32).  Unfused, fl(fl(x alpha) + add)
+    is off by at most U |x alpha| + U |ref|; the fused form by U |ref| alone: e = U |x alpha| + U |ref| admits both.  Without
+    `add` there is one rounding: e = U |ref|."""
+    p = x.double() * f32_scalar(alpha)
+    if add is None:
+        return p, U * p.abs()
+    ref = p + add.double()
+    return ref, U * p.abs() + U * ref.abs()
+
+
+def lora_ref_bound(x, a, scale):
+    """(ref, e) of scale * x @ a^T, x [M, K0] and a [r, K0] bf16 taken as data.  A lane of lora_down_kernel sums K0 / 64
+    exact bf16 products in series (K0 / 512 steps of 8), the wave adds 6 shuffle levels, 2 spare for the ragged last step:
+        e = (K0 / 64 + 8) U |scale| sum |x a| + 2U |ref|       (2U: the product with scale, and margin for its f32 value)."""
+    K0 = x.shape[-1]
+    s = f32_scalar(scale)
+    dot, mag = dot64(x, a)
+    ref = s * dot
+    return ref, (K0 / 64.0 + 8.0) * U * abs(s) * mag + 2 * U * ref.abs()
+
+
+def _sigmoid_bound(s, e_s):
+    """sigma = 1 / (1 + __expf(-s)) of an f32 s within e_s of the float64 s.  sigma' = sigma (1 - sigma) <= 1/4 falls with |t|,
+    so over [s - e_s, s + e_s] it is at most its value at the point nearest 0, t = max(|s| - e_s, 0) (the mean value theorem;
+    tighter than the flat 1/4, which leaves a saturated sigmoid a bound thousands of times its error); __expf is exp2 of the
+    rounded product s log2(e), within (|s| + 3) U relative, which moves sigma by sigma (1 - sigma) times that; the sum 1 + e
+    and the division are two roundings, 2 more on the same factor and 2U sigma:
+        e_sigma = e_s sigma'(t) + (|s| + 5) U sigma (1 - sigma) + 2U sigma."""
+    sg = torch.sigmoid(s)
+    t = (s.abs() - e_s).clamp_min(0.0)
+    return sg, e_s * torch.sigmoid(t) * torch.sigmoid(-t) + (s.abs() + 5) * U * sg * torch.sigmoid(-s) + 2 * U * sg
+
+
+def gate_ref_bound(q, w, b, a):
+    """(ref, e) of the BEATs gate  sigma(s_a) (sigma(s_b) A_h - 1) + 2,  q [M, H, 64] bf16 as data, w [8, 64], b [8], a [H] f32:
+    s_a / s_b are the sums of the accumulators 0..3 / 4..7, each b_j + 64 serial products (65 terms) and 3 more additions:
+        e_s = 70 U sum_j (sum_d |w_jd q_d| + |b_j|),
+        e   = e_sa |sigma_b A - 1| + sigma_a |A| e_sb + 4U (|ref| + 2)
+    (the last: the product with A, the - 1, the outer product and the + 2, on values no larger than |ref| + 2)."""
+    q64, w64, b64 = q.double(), w.double(), b.double()
+    proj = q64 @ w64.t() + b64                                 # [M, H, 8]
+    mag = q64.abs() @ w64.abs().t() + b64.abs()
+    s = proj.view(*proj.shape[:-1], 2, 4).sum(-1)
+    e_s = 70 * U * mag.view(*mag.shape[:-1], 2, 4).sum(-1)
+    sa, e_a = _sigmoid_bound(s[..., 0], e_s[..., 0])
+    sb, e_b = _sigmoid_bound(s[..., 1], e_s[..., 1])
+    A = a.double()
+    ref = sa * (sb * A - 1.0) + 2.0
+    return ref, e_a * (sb * A - 1.0).abs() + sa * A.abs() * e_b + 4 * U * (ref.abs() + 2)
+
+
+def ce_ref_bound(logits, labels):
+    """(row_ref, row_e, mean_ref, mean_e) of the ignore_index cross entropy; logits [M, V] f32 as data, labels [M] (a label
+    outside [0, V) is ignored: its row is 0 exactly, bound 0).  m = max x, d = x - m, p = softmax, l = log sum e^d,
+    ref = l + m - x_y.  ce_rows_kernel: d is rounded once (U |d|), __expf of it is within (|d| + 3) U relative, so each term
+    of the sum carries (2 |d| + 3) U relative and the sum moves by U sum p (2 |d| + 3) relative — absolute in l, its log; a
+    thread's chain of V / 256 additions, the shuffle tree and the four wave sums of positive terms add (V / 256 + 8) U; logf
+    2U |l|; the two additions U |l + m| and U |ref|; terms flushed below the smallest normal, 1e-37 V:
+        e = (V / 256 + 8) U + U sum_v p_v (2 |d_v| + 3) + 2U |l| + U |l + m| + U |ref| + 1e-37 V.
+    The mean over the n valid rows is a sum of M / 256 serial terms per thread, the tree, and one division:
+        e_mean = (M / 256 + 8) U mean |ref_row| + mean e_row + U |mean|;  no valid row: NaN (mean_e 0)."""
+    M, V = logits.shape
+    x = logits.double()
+    y = labels.long()
+    valid = (y >= 0) & (y < V)
+    m = x.max(-1, keepdim=True).values
+    d = x - m
+    ex = torch.exp(d)
+    z = ex.sum(-1, keepdim=True)
+    p = ex / z
+    l = torch.log(z)
+    xy = x.gather(1, y.clamp(0, V - 1)[:, None])
+    ref = l + m - xy
+    e = ((V / 256.0 + 8.0) * U + U * (p * (2 * d.abs() + 3)).sum(-1, keepdim=True) + 2 * U * l.abs() + U * (l + m).abs()
+         + U * ref.abs() + 1e-37 * V)
+    ref = torch.where(valid, ref[:, 0], torch.zeros_like(ref[:, 0]))
+    e = torch.where(valid, e[:, 0], torch.zeros_like(e[:, 0]))
+    n = int(valid.sum())
+    if n == 0:
+        return ref, e, float("nan"), 0.0
+    mean = float(ref.sum() / n)
+    e_mean = (M / 256.0 + 8.0) * U * float(ref.abs().sum() / n) + float(e.sum() / n) + U * abs(mean)
+    return ref, e, mean, e_mean
+
+
+def whisper_ref_bound(r):
+    """(r, e) for one clip's float64 log-mel r = (max(l, l_max - 8) + 4) / 4 (oracle: whisper_logmel(as_f64=True)),
+    l = log10(max(mel, 1e-10)).  The kernel's mel energies are float64; it rounds l to f32 (U |l|), takes the maximum of
+    those (U |l_max|), subtracts 8 (U |l_max - 8|), adds 4 (U |l_c + 4|, at most U (|l_c| + 4)) and divides by 4 (exact), l_c
+    the clamped value:
+        e = U (2 max(|l_c|, |l_max| + 8) + 4) / 4 + U |r| + 2^-30.
+    |l| is taken at the clamped value l_c = 4 r - 4 (tighter than the unclamped l, and all r gives): the rounding of an l
+    below the clamp reaches the output only if it crosses the clamp, and then l is within that rounding of l_c."""
+    lc = 4.0 * r - 4.0
+    lmax = lc.max().abs()
+    return r, U * (2 * torch.maximum(lc.abs(), lmax + 8.0) + 4.0) / 4.0 + U * r.abs() + F64_SLACK
+
+
+def kaldi_ref_bound(r):
+    """(r, e) for the float64 normalised fbank r (oracle: kaldi_fbank(as_f64=True) with the f32 values of mean and std, which
+    is what the kernel receives): the kernel works in float64 and rounds once, e = U |r| + 2^-30."""
+    return r, U * r.abs() + F64_SLACK
