@@ -7,7 +7,8 @@
 //      with f(x) = x < 0 ? x * penalty : x / penalty (once per distinct token, as HF's gather/scatter does);
 //   2. exact k-th largest value by a 4-pass 8-bit radix select over order-preserving integer keys (LDS histograms);
 //   3. every token >= that value (ties kept, as HF's `scores < kth` mask does) goes to an LDS candidate list, which is
-//      bitonic-sorted by (value descending, token id ascending);
+//      bitonic-sorted by (value descending, token id ascending); more than SAMPLE_CAP such tokens (ties at the cut): the
+//      list is every token above the cut, then the tied ones by ascending token id until it is full;
 //   4. softmax over the candidates; nucleus cut: candidate j is dropped when the probability mass of candidates j.. (the
 //      ascending cumulative sum HF computes) is <= 1 - top_p, the largest one always stays;
 //   5. inverse-CDF draw over the kept candidates in that order with the caller's uniform u in [0,1);
@@ -98,7 +99,45 @@ __global__ __launch_bounds__(256) void sample_eos_kernel(
     }
   }
   __syncthreads();
-  const int n_cand = (int)min(s_count, (unsigned int)SAMPLE_CAP);
+  const unsigned int n_qual = s_count;
+  if (n_qual > SAMPLE_CAP) {
+    // More qualifying tokens than slots (ties at the cut: a flat row, a -inf-masked row, top-k off with ties at the 1024th
+    // value): which ones the atomics above kept depends on arrival order.  Rebuild the list by rule: every token strictly
+    // above the cut (fewer than top_k <= SAMPLE_CAP of them, any order: the sort below fixes it), then the tied ones by
+    // ascending token id until the list is full — a block scan over the row, 256 tokens per round.  n_qual is block-uniform.
+    const int lane = tid & 63, wave = tid >> 6;
+    __syncthreads();                                 // every thread has read s_count
+    if (tid == 0) s_count = 0u;
+    __syncthreads();
+    for (int v = tid; v < V; v += 256) {
+      const unsigned int k = f32_order_key(w[v]);
+      if (k > kth) {
+        const unsigned int slot = atomicAdd(&s_count, 1u);
+        if (slot < SAMPLE_CAP) {
+          ckey[slot] = k;
+          cidx[slot] = v;
+        }
+      }
+    }
+    __syncthreads();
+    unsigned int filled = min(s_count, (unsigned int)SAMPLE_CAP);
+    for (int base = 0; base < V && filled < SAMPLE_CAP; base += 256) {
+      const int v = base + tid;
+      const bool tie = v < V && f32_order_key(w[v]) == kth;
+      const unsigned long long bal = __ballot(tie);
+      if (lane == 0) hist[wave] = (unsigned int)__popcll(bal);
+      __syncthreads();
+      unsigned int slot = filled + (unsigned int)__popcll(bal & ((1ull << lane) - 1ull));
+      for (int q = 0; q < wave; ++q) slot += hist[q];
+      if (tie && slot < SAMPLE_CAP) {
+        ckey[slot] = kth;
+        cidx[slot] = v;
+      }
+      filled += (hist[0] + hist[1]) + (hist[2] + hist[3]);
+      __syncthreads();                               // hist is rewritten by the next round
+    }
+  }
+  const int n_cand = (int)min(n_qual, (unsigned int)SAMPLE_CAP);
   int n_sort = 1;
   while (n_sort < n_cand) n_sort <<= 1;
   for (int i = n_cand + tid; i < n_sort; i += 256) {
@@ -128,7 +167,8 @@ __global__ __launch_bounds__(256) void sample_eos_kernel(
   const float top = w[cidx[0]];
   float part = 0.0f;
   for (int i = tid; i < n_cand; i += 256) {
-    const float e = expf(w[cidx[i]] - top);
+    const float x = w[cidx[i]];
+    const float e = x == x ? expf(x - top) : 0.0f;   // a listed NaN (fewer comparable scores than top_k, or top-k off) has no mass
     cprob[i] = e;
     part += e;
   }

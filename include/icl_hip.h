@@ -356,6 +356,12 @@ int icl_argmax_fsm(const float* logits, int64_t ldl, int32_t B, int32_t V, const
  * tokens and a nucleus wider than that is truncated to them; any other top_k is ICL_EINVAL.  Greedy search with a
  * repetition penalty is top_k = 1.  Optional debug outputs (NULL to skip): the kept tokens, their renormalised
  * probabilities and their count, dbg_cap entries per sequence.
+ * Overflow rule: the candidate list has 1024 slots.  When more than 1024 tokens are at or above the cut (ties at the cut: a
+ * flat row, a row masked with -inf that leaves fewer finite scores than top_k, top-k off with ties at the 1024th value),
+ * the list holds EVERY token strictly above the cut, then the tied tokens by ascending token id until it is full — the
+ * first 1024 tokens in (score desc, token asc) order, the same on every launch.  Probabilities are finite whenever the row
+ * has a finite score: a -inf score has probability 0 and is never drawn, and neither is a NaN score (NaN sorts below -inf;
+ * one that reaches the list — fewer comparable scores than top_k, or top-k off — carries no mass).
  * Replaces HF generate(do_sample=True, temperature, top_p, repetition_penalty) as called at models/custom_salmon.py:705-721
  * (RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper, TopKLogitsWarper [generation-config default 50],
  * TopPLogitsWarper, softmax, multinomial).

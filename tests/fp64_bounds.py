@@ -14,7 +14,10 @@ Norms: norm_bound() below, derived in the docstring of test_gpu_norm_exact.py.
 
 Glue and audio front-end kernels (test_gpu_glue_exact.py, test_gpu_frontend_exact.py; on the CPU test_glue_bounds.py): the
 helpers of the last section, each with its derivation in its docstring.  Their bf16 outputs are judged by bf16_interval(): out
-must lie in [bf16(ref - e), bf16(ref + e)], which leaves a truncating or doubly rounding store no output ulp to hide in."""
+must lie in [bf16(ref - e), bf16(ref + e)], which leaves a truncating or doubly rounding store no output ulp to hide in.
+
+Sampling and beam-step kernels (test_gpu_decode_tail_exact.py; on the CPU test_decode_tail_bounds.py): the references and the
+derivations of their bounds are in oracle/decode_tail.py; check_sampler_row() / check_beam_row() at the end judge one row."""
 import math
 
 import torch
@@ -296,3 +299,119 @@ def kaldi_ref_bound(r):
     """(r, e) for the float64 normalised fbank r (oracle: kaldi_fbank(as_f64=True) with the f32 values of mean and std, which
     is what the kernel receives): the kernel works in float64 and rounds once, e = U |r| + 2^-30."""
     return r, U * r.abs() + F64_SLACK
+
+
+# ---- the sampled and the beam-search decode tails (test_decode_tail_bounds.py on the CPU, test_gpu_decode_tail_exact.py) -------
+# The references and the derivations of their bounds are project code: oracle/decode_tail.py.  What follows judges one row of
+# outputs — the kernel's, or those of the f32 emulation of tests/decode_tail_cases.py — against them; both checkers return
+# (worst err / bound, ambiguous) and raise AssertionError.
+def _ratio(err, bound):
+    import numpy as np
+    err, bound = np.asarray(err, dtype=np.float64), np.asarray(bound, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        r = np.where(err == 0, 0.0, err / bound)
+    return float(np.nan_to_num(r, nan=float("inf")).max()) if r.size else 0.0
+
+
+def _same_bits(a, b):
+    import numpy as np
+    return np.array_equal(np.ascontiguousarray(a, dtype=np.float32).view(np.uint32),
+                          np.ascontiguousarray(b, dtype=np.float32).view(np.uint32))
+
+
+def check_sampler_row(case, b, out, tag=""):
+    """One row of a sampler launch.  `case`: a dict of tests/decode_tail_cases.py; `out`: work [ldw], ids / probs [cap],
+    count, next_id, tokens [width], finished.  Always: the scores bit for bit (NaN where NaN), every sentinel, the kept ids
+    (exact: their order does not depend on any sum), count in [keep_lo, keep_hi], each probability within its bound of the
+    float64 value renormalised over the kernel's own count, a justified pick, the bookkeeping.  On a determinate row also
+    count == keep and the float64 pick."""
+    import numpy as np
+    from oracle import decode_tail as dt
+    V, step, S = case["V"], case["step"], case["sentinel"]
+    row = case["logits"][b, :V]
+    prev = case["tokens"][b, :step]
+    scores = dt.sampler_scores(row, prev, case["pen"], case["temp"])
+    work = np.asarray(out["work"], dtype=np.float32)
+    nan = np.isnan(scores)
+    assert np.array_equal(np.isnan(work[:V]), nan), f"{tag}: NaN pattern of the scores"
+    assert _same_bits(np.where(nan, 0, work[:V]), np.where(nan, 0, scores)), \
+        f"{tag}: scores differ from the two f32 operations at {np.nonzero(np.where(nan, 0, work[:V]) != np.where(nan, 0, scores))[0][:5]}"
+    assert _same_bits(work[V:], np.full(work.shape[0] - V, S, np.float32)), f"{tag}: work written past V"
+    ref = dt.SamplerRef(scores, case["top_k"], case["top_p"])
+    cnt = int(out["count"])
+    assert ref.keep_lo <= cnt <= ref.keep_hi, f"{tag}: count {cnt} outside [{ref.keep_lo}, {ref.keep_hi}]"
+    ids = np.asarray(out["ids"])
+    assert ids[:cnt].tolist() == ref.cand[:cnt].tolist(), f"{tag}: kept ids"
+    assert bool((ids[cnt:] == -1).all()), f"{tag}: debug ids written past count"
+    probs = np.asarray(out["probs"], dtype=np.float32)
+    assert _same_bits(probs[cnt:], np.full(probs.shape[0] - cnt, S, np.float32)), f"{tag}: debug probs written past count"
+    cdf, e_cdf, p64, e_p = ref.kept(cnt)
+    assert bool(np.isfinite(probs[:cnt]).all()), f"{tag}: non-finite probability"
+    err = np.abs(probs[:cnt].astype(np.float64) - p64)
+    ratio = _ratio(err, e_p)
+    assert bool((err <= e_p).all()), f"{tag}: probability outside its bound, worst err/bound {ratio}"
+    fin_in, nxt = int(case["finished"][b]), int(out["next_id"])
+    u = case["u"][b]
+    if fin_in:
+        assert nxt == case["pad"], f"{tag}: finished row emitted {nxt}"
+    else:
+        ok = ref.cand[ref.justified_picks(u, cnt)].tolist()
+        assert nxt in ok, f"{tag}: pick {nxt} not justified by u={u!r} (justified: {ok})"
+    j64, pick_det = ref.pick(u, ref.keep)
+    determinate = ref.cut_determinate and pick_det
+    if determinate:
+        assert cnt == ref.keep, f"{tag}: determinate row, count {cnt} != {ref.keep}"
+        if not fin_in:
+            assert nxt == int(ref.cand[j64]), f"{tag}: determinate row, pick {nxt} != {int(ref.cand[j64])}"
+    want_fin = int(bool(fin_in) or nxt in [e for e in case["eos"] if e >= 0])
+    assert int(out["finished"]) == want_fin, f"{tag}: finished flag"
+    toks = np.asarray(out["tokens"])
+    want = case["tokens"][b].copy()
+    want[step] = nxt
+    assert toks.tolist() == want.tolist(), f"{tag}: out_tokens"
+    return ratio, not determinate
+
+
+def check_beam_row(ref, out, old, tag=""):
+    """One batch row of a beam-step launch against `ref` (oracle.decode_tail.BeamStepRef, built from the incoming state
+    `old`).  `out` / `old`: dicts of the row's run_score [K], run_seq [K, T], fin_score, fin_seq, fin_len, fin_flag, unsat
+    and (out) next_ids, parent (beam index inside the row).  Always: ranges; each running sequence is its parent's old one
+    with the token at `step`; run_score within the bound of the float64 score of the (parent, token) chosen, and that score
+    within the bounds of the reference's i-th best run value (the rank it took); a closed row keeps its finished slots bit
+    for bit.  On a determinate step every integer equals the reference and fin_score is within its bound."""
+    import numpy as np
+    K, V, T, step = ref.K, ref.V, ref.T, ref.step
+    par, nxt = np.asarray(out["parent"]).astype(np.int64), np.asarray(out["next_ids"]).astype(np.int64)
+    assert bool(((par >= 0) & (par < K)).all()) and bool(((nxt >= 0) & (nxt < V)).all()), f"{tag}: parent / token range"
+    want_seq = np.asarray(old["run_seq"])[par].copy()
+    want_seq[np.arange(K), step] = nxt
+    assert np.array_equal(np.asarray(out["run_seq"]), want_seq), f"{tag}: run_seq is not parent's sequence + token"
+    assert int(out["unsat"]) in (0, 1) and set(np.asarray(out["fin_flag"]).tolist()) <= {0, 1}, f"{tag}: flags"
+    assert bool(((np.asarray(out["fin_len"]) >= 0) & (np.asarray(out["fin_len"]) <= T)).all()), f"{tag}: fin_len range"
+    errs, bounds = [], []
+    rs = np.asarray(out["run_score"], dtype=np.float64)
+    for i in range(K):
+        a, e = ref.score_of(int(par[i]), int(nxt[i]))
+        if np.isfinite(a):
+            errs.append(abs(rs[i] - a)); bounds.append(e)
+            assert abs(rs[i] - a) <= e, f"{tag}: run_score[{i}] {rs[i]} vs {a}, bound {e}"
+            assert abs(a - ref.run_score[i]) <= e + ref.run_score_e[i], f"{tag}: beam {i} took a rank its score does not justify"
+        else:
+            assert rs[i] == a and ref.run_score[i] == a, f"{tag}: run_score[{i}] {rs[i]} vs {a}"
+    if not ref.row_open:
+        for name in ("fin_seq", "fin_len", "fin_flag"):
+            assert np.array_equal(np.asarray(out[name]), np.asarray(old[name])), f"{tag}: closed row, {name} changed"
+        assert _same_bits(out["fin_score"], old["fin_score"]) and int(out["unsat"]) == 0, f"{tag}: closed row changed"
+    if ref.determinate:
+        assert par.tolist() == ref.parent.tolist() and nxt.tolist() == ref.next_ids.tolist(), \
+            f"{tag}: parents / tokens {par.tolist()} {nxt.tolist()} vs {ref.parent.tolist()} {ref.next_ids.tolist()}"
+        assert np.array_equal(np.asarray(out["fin_flag"]), ref.fin_flag), f"{tag}: fin_flag"
+        assert np.array_equal(np.asarray(out["fin_len"]), ref.fin_len), f"{tag}: fin_len"
+        assert np.array_equal(np.asarray(out["fin_seq"]), ref.fin_seq), f"{tag}: fin_seq"
+        assert int(out["unsat"]) == ref.unsat, f"{tag}: unsat {int(out['unsat'])} vs {ref.unsat}"
+        fs = np.asarray(out["fin_score"], dtype=np.float64)
+        for i in range(K):
+            errs.append(abs(fs[i] - ref.fin_score[i])); bounds.append(ref.fin_score_e[i])
+            assert abs(fs[i] - ref.fin_score[i]) <= ref.fin_score_e[i], \
+                f"{tag}: fin_score[{i}] {fs[i]} vs {ref.fin_score[i]}, bound {ref.fin_score_e[i]}"
+    return _ratio(errs, bounds), not ref.determinate
