@@ -475,6 +475,12 @@ def decode_plan(Bn: int, cfg, k_aug: int, n_cu: int, weight_dtype: str = "bf16",
     return DecodePlan(Bn, plan, nsplit * Bn * max(qkv_width(cfg), 2 * I) if nsplit > 1 else 0)
 
 
+def prefill_sites(cfg, k_aug: int, tile: int = 0) -> Dict[str, GemmLaunch]:
+    """The four GEMM sites of a prefill layer, in the form of ``DecodePlan.sites``: the row-major weights, no split-K, the
+    library's tile choice (0) — or one pinned ``tile`` (the trimmed last layer, ``LlamaHIP._last_layer_rows``)."""
+    return {name: GemmLaunch(tile, 1, "row", N, K) for name, (N, K) in site_shapes(cfg, k_aug).items()}
+
+
 # ================================================================================================
 # K9 + K10 + K11 (+K12 host side): Llama
 # ================================================================================================
@@ -494,13 +500,6 @@ class LlamaHIP:
     # attention, o_proj, norm and MLP on those rows alone (``prefill(last_rows_only=True)``; bit-identical).
     # ICL_PREFILL_LAST_ROWS=0 restores the full-height last layer + a gather, for A/B.
     prefill_last_rows = os.environ.get("ICL_PREFILL_LAST_ROWS", "1") != "0"
-    # f32 [n_seqs, hidden] or None: set by ``want_last_rows``, consumed by the next ``prefill`` call
-    _last_rows_out: Optional[torch.Tensor] = None
-
-    def want_last_rows(self, out: torch.Tensor) -> None:
-        """The NEXT ``prefill`` call runs as ``prefill(..., last_rows_only=True, last_out=out)``.  The request travels on the
-        object, not in the call, so that ``prefill`` keeps its (ws, h, seq_lens, cache) call form for code that wraps it."""
-        self._last_rows_out = out
 
     def decode_plan(self, Bn: int) -> DecodePlan:
         """The GEMM launches of a decode step over Bn rows on this device, in this runtime's weight mode (``decode_plan``)."""
@@ -557,72 +556,54 @@ class LlamaHIP:
         B.embed_gather_interleave(src_idx, self.w.embed, speech, h)
         return h
 
-    # ---- one decoder layer over M packed rows ---------------------------------------------------
-    def _layer(self, ws: Workspace, L, h, M: int, tag: str, attn_fn, pos, seq_ids, kc, vc, max_len: int,
-               split: Optional[DecodePlan] = None, kv_rows_to_c: bool = True, xn_ready: bool = False, next_norm=None,
-               attn_does_rope: bool = False, rope_fn=None):
-        """``xn_ready``: the previous call has already written this layer's normalised input (decode: fused into the reduction
-        of the previous down_proj).  ``next_norm`` = (gamma, out bf16 [M, >= hidden]) of the RMSNorm that follows this layer
-        (the next layer's input norm into the same ``xn`` buffer, or the final norm): decode fuses it into the down_proj's
-        split-K reduction, as it does the post-attention norm into the o_proj's (icl_gemm_rmsnorm_bf16).  ``rope_fn(qkv)``
-        replaces the stand-alone RoPE + cache append of a decode step (the FP8 KV cache's icl_rope_kv_fp8).  ``split``: the decode
-        step's GEMM plan (``decode_plan``); None = prefill (the library's tile choice, no split-K)."""
-        c, w = self.w.cfg, self.w
-        hd, I, D, H = c.hidden, c.ffn, c.head_dim, c.n_heads
-        k_off, v_off = qkv_offsets(c)
-        xn = ws.get(tag + "xn", (M, w.k_aug), BF16, zero=True)   # augmentation tail stays zero
-        qkv = ws.get(tag + "qkv", (M, qkv_width(c)), BF16)
-        att = ws.get(tag + "att", (M, hd), BF16)
-        act = ws.get(tag + "act", (M, I), BF16)
-        wsk = ws.get(tag + "splitk", (split.workspace,), F32) if split is not None and split.workspace else None
-
-        def launch_of(name):                       # the plan's launch of this site; prefill: the library's tile on the row-major weight
-            return split.sites[name] if split is not None else GemmLaunch(0, 1, "row", *site_shapes(c, w.k_aug)[name])
-
-        def site_gemm(name, a, out, norm=None, **epilogue):
-            """The GEMM of site ``name`` on the weight form its launch names: row-major, decode-packed (tiles 5 / 6) or the fp8
-            decode-packed copy + row scales (FP8 weight mode, <= 8 rows).  ``norm`` = (gamma, xn): the RMSNorm fused behind it."""
-            p, idx = launch_of(name), DECODE_SITES.index(name)
-            q, scale = L.fp8[idx] if p.weight == "fp8" else (None, None)
-            wt = q if p.weight == "fp8" else L.decode_packed[idx] if p.weight == "packed" else (L.wqkv, L.wo, L.wgu, L.wdown)[idx]
-            kw = dict(split_k=p.split_k, workspace=wsk, tile=p.tile, N=p.N, K=p.K, w_scale=scale, **epilogue)
-            if norm is not None:
-                return B.gemm_rmsnorm(a, wt, out, norm[0], c.rms_eps, norm[1], **kw)
-            return B.gemm(a, wt, out, **kw)
-        if not xn_ready:
+    # ---- the pieces of a decoder layer over M packed rows; prefill and decode_step write out the K/V route between them ----
+    def _xn(self, ws: Workspace, L, h, M: int, tag: str, decode: bool, ready: bool = False) -> torch.Tensor:
+        """The layer's input for the QKV projection, bf16 [M, k_aug] in ``tag + "xn"``: RMSNorm of ``h`` (unless ``ready``: the
+        previous down_proj has written it, fused into its reduction) and the LoRA down-projection into the augmentation columns."""
+        c, hd = self.w.cfg, self.w.cfg.hidden
+        xn = ws.get(tag + "xn", (M, self.w.k_aug), BF16, zero=True)   # augmentation tail stays zero
+        if not ready:
             B.rmsnorm(h, L.rms1, xn, c.rms_eps, N=hd)
         if L.lora_a is not None:   # x_aug[:, hd:hd+2r] = x @ (s*A)^T : a skinny GEMM for prefill, a GEMV-style kernel for decode
             # prefill: always the 64x64 tile (the choice must not depend on the batch, or rows would not be batch-invariant);
             # decode: the skinny kernel (one block, K split over its 8 waves) up to 64 rows, the block-per-row kernel above
             # that (an N = 16 GEMM on the 64x64 tile is 2 blocks walking all of K: 40 us vs 15)
             r2 = L.lora_a.shape[0]
-            if split is not None and M > 64:
+            if decode and M > 64:
                 B.lora_down(xn, hd, L.lora_a, r2, 1.0, M=M)      # the LoRA scale is folded into lora_a at pack time
             else:
-                B.gemm(xn, L.lora_a, xn[:, hd:hd + r2], K=hd, tile=4 if split is not None else 2)
-        if split is None and c.group == 1 and B.rope_fusable(M, H, D, L.wqkv.shape[1]):
-            # prefill on the 256x256 tile: RoPE + cache append run in the GEMM's staged epilogue (same bits as the two calls)
-            B.gemm(xn, L.wqkv, qkv, bias=L.bqkv, tile=3,
-                   rope=(k_off, v_off, w.rope_cos, w.rope_sin, pos, seq_ids, kc, vc, H, D, max_len, kv_rows_to_c))
+                B.gemm(xn, L.lora_a, xn[:, hd:hd + r2], K=hd, tile=4 if decode else 2)
+        return xn
+
+    def _site_gemm(self, L, sites: Dict[str, GemmLaunch], name: str, a, out, wsk, norm=None, **epilogue):
+        """The GEMM of site ``name`` on the weight form its launch names: row-major, decode-packed (tiles 5 / 6) or the fp8
+        decode-packed copy + row scales (FP8 weight mode, <= 8 rows).  ``wsk``: the split-K workspace or None;
+        ``norm`` = (gamma, xn): the RMSNorm fused behind the GEMM (icl_gemm_rmsnorm_*)."""
+        p, idx = sites[name], DECODE_SITES.index(name)
+        q, scale = L.fp8[idx] if p.weight == "fp8" else (None, None)
+        wt = q if p.weight == "fp8" else L.decode_packed[idx] if p.weight == "packed" else (L.wqkv, L.wo, L.wgu, L.wdown)[idx]
+        kw = dict(split_k=p.split_k, workspace=wsk, tile=p.tile, N=p.N, K=p.K, w_scale=scale, **epilogue)
+        if norm is not None:
+            return B.gemm_rmsnorm(a, wt, out, norm[0], self.w.cfg.rms_eps, norm[1], **kw)
+        return B.gemm(a, wt, out, **kw)
+
+    def _attn_out_mlp(self, ws: Workspace, L, h, xn, att, tag: str, sites: Dict[str, GemmLaunch], wsk, next_norm=None) -> bool:
+        """From the attention output to the end of the layer: h += att Wo^T, post-attention RMSNorm into ``xn``, gate/up, h += down.
+        ``next_norm`` = (gamma, out bf16 [M, >= hidden]) of the RMSNorm that follows this layer (the next layer's input norm, or
+        the final norm): a ``down`` launch with ``fused_norm`` runs it in its split-K reduction, as ``o`` does the post-attention
+        norm (icl_gemm_rmsnorm_bf16) — True is returned when it has been written."""
+        c = self.w.cfg
+        act = ws.get(tag + "act", (att.shape[0], c.ffn), BF16)
+        if sites["o"].fused_norm:     # one call (one kernel when the GEMM is split-K)
+            self._site_gemm(L, sites, "o", att, h, wsk, norm=(L.rms2, xn), residual=h)
         else:
-            site_gemm("qkv", xn, qkv, bias=L.bqkv)
-            if rope_fn is not None:
-                rope_fn(qkv)
-            elif c.group > 1:           # grouped-query attention: the plain route, RoPE + append in a launch of their own
-                B.rope_kv_gqa(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, seq_ids, kc, vc, H, c.kv_heads, D, max_len, M=M)
-            elif not attn_does_rope:    # decode: RoPE + cache append run inside the attention launch (icl_attn_decode_rope_bf16)
-                B.rope_kv(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, seq_ids, kc, vc, H, D, max_len, M=M)
-        attn_fn(qkv, att)
-        if launch_of("o").fused_norm:   # decode: h += att Wo^T and the post-attention RMSNorm in one call (one kernel when the GEMM is split-K)
-            site_gemm("o", att, h, norm=(L.rms2, xn), residual=h)
-        else:
-            site_gemm("o", att, h, residual=h)
-            B.rmsnorm(h, L.rms2, xn, c.rms_eps, N=hd)
-        site_gemm("gu", xn, act, swiglu=True)
-        if launch_of("down").fused_norm and next_norm is not None:
-            site_gemm("down", act, h, norm=next_norm, residual=h)
+            self._site_gemm(L, sites, "o", att, h, wsk, residual=h)
+            B.rmsnorm(h, L.rms2, xn, c.rms_eps, N=c.hidden)
+        self._site_gemm(L, sites, "gu", xn, act, wsk, swiglu=True)
+        if sites["down"].fused_norm and next_norm is not None:
+            self._site_gemm(L, sites, "down", act, h, wsk, norm=next_norm, residual=h)
             return True
-        site_gemm("down", act, h, residual=h)
+        self._site_gemm(L, sites, "down", act, h, wsk, residual=h)
         return False
 
     # ---- K10: prefill over ragged packed sequences ------------------------------------------------
@@ -635,9 +616,7 @@ class LlamaHIP:
         head.  Every layer's K / V still reach the cache for all rows; ``h`` is then NOT the final hidden states (the last
         layer leaves its other rows untouched, ``_last_layer_rows``).  The rows returned are bit-identical to the same rows of
         the full prefill."""
-        if self._last_rows_out is not None:        # a request left by want_last_rows: this call serves it
-            last_rows_only, last_out, self._last_rows_out = True, self._last_rows_out, None
-        c = self.w.cfg
+        c, w = self.w.cfg, self.w
         dev = h.device
         M = sum(seq_lens)
         cu_h = [0]
@@ -652,51 +631,58 @@ class LlamaHIP:
         H, D, hd = c.n_heads, c.head_dim, c.hidden
         k_off, v_off = qkv_offsets(c)
         gqa = c.group > 1      # grouped-query attention: no fused RoPE epilogue, so k / v stay packed next to q and no trimming
-
-        # With a cache and the fused QKV epilogue, k / v are written ONCE — into the cache — and the attention reads them
-        # there ([seq][head][pos][D]: 256-B rows at a 256-B stride instead of a 3*hidden stride); the k / v columns of the QKV
-        # buffer are never written.  Without a cache (teacher-forced forward) they stay packed next to q.
-        # FP8 KV cache: prefill attends to its own unrounded k / v, so the layer runs as without a cache (k / v rows into the QKV
-        # buffer) and one icl_kv_append_fp8 pass rounds them into the cache before the attention.
         fp8 = cache is not None and cache.dtype == "fp8"
-        kv_from_cache = cache is not None and not fp8 and not gqa and B.rope_fusable(M, H, D, self.w.k_aug)
+        max_len = cache.max_len if cache is not None else 0
+        # the QKV GEMM runs on the 256x256 tile: RoPE + cache append run in its staged epilogue (same bits as the two calls)
+        epilogue = not gqa and B.rope_fusable(M, H, D, w.k_aug)
+        in_cache = epilogue and cache is not None and not fp8      # ... and the attention reads k / v from the (bf16) cache
         # the trimmed last layer is built on the 256-tile's fused RoPE epilogue (head_dim 128) and a bf16 cache; other models
         # and the FP8 KV mode (whose prefill attends to unrounded packed k / v) keep the full-height layer and gather after it
-        trim = last_rows_only and self.prefill_last_rows and not fp8 and not gqa and B.rope_epilogue_ok(H, D, self.w.k_aug)
-
-        def attn(qkv, att):
-            B.attn_fwd(qkv[:, :k_off], qkv[:, k_off:v_off], qkv[:, v_off:], att, cu, maxS, H, D, D ** -0.5, causal=True,
-                       n_kv_heads=c.kv_heads if gqa else 0)
-
-        last_idx = _i32([e - 1 for e in cu_h[1:]], dev) if last_rows_only else None
-
-        def last_rows(src):
+        trim = last_rows_only and self.prefill_last_rows and not fp8 and not gqa and B.rope_epilogue_ok(H, D, w.k_aug)
+        last_idx = out = None
+        if last_rows_only:
+            last_idx = _i32([e - 1 for e in cu_h[1:]], dev)
             out = last_out if last_out is not None else ws.get("pfl_h", (len(seq_lens), hd), F32)
-            return B.gather_rows(src, last_idx, out)
-
-        n_layers = len(self.w.layers)
-        for i, L in enumerate(self.w.layers):
-            kc = cache.k[i] if cache is not None else None
-            vc = cache.v[i] if cache is not None else None
-            if trim and i == n_layers - 1:
-                return self._last_layer_rows(ws, L, h, M, seq_lens, pos, sid, cu, kc, vc, cache.max_len, last_idx, last_rows)
-            fn = attn
+        sites = prefill_sites(c, w.k_aug)
+        for i, L in enumerate(w.layers):
+            kc, vc, ks, vs = cache.layer(i) if cache is not None else (None, None, None, None)
+            if trim and i == len(w.layers) - 1:
+                return self._last_layer_rows(ws, L, h, seq_lens, pos, sid, cu, kc, vc, max_len, last_idx, out)
+            xn = self._xn(ws, L, h, M, "pf_", decode=False)
+            qkv = ws.get("pf_qkv", (M, qkv_width(c)), BF16)
+            att = ws.get("pf_att", (M, hd), BF16)
+            # Who rotates q / k and where k / v go.  With a bf16 cache and the fused epilogue, k / v are written ONCE — into the
+            # cache — and the attention reads them there ([seq][head][pos][D]: 256-B rows at a 256-B stride instead of a 3*hidden
+            # stride); the k / v columns of the QKV buffer are never written.  Otherwise they stay packed next to q.  FP8 KV
+            # cache: prefill attends to its own unrounded k / v, so RoPE appends nowhere and one icl_kv_append_fp8 pass rounds the
+            # rows into the cache before the attention.
+            if in_cache:            # epilogue into the cache
+                B.gemm(xn, L.wqkv, qkv, bias=L.bqkv, tile=3,
+                       rope=(k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, kc, vc, H, D, max_len, False))
+            elif epilogue:          # epilogue with packed k / v: no cache (teacher-forced forward) or the FP8 one
+                B.gemm(xn, L.wqkv, qkv, bias=L.bqkv, tile=3,
+                       rope=(k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, None, None, H, D, 0, True))
+            elif gqa:               # stand-alone RoPE + append, grouped-query (never with the FP8 cache)
+                self._site_gemm(L, sites, "qkv", xn, qkv, None, bias=L.bqkv)
+                B.rope_kv_gqa(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, kc, vc, H, c.kv_heads, D, max_len, M=M)
+            elif fp8:               # stand-alone RoPE, no append
+                self._site_gemm(L, sites, "qkv", xn, qkv, None, bias=L.bqkv)
+                B.rope_kv(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, None, None, H, D, 0, M=M)
+            else:                   # stand-alone RoPE + append to the bf16 cache, if there is one
+                self._site_gemm(L, sites, "qkv", xn, qkv, None, bias=L.bqkv)
+                B.rope_kv(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, kc, vc, H, D, max_len, M=M)
             if fp8:
-                def fn(qkv, att, i=i):
-                    B.kv_append_fp8(qkv, k_off, v_off, pos, sid, cache.k[i], cache.v[i], cache.ks[i], cache.vs[i], H, D, cache.max_len,
-                                    M=M)
-                    attn(qkv, att)
-                self._layer(ws, L, h, M, "pf_", fn, pos, sid, None, None, 0)
-                continue
-            if kv_from_cache:
-                def fn(qkv, att, kc=kc, vc=vc):
-                    B.attn_fwd(qkv[:, :hd], kc, vc, att, cu, maxS, H, D, D ** -0.5, causal=True, kv_cache_max_len=cache.max_len)
-            self._layer(ws, L, h, M, "pf_", fn, pos, sid, kc, vc, cache.max_len if cache is not None else 0,
-                        kv_rows_to_c=not kv_from_cache)
-        return last_rows(h) if last_rows_only else h
+                B.kv_append_fp8(qkv, k_off, v_off, pos, sid, kc, vc, ks, vs, H, D, max_len, M=M)
+            if in_cache:
+                B.attn_fwd(qkv[:, :hd], kc, vc, att, cu, maxS, H, D, D ** -0.5, causal=True, kv_cache_max_len=max_len)
+            else:
+                B.attn_fwd(qkv[:, :k_off], qkv[:, k_off:v_off], qkv[:, v_off:], att, cu, maxS, H, D, D ** -0.5, causal=True,
+                           n_kv_heads=c.kv_heads if gqa else 0)
+            self._attn_out_mlp(ws, L, h, xn, att, "pf_", sites, None)
+        return B.gather_rows(h, last_idx, out) if last_rows_only else h
 
-    def _last_layer_rows(self, ws: Workspace, L, h, M: int, seq_lens: List[int], pos, sid, cu, kc, vc, max_len: int,
-                         last_idx, last_rows) -> torch.Tensor:
+    def _last_layer_rows(self, ws: Workspace, L, h, seq_lens: List[int], pos, sid, cu, kc, vc, max_len: int,
+                         last_idx, hg) -> torch.Tensor:
         """The last decoder layer of a prefill whose caller reads the last row of every sequence only: the layer's k / v are
         projected (and appended to the cache) for all M rows; q, the attention, o_proj, the post-attention norm and the MLP run
         on the len(seq_lens) gathered rows.  Exact, not approximate: every kernel here computes a row independently of its
@@ -704,21 +690,17 @@ class LlamaHIP:
         order (tiles 1 - 3 agree, so the small launches are pinned to tile 3 instead of the library's small-M choice), the same
         fused RoPE epilogue at the row's position, and the full attention launch's wave, lane and 64-key tile sequence
         (icl_attn_fwd_suffix_bf16, q_len = 1).  The gathered buffers have names of their own (pfl_*): the full-height ones
-        keep their size.  Returns the rows' final hidden states, f32 [len(seq_lens), hidden]."""
+        keep their size.  Returns ``hg``, f32 [len(seq_lens), hidden]: the rows' final hidden states."""
         c, w = self.w.cfg, self.w
-        hd, I, D, H = c.hidden, c.ffn, c.head_dim, c.n_heads
-        Bn, dev = len(seq_lens), h.device
-        xn = ws.get("pf_xn", (M, w.k_aug), BF16, zero=True)
-        B.rmsnorm(h, L.rms1, xn, c.rms_eps, N=hd)
-        if L.lora_a is not None:
-            r2 = L.lora_a.shape[0]
-            B.gemm(xn, L.lora_a, xn[:, hd:hd + r2], K=hd, tile=2)
+        hd, D, H = c.hidden, c.head_dim, c.n_heads
+        M, Bn, dev = sum(seq_lens), len(seq_lens), h.device
+        xn = self._xn(ws, L, h, M, "pf_", decode=False)
         rope = (w.rope_cos, w.rope_sin)
         # k | v rows of wqkv, all M rows, into the cache only: C is never written (kv_rows_to_c = 0)
         qkv = ws.get("pf_qkv", (M, qkv_width(c)), BF16)
         B.gemm(xn, L.wqkv[hd:], qkv, bias=L.bqkv[hd:] if L.bqkv is not None else None, tile=3,
                rope=(0, hd, *rope, pos, sid, kc, vc, H, D, max_len, False))
-        hg = last_rows(h)
+        B.gather_rows(h, last_idx, hg)
         xg = ws.get("pfl_xn", (Bn, w.k_aug), BF16)              # whole augmented rows: the LoRA columns and the zero tail come along
         B.gather_rows(xn, last_idx, xg)
         # q rows of wqkv on the gathered rows, rotated at each row's own (last) position
@@ -728,11 +710,7 @@ class LlamaHIP:
         att = ws.get("pfl_att", (Bn, hd), BF16)
         B.attn_fwd(q, kc, vc, att, cu, max(seq_lens), H, D, D ** -0.5, causal=True, kv_cache_max_len=max_len,
                    cu_q=_i32(list(range(Bn + 1)), dev))
-        B.gemm(att, L.wo, hg, residual=hg, tile=3, N=hd, K=hd)
-        B.rmsnorm(hg, L.rms2, xg, c.rms_eps, N=hd)
-        act = ws.get("pfl_act", (Bn, I), BF16)
-        B.gemm(xg, L.wgu, act, swiglu=True, tile=3, N=2 * I, K=hd)
-        B.gemm(act, L.wdown, hg, residual=hg, tile=3, N=hd, K=I)
+        self._attn_out_mlp(ws, L, hg, xg, att, "pfl_", prefill_sites(c, w.k_aug, tile=3), None)
         return hg
 
     def logits(self, ws: Workspace, h_rows: torch.Tensor, name: str = "ll_logits", xn_ready: bool = False) -> torch.Tensor:
@@ -750,56 +728,50 @@ class LlamaHIP:
     # ---- K11: one decode step for Bn sequences -----------------------------------------------------
     def decode_step(self, ws: Workspace, cache: "KVCache", next_ids: torch.Tensor, pos: torch.Tensor,
                     lens: torch.Tensor, sid: torch.Tensor) -> torch.Tensor:
-        c = self.w.cfg
+        c, w = self.w.cfg, self.w
         Bn = next_ids.numel()
         h = self.embed(ws, next_ids, None, name="dc_h")
         H, D = c.n_heads, c.head_dim
         k_off, v_off = qkv_offsets(c)
-        split = self.decode_plan(Bn)
-        if any(p.weight == "packed" for p in split.sites.values()):
+        plan = self.decode_plan(Bn)
+        sites = plan.sites
+        if any(p.weight == "packed" for p in sites.values()):
             self.ensure_decode_packed()
 
-        layers = self.w.layers
-        xn_next = ws.get("dc_xn", (Bn, self.w.k_aug), BF16, zero=True)          # the layers' normalised-input buffer (_layer's tag + "xn")
+        layers = w.layers
+        xn_next = ws.get("dc_xn", (Bn, w.k_aug), BF16, zero=True)            # the layers' normalised-input buffer (_xn's)
         xn_final = ws.get("dc_logits_xn", (Bn, c.hidden), BF16)
-        ready = False
+        qkv = ws.get("dc_qkv", (Bn, qkv_width(c)), BF16)
+        att = ws.get("dc_att", (Bn, c.hidden), BF16)
+        wsk = ws.get("dc_splitk", (plan.workspace,), F32) if plan.workspace else None
         fp8 = cache.dtype == "fp8"
+        max_len, scale = cache.max_len, D ** -0.5
+        # One launch: rotate q / k at pos, append k / v, attend — bit-identical to the two launches, so the choice is free.
+        # Same-box A/B (tools/ab_decode_rope.sh, profiles/r04_decode_rope_ab.txt): at 256 rows decode 143.2 -> 142.5 ms; at ONE
+        # sequence 58.4 -> 59.6 ms per utterance — the rotation's dependent loads (pos -> cos / sin, q, k) sit in front of a
+        # latency-bound attention and cost more than the 5-us launch they replace — so small batches keep the two launches.
+        fuse_rope = self.fuse_decode_rope and Bn > 8
+        ready = False
         for i, L in enumerate(layers):
-            kc, vc = cache.k[i], cache.v[i]
-            ks, vs = (cache.ks[i], cache.vs[i]) if fp8 else (None, None)
-
-            # One launch: rotate q / k at pos, append k / v, attend — bit-identical to the two launches, so the choice is free.
-            # Same-box A/B (tools/ab_decode_rope.sh, profiles/r04_decode_rope_ab.txt): at 256 rows decode 143.2 -> 142.5 ms; at ONE
-            # sequence 58.4 -> 59.6 ms per utterance — the rotation's dependent loads (pos -> cos / sin, q, k) sit in front of a
-            # latency-bound attention and cost more than the 5-us launch they replace — so small batches keep the two launches.
-            # Grouped-query attention: two launches at every batch size, RoPE + append (_layer) and the GQA decode attention.
-            fuse_rope = self.fuse_decode_rope and Bn > 8 and c.group == 1
-            rope_fn = None
-            if c.group > 1:
-                def attn(qkv, att, kc=kc, vc=vc):
-                    B.attn_decode_gqa(qkv[:, :k_off], kc, vc, att, lens, H, c.kv_heads, D, cache.max_len, D ** -0.5)
-            elif fp8 and fuse_rope:       # FP8 KV cache: the same two forms, rounding the appended row to x' (icl_hip.h)
-                def attn(qkv, att, kc=kc, vc=vc, ks=ks, vs=vs):
-                    B.attn_decode_rope_fp8(qkv, k_off, v_off, self.w.rope_cos, self.w.rope_sin, pos, sid, kc, vc, ks, vs,
-                                           att, lens, H, D, cache.max_len, D ** -0.5)
+            kc, vc, ks, vs = cache.layer(i)
+            xn = self._xn(ws, L, h, Bn, "dc_", decode=True, ready=ready)
+            self._site_gemm(L, sites, "qkv", xn, qkv, wsk, bias=L.bqkv)
+            if c.group > 1:       # grouped-query attention: two launches at every batch size, RoPE + append and the GQA decode attention
+                B.rope_kv_gqa(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, kc, vc, H, c.kv_heads, D, max_len, M=Bn)
+                B.attn_decode_gqa(qkv[:, :k_off], kc, vc, att, lens, H, c.kv_heads, D, max_len, scale)
+            elif fp8 and fuse_rope:   # FP8 KV cache: the same two forms, rounding the appended row to x' (icl_hip.h)
+                B.attn_decode_rope_fp8(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, kc, vc, ks, vs, att, lens, H, D,
+                                       max_len, scale)
             elif fp8:
-                def rope_fn(qkv, ks=ks, vs=vs, kc=kc, vc=vc):
-                    B.rope_kv_fp8(qkv, k_off, v_off, self.w.rope_cos, self.w.rope_sin, pos, sid, kc, vc, ks, vs, H, D,
-                                  cache.max_len, M=Bn)
-
-                def attn(qkv, att, kc=kc, vc=vc, ks=ks, vs=vs):
-                    B.attn_decode_fp8(qkv[:, :k_off], kc, vc, ks, vs, att, lens, H, D, cache.max_len, D ** -0.5)
+                B.rope_kv_fp8(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, kc, vc, ks, vs, H, D, max_len, M=Bn)
+                B.attn_decode_fp8(qkv[:, :k_off], kc, vc, ks, vs, att, lens, H, D, max_len, scale)
             elif fuse_rope:
-                def attn(qkv, att, kc=kc, vc=vc):
-                    B.attn_decode_rope(qkv, k_off, v_off, self.w.rope_cos, self.w.rope_sin, pos, sid, kc, vc, att, lens,
-                                       H, D, cache.max_len, D ** -0.5)
+                B.attn_decode_rope(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, kc, vc, att, lens, H, D, max_len, scale)
             else:
-                def attn(qkv, att, kc=kc, vc=vc):
-                    B.attn_decode(qkv[:, :k_off], kc, vc, att, lens, H, D, cache.max_len, D ** -0.5)
-
-            nxt = (layers[i + 1].rms1, xn_next) if i + 1 < len(layers) else (self.w.norm, xn_final)
-            ready = self._layer(ws, L, h, Bn, "dc_", attn, pos, sid, kc, vc, cache.max_len, split=split, xn_ready=ready,
-                                next_norm=nxt, attn_does_rope=fuse_rope, rope_fn=rope_fn)
+                B.rope_kv(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, kc, vc, H, D, max_len, M=Bn)
+                B.attn_decode(qkv[:, :k_off], kc, vc, att, lens, H, D, max_len, scale)
+            nxt = (layers[i + 1].rms1, xn_next) if i + 1 < len(layers) else (w.norm, xn_final)
+            ready = self._attn_out_mlp(ws, L, h, xn, att, "dc_", sites, wsk, next_norm=nxt)
         return self.logits(ws, h, name="dc_logits", xn_ready=ready)
 
 
@@ -839,6 +811,10 @@ class KVCache:
             self.k = ws.get("kv_k", shape, BF16)
             self.v = ws.get("kv_v", shape, BF16)
             self.ks = self.vs = None
+
+    def layer(self, i: int):
+        """(k, v, k scales, v scales) of layer i; the scales are None in a bf16 cache."""
+        return self.k[i], self.v[i], None if self.ks is None else self.ks[i], None if self.vs is None else self.vs[i]
 
     def planes(self):
         """((k, k scales), (v, v scales)); the scales are None in a bf16 cache."""

@@ -222,18 +222,16 @@ class CausalLMRuntimeMixin:
         # GEMMs measured 1.3 % faster per utterance at 128 sequences than at 256.  A sequence's arithmetic does not depend on
         # its neighbours in either phase, so the split changes no result.
         # Only the last position of every prompt is read from here on (final norm, LM head; decode reads the K/V cache): the
-        # prefill writes those rows into ``gen_last`` and trims its last layer to them (LlamaHIP.want_last_rows / prefill).
+        # prefill writes those rows into ``gen_last`` and trims its last layer to them (LlamaHIP.prefill, last_rows_only).
         last = ws.get("gen_last", (Bn, c.hidden), F32)
         if Bn <= self.prefill_chunk:
-            self.llama.want_last_rows(last)
-            self.llama.prefill(ws, h, lens, cache)
+            self.llama.prefill(ws, h, lens, cache, last_rows_only=True, last_out=last)
         else:
             r0 = 0
             for b0 in range(0, Bn, self.prefill_chunk):
                 b1 = min(Bn, b0 + self.prefill_chunk)
                 r1 = r0 + sum(lens[b0:b1])
-                self.llama.want_last_rows(last[b0:b1])
-                self.llama.prefill(ws, h[r0:r1], lens[b0:b1], cache.rows(b0, b1))
+                self.llama.prefill(ws, h[r0:r1], lens[b0:b1], cache.rows(b0, b1), last_rows_only=True, last_out=last[b0:b1])
                 r0 = r1
         logits = self.llama.logits(ws, last, name="gen_logits")
         first = logits.clone() if want_first_logits else None
@@ -417,8 +415,7 @@ class CausalLMRuntimeMixin:
         for b0 in range(0, Bn, self.prefill_chunk):
             b1 = min(Bn, b0 + self.prefill_chunk)
             r1 = r0 + sum(lens[b0:b1])
-            self.llama.want_last_rows(last[b0:b1])
-            self.llama.prefill(ws, h[r0:r1], lens[b0:b1], pre.rows(b0, b1))
+            self.llama.prefill(ws, h[r0:r1], lens[b0:b1], pre.rows(b0, b1), last_rows_only=True, last_out=last[b0:b1])
             r0 = r1
         logits = self.llama.logits(ws, last, name="gen_logits")
         first = logits.clone() if want_first_logits else None

@@ -321,8 +321,8 @@ def xprime_reference(rt):
             for c in (kc, vc):
                 c[s[:, None], h[None], p[:, None]] = ref_q(c[s[:, None], h[None], p[:, None]])[2]
 
-    def prefill_xp(ws, h, seq_lens, cache=None):
-        out = prefill(ws, h, seq_lens, cache)
+    def prefill_xp(ws, h, seq_lens, cache=None, **kw):
+        out = prefill(ws, h, seq_lens, cache, **kw)
         if cache is not None:
             for b, n in enumerate(seq_lens):
                 for c in (cache.k, cache.v):
@@ -498,8 +498,8 @@ def test_cli_fp8_kv_writes_the_same_files_as_the_x_prime_reference(tmp_path, mon
                 for c in (kc, vc):
                     c[s[:, None], h[None], p[:, None]] = ref_q(c[s[:, None], h[None], p[:, None]])[2]
 
-        def prefill_xp(self, ws, h, seq_lens, cache=None):
-            out = prefill(self, ws, h, seq_lens, cache)
+        def prefill_xp(self, ws, h, seq_lens, cache=None, **kw):
+            out = prefill(self, ws, h, seq_lens, cache, **kw)
             if cache is not None:
                 for b, n in enumerate(seq_lens):
                     for c in (cache.k, cache.v):

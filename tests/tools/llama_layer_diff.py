@@ -39,7 +39,7 @@ xn2_o = ob._rms(h1_o, lp + "post_attention_layernorm.weight")
 g_o = om._lin(xn2_o, lsd, lp + "mlp.gate_proj", rnd); u_o = om._lin(xn2_o, lsd, lp + "mlp.up_proj", rnd)
 act_o = rnd(F.silu(g_o) * u_o)
 h2_o = h1_o + om._lin(act_o, lsd, lp + "mlp.down_proj", rnd)
-# GPU pieces (same calls as LlamaHIP._layer, no cache)
+# GPU pieces (same calls as a layer of LlamaHIP.prefill, no cache)
 BF16 = torch.bfloat16
 xn = torch.zeros(S, w.k_aug, dtype=BF16, device="cuda")
 B.rmsnorm(h, L.rms1, xn, c.rms_eps, N=hd)
