@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from ..runtime import synth
 from ..runtime.config import QwenAudioCfg
+from ..runtime.packing import refuse_stray_qk_norm
 from ..utils.tokenization import ByteTokenizer, Encoding
 from .base_model import BaseModel
 from .custom_salmon import PackedTreeModule, check_llm_kv_dtype, check_llm_weight_dtype
@@ -63,6 +64,7 @@ class QwenModule(PackedTreeModule):
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         from ..runtime.qwen import normalize_qwen_keys
         sd = normalize_qwen_keys(dict(state_dict))
+        refuse_stray_qk_norm((k for k in sd if k.startswith("language_model.")), self.cfg.llm)   # before strict=False drops them
         own = self.state_dict()
         sd = {k: v for k, v in sd.items() if k in own or strict}
         out = super().load_state_dict(sd, strict=strict, assign=assign)

@@ -26,7 +26,7 @@ import torch.nn as nn
 
 from ..runtime import synth
 from ..runtime.config import LlamaCfg, QFormerCfg, SalmonnCfg, WhisperCfg, with_llama
-from ..runtime.packing import normalize_keys
+from ..runtime.packing import normalize_keys, refuse_stray_qk_norm
 from ..utils.tokenization import load_llama_tokenizer
 from .base_model import BaseModel
 
@@ -221,6 +221,7 @@ class SalmonnModule(PackedTreeModule):
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         sd = normalize_keys(dict(state_dict))
+        refuse_stray_qk_norm((k for k in sd if k.startswith("llama_model.")), self.cfg.llama)   # before strict=False drops them
         own = self.state_dict()
         sd = {k: v for k, v in sd.items() if k in own or strict}
         result = super().load_state_dict(sd, strict=strict, assign=assign)

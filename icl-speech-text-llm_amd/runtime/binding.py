@@ -78,6 +78,9 @@ _SIGNATURES = {
                                  c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "icl_rope_kv_gqa_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "icl_qknorm_rope_kv_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                        c_void_p]),
     "icl_gemm_rope_kv_bf16": (c_int, [POINTER(GemmArgs), c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "icl_pack_decode_weights": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
@@ -516,6 +519,19 @@ def rope_kv_gqa(qkv, k_off: int, v_off: int, cos, sin, pos, seq_ids, kcache, vca
                                                sin.data_ptr(), pos.data_ptr(), _ptr(seq_ids), _ptr(kcache),
                                                _ptr(vcache), M, n_heads, n_kv_heads, head_dim, max_len, _stream()),
            "icl_rope_kv_gqa_bf16")
+
+
+def qknorm_rope_kv(qkv, k_off: int, v_off: int, q_gamma, k_gamma, eps: float, cos, sin, pos, seq_ids, kcache, vcache,
+                   n_heads: int, n_kv_heads: int, head_dim: int, max_len: int, M=None):
+    """``rope_kv_gqa`` with the per-head RMSNorm of a QK-norm decoder (Qwen3) in front of the rotation: every q head row is
+    normalised over ``head_dim`` with ``q_gamma``, every k head row with ``k_gamma`` (f32 [head_dim]), rounded to bf16, rotated."""
+    _require_gpu(qkv, q_gamma, k_gamma, cos, sin, pos, seq_ids, kcache, vcache)
+    M = qkv.shape[0] if M is None else M
+    _check(load_library().icl_qknorm_rope_kv_bf16(qkv.data_ptr(), qkv.stride(0), k_off, v_off, _ptr(q_gamma), _ptr(k_gamma),
+                                                  eps, cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), _ptr(seq_ids),
+                                                  _ptr(kcache), _ptr(vcache), M, n_heads, n_kv_heads, head_dim, max_len,
+                                                  _stream()),
+           "icl_qknorm_rope_kv_bf16")
 
 
 def embed_gather_interleave(src_idx, table, speech, out):

@@ -62,7 +62,8 @@ def read_config(path: str) -> Optional[dict]:
 
 # ---- Llama / Vicuna -----------------------------------------------------------------------------------------------
 def llama_cfg_from_hf(cfg_json: dict, base: LlamaCfg) -> LlamaCfg:
-    """``config.json`` of a HF Llama folder → LlamaCfg (vocab grows by the ``[PAD]`` token SALMONN adds)."""
+    """``config.json`` of a HF Llama folder → LlamaCfg (vocab grows by the ``[PAD]`` token SALMONN adds).  ``model_type``
+    "qwen3" sets ``qk_norm``: its attention normalises every q and k head (``self_attn.{q,k}_norm.weight``)."""
     heads = cfg_json["num_attention_heads"]
     kv = cfg_json.get("num_key_value_heads") or heads
     hd = cfg_json.get("head_dim")
@@ -76,7 +77,7 @@ def llama_cfg_from_hf(cfg_json: dict, base: LlamaCfg) -> LlamaCfg:
                    rope_theta=float((cfg_json.get("rope_parameters") or {}).get("rope_theta", cfg_json.get("rope_theta", base.rope_theta))),
                    max_pos=cfg_json.get("max_position_embeddings", base.max_pos),
                    bos_id=cfg_json.get("bos_token_id", base.bos_id), eos_id=cfg_json.get("eos_token_id", base.eos_id),
-                   pad_id=cfg_json["vocab_size"])
+                   pad_id=cfg_json["vocab_size"], qk_norm=cfg_json.get("model_type") == "qwen3")
 
 
 def llama_from_hf(sd: SD, vocab: int) -> SD:

@@ -86,6 +86,7 @@ class LlamaCfg:
     lora_targets: tuple = ("q_proj", "v_proj")   # peft's Llama default (SALMONN); Qwen path: ("q_proj", "k_proj"), custom_qwen.py:75
     qkv_bias: bool = False    # Qwen2 attention has q/k/v biases
     n_kv_heads: Optional[int] = None   # grouped-query attention: K/V heads (None = n_heads); head_dim 128 only
+    qk_norm: bool = False     # Qwen3 attention: RMSNorm over head_dim on every q and k head, between the projection and RoPE
 
     def __post_init__(self):
         check_gqa(self)

@@ -631,14 +631,16 @@ class LlamaHIP:
         H, D, hd = c.n_heads, c.head_dim, c.hidden
         k_off, v_off = qkv_offsets(c)
         gqa = c.group > 1      # grouped-query attention: no fused RoPE epilogue, so k / v stay packed next to q and no trimming
+        qkn = c.qk_norm        # per-head q / k RMSNorm (Qwen3) in front of the rotation: one more reason not to fuse or trim
         fp8 = cache is not None and cache.dtype == "fp8"
         max_len = cache.max_len if cache is not None else 0
         # the QKV GEMM runs on the 256x256 tile: RoPE + cache append run in its staged epilogue (same bits as the two calls)
-        epilogue = not gqa and B.rope_fusable(M, H, D, w.k_aug)
+        epilogue = not gqa and not qkn and B.rope_fusable(M, H, D, w.k_aug)
         in_cache = epilogue and cache is not None and not fp8      # ... and the attention reads k / v from the (bf16) cache
         # the trimmed last layer is built on the 256-tile's fused RoPE epilogue (head_dim 128) and a bf16 cache; other models
         # and the FP8 KV mode (whose prefill attends to unrounded packed k / v) keep the full-height layer and gather after it
-        trim = last_rows_only and self.prefill_last_rows and not fp8 and not gqa and B.rope_epilogue_ok(H, D, w.k_aug)
+        trim = (last_rows_only and self.prefill_last_rows and not fp8 and not gqa and not qkn
+                and B.rope_epilogue_ok(H, D, w.k_aug))
         last_idx = out = None
         if last_rows_only:
             last_idx = _i32([e - 1 for e in cu_h[1:]], dev)
@@ -662,6 +664,10 @@ class LlamaHIP:
             elif epilogue:          # epilogue with packed k / v: no cache (teacher-forced forward) or the FP8 one
                 B.gemm(xn, L.wqkv, qkv, bias=L.bqkv, tile=3,
                        rope=(k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, None, None, H, D, 0, True))
+            elif qkn:               # per-head q / k norm + RoPE + append in one launch, multi-head or grouped (never the FP8 cache)
+                self._site_gemm(L, sites, "qkv", xn, qkv, None, bias=L.bqkv)
+                B.qknorm_rope_kv(qkv, k_off, v_off, L.q_gamma, L.k_gamma, c.rms_eps, w.rope_cos, w.rope_sin, pos, sid, kc, vc, H,
+                                 c.kv_heads, D, max_len, M=M)
             elif gqa:               # stand-alone RoPE + append, grouped-query (never with the FP8 cache)
                 self._site_gemm(L, sites, "qkv", xn, qkv, None, bias=L.bqkv)
                 B.rope_kv_gqa(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, kc, vc, H, c.kv_heads, D, max_len, M=M)
@@ -750,13 +756,20 @@ class LlamaHIP:
         # Same-box A/B (tools/ab_decode_rope.sh, profiles/r04_decode_rope_ab.txt): at 256 rows decode 143.2 -> 142.5 ms; at ONE
         # sequence 58.4 -> 59.6 ms per utterance — the rotation's dependent loads (pos -> cos / sin, q, k) sit in front of a
         # latency-bound attention and cost more than the 5-us launch they replace — so small batches keep the two launches.
-        fuse_rope = self.fuse_decode_rope and Bn > 8
+        fuse_rope = self.fuse_decode_rope and Bn > 8 and not c.qk_norm
         ready = False
         for i, L in enumerate(layers):
             kc, vc, ks, vs = cache.layer(i)
             xn = self._xn(ws, L, h, Bn, "dc_", decode=True, ready=ready)
             self._site_gemm(L, sites, "qkv", xn, qkv, wsk, bias=L.bqkv)
-            if c.group > 1:       # grouped-query attention: two launches at every batch size, RoPE + append and the GQA decode attention
+            if c.qk_norm:         # QK-norm (Qwen3): two launches at every batch size, norm + RoPE + append and the decode attention
+                B.qknorm_rope_kv(qkv, k_off, v_off, L.q_gamma, L.k_gamma, c.rms_eps, w.rope_cos, w.rope_sin, pos, sid, kc, vc, H,
+                                 c.kv_heads, D, max_len, M=Bn)
+                if c.group > 1:
+                    B.attn_decode_gqa(qkv[:, :k_off], kc, vc, att, lens, H, c.kv_heads, D, max_len, scale)
+                else:
+                    B.attn_decode(qkv[:, :k_off], kc, vc, att, lens, H, D, max_len, scale)
+            elif c.group > 1:     # grouped-query attention: two launches at every batch size, RoPE + append and the GQA decode attention
                 B.rope_kv_gqa(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, kc, vc, H, c.kv_heads, D, max_len, M=Bn)
                 B.attn_decode_gqa(qkv[:, :k_off], kc, vc, att, lens, H, c.kv_heads, D, max_len, scale)
             elif fp8 and fuse_rope:   # FP8 KV cache: the same two forms, rounding the appended row to x' (icl_hip.h)
@@ -780,12 +793,16 @@ KV_DTYPES = ("bf16", "fp8")
 
 def check_kv_dtype(value: str, cfg=None) -> str:
     """The KV-cache dtype of the LLM decoder: "bf16" (default) or "fp8" (the opt-in FP8 KV cache, include/icl_hip.h).
-    ``cfg`` (the decoder's LlamaCfg, when known): the FP8 KV cache has no grouped-query kernels — "fp8" is then a ValueError."""
+    ``cfg`` (the decoder's LlamaCfg, when known): the FP8 KV cache has no grouped-query kernels and none with the per-head q / k
+    norm of a QK-norm decoder (Qwen3) — "fp8" is then a ValueError."""
     if value not in KV_DTYPES:
         raise ValueError(f"llm_kv_dtype must be one of {KV_DTYPES}, not {value!r}")
     if value == "fp8" and cfg is not None and getattr(cfg, "group", 1) > 1:
         raise ValueError("llm_kv_dtype='fp8' is not available for a grouped-query decoder "
                          f"({cfg.n_heads} query heads / {cfg.kv_heads} K/V heads): the FP8 KV kernels are multi-head only")
+    if value == "fp8" and cfg is not None and getattr(cfg, "qk_norm", False):
+        raise ValueError("llm_kv_dtype='fp8' is not available for a QK-norm decoder (qk_norm=True, Qwen3): the FP8 KV kernels "
+                         "have no per-head q / k RMSNorm in front of the rotation")
     return value
 
 

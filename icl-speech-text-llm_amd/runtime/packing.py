@@ -266,6 +266,8 @@ class LlamaLayer:
     wdown: torch.Tensor
     decode_packed: Optional[tuple] = None   # (wqkv, wo, wgu, wdown) in the M <= 128 decode tile's layout, made on first use
     fp8: Optional[tuple] = None             # FP8 weight mode: ((q, scales) of wqkv, wo, wgu, wdown), LlamaHIP(weight_dtype="fp8")
+    q_gamma: Optional[torch.Tensor] = None  # QK-norm (Qwen3): f32 [head_dim] gains of the per-head q / k RMSNorm, else None
+    k_gamma: Optional[torch.Tensor] = None
 
 
 @dataclass
@@ -303,8 +305,24 @@ def qkv_row_blocks(cfg: LlamaCfg):
     return (0, k_off), (k_off, v_off - k_off), (v_off, v_off - k_off)
 
 
+QK_NORM_KEYS = ("self_attn.q_norm.weight", "self_attn.k_norm.weight")
+
+
+def refuse_stray_qk_norm(keys, cfg: LlamaCfg) -> None:
+    """A checkpoint with per-head q / k norm gains (Qwen3) under a configuration without ``qk_norm`` is a ValueError naming the
+    key: dropping the two tensors would run a model that is not the checkpoint."""
+    if cfg.qk_norm:
+        return
+    for k in keys:
+        if k.endswith(QK_NORM_KEYS):
+            raise ValueError(f"the checkpoint holds {k!r} (per-head q / k RMSNorm, Qwen3) but the decoder's configuration has "
+                             "qk_norm=False: set LlamaCfg.qk_norm (a Qwen3 config.json has model_type 'qwen3')")
+
+
 def pack_llama(sd: SD, cfg: LlamaCfg, device, prefix: str = "llama_model.", consume: bool = False) -> PackedLlama:
-    """HF causal-LM names under `prefix`: model.embed_tokens, model.layers.{i}.*, model.norm, lm_head (Llama and Qwen2 alike)."""
+    """HF causal-LM names under `prefix`: model.embed_tokens, model.layers.{i}.*, model.norm, lm_head (Llama, Qwen2 and Qwen3
+    alike; ``cfg.qk_norm``: self_attn.{q,k}_norm.weight, f32 [head_dim])."""
+    refuse_stray_qk_norm((k for k in sd if k.startswith(prefix)), cfg)
     h, I, r = cfg.hidden, cfg.ffn, cfg.lora_rank
     assert h % 64 == 0 and I % 64 == 0 and cfg.head_dim in (64, 128)
     check_gqa(cfg)
@@ -332,6 +350,10 @@ def pack_llama(sd: SD, cfg: LlamaCfg, device, prefix: str = "llama_model.", cons
         bqkv = None
         if cfg.qkv_bias:
             bqkv = _f32(torch.cat([_take(sd, lp + f"self_attn.{n}.bias", consume).float() for n in ("q_proj", "k_proj", "v_proj")]), device)
+        q_gamma = k_gamma = None
+        if cfg.qk_norm:
+            q_gamma, k_gamma = (_f32(_take(sd, lp + key, consume), device) for key in QK_NORM_KEYS)
+            assert q_gamma.shape == k_gamma.shape == (cfg.head_dim,), (lp, tuple(q_gamma.shape), tuple(k_gamma.shape))
         g = _take(sd, lp + "mlp.gate_proj.weight", consume).to(device=device, dtype=torch.bfloat16)
         u = _take(sd, lp + "mlp.up_proj.weight", consume).to(device=device, dtype=torch.bfloat16)
         wgu = torch.stack([g.view(I // 16, 16, h), u.view(I // 16, 16, h)], dim=1).reshape(2 * I, h).contiguous()
@@ -340,7 +362,7 @@ def pack_llama(sd: SD, cfg: LlamaCfg, device, prefix: str = "llama_model.", cons
             rms1=_f32(_take(sd, lp + "input_layernorm.weight", consume), device), bqkv=bqkv, wqkv=wqkv, lora_a=lora_a,
             wo=_bf(_take(sd, lp + "self_attn.o_proj.weight", consume), device),
             rms2=_f32(_take(sd, lp + "post_attention_layernorm.weight", consume), device), wgu=wgu,
-            wdown=_bf(_take(sd, lp + "mlp.down_proj.weight", consume), device)))
+            wdown=_bf(_take(sd, lp + "mlp.down_proj.weight", consume), device), q_gamma=q_gamma, k_gamma=k_gamma))
     D = cfg.head_dim
     inv = 1.0 / (cfg.rope_theta ** (torch.arange(0, D, 2, dtype=torch.float32) / D))
     ang = torch.arange(cfg.max_pos, dtype=torch.float32)[:, None] * inv[None, :]

@@ -147,6 +147,9 @@ def llama_state(cfg: LlamaCfg, g: _Gen, prefix: str = "llama_model.", margin: bo
             for n in ("q_proj", "k_proj", "v_proj"):
                 sd[lp + f"self_attn.{n}.bias"] = (g.bias(rows[n]) if g.jitter else
                                                   0.02 * torch.randn(rows[n], generator=g.g, device=g.device))
+        if cfg.qk_norm:     # 1 + 0.3 N(0, 1), q and k drawn apart in every layer: a swapped or ignored gain shows
+            for n in ("q_norm", "k_norm"):
+                sd[lp + f"self_attn.{n}.weight"] = 1.0 + 0.3 * torch.randn(cfg.head_dim, generator=g.g, device=g.device)
         if cfg.lora_rank:
             for n in cfg.lora_targets:
                 sd[lp + f"self_attn.{n}.lora_A.weight"] = g.normal(cfg.lora_rank, h)

@@ -279,6 +279,26 @@ int icl_rope_kv_gqa_bf16(void* qkv, int64_t ld, int64_t k_off, int64_t v_off, co
                          void* vcache, int32_t M, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim,
                          int32_t max_len, void* stream);
 
+/* ---- K10/K11/K14: per-head q / k RMSNorm + rotary embedding + KV-cache append (QK-norm decoders: Qwen3) ----------
+ * icl_rope_kv_gqa_bf16 with an RMSNorm over head_dim on every q head row and every k head row in front of the rotation; the
+ * contract is that call's in everything the two share (in-place q / k, the append of k and v to
+ * [n_seqs][n_kv_heads][max_len][head_dim], caches NULL together, disjoint column blocks).  head_dim 64 or 128;
+ * q_gamma / k_gamma f32 [head_dim], shared by all heads; eps > 0.  For a head row x (bf16) of q or k:
+ *     ss   = sum_i x[i]^2 in f32: each of the head_dim / 8 lanes of the row adds its eight squares in element order, the
+ *            partial sums are folded by an xor butterfly over lane distances 1, 2, .. head_dim / 16
+ *     r    = rsqrtf(ss * (1 / head_dim) + eps)
+ *     n[i] = bf16_rne((x[i] * r) * gamma[i])            gamma = q_gamma for q rows, k_gamma for k rows
+ * and n goes through rope_rot8 exactly as icl_rope_kv_gqa_bf16 rotates a buffer holding n (non-contracted IEEE arithmetic:
+ * that stage is bit-defined).  One bf16 rounding point sits between the norm and the rotation, where a bf16 execution of the
+ * HF module rounds too.  An all-zero row gives zeros; the domain is |x| <= 2^60.  v is copied to the cache untouched.
+ * Replaces Qwen3Attention's q_norm / k_norm (Qwen3RMSNorm over head_dim) + apply_rotary_pos_emb + DynamicCache.update of
+ * transformers, reached from models/custom_salmon.py:630-636 / :704-720.
+ */
+int icl_qknorm_rope_kv_bf16(void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* q_gamma,
+                            const float* k_gamma, float eps, const float* cos, const float* sin, const int32_t* pos,
+                            const int32_t* seq_ids, void* kcache, void* vcache, int32_t M, int32_t n_heads,
+                            int32_t n_kv_heads, int32_t head_dim, int32_t max_len, void* stream);
+
 /* ---- K10/K11: QKV projection with RoPE + KV-cache append fused into its epilogue -----------
  * icl_gemm_bf16(args) followed by icl_rope_kv_bf16 on its output, as ONE kernel: the 256x256 tile
  * stages its bf16 C tile through LDS, and with head_dim = 128 a tile is two whole heads of q, k or
