@@ -55,7 +55,7 @@ class QwenAudioRuntime(CausalLMRuntimeMixin):
                                        _f32(_take(sd, "multi_modal_projector.linear.bias", consume), self.device), cfg.llm.hidden)
         self.llama = LlamaHIP(pack_llama(sd, cfg.llm, self.device, prefix="language_model.", consume=consume), self.device,
                               weight_dtype=llm_weight_dtype)
-        self._graphs, self._graph_warm, self._graph_gen = {}, set(), 0
+        self._graph_reset()
 
     # ---- K13 ---------------------------------------------------------------------------------------
     def encode_audio(self, input_features: Optional[torch.Tensor] = None, mel_lens: Optional[Sequence[int]] = None,

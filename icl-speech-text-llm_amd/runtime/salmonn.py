@@ -39,6 +39,27 @@ class GenerateResult:
     #                                                 token among the candidates it was chosen from (0 after a row's EOS)
 
 
+def _undrop(sub: GenerateResult, keep: List[int], bad: List[int], n: int, pad: int) -> GenerateResult:
+    """``overlong="drop"``: the result of the kept rows scattered back to ``n`` rows; a dropped row's tokens are pad, its logits
+    and log-probabilities NaN."""
+    def spread(x, dim, fill):
+        if x is None:
+            return None
+        shape = list(x.shape)
+        shape[dim] = n
+        out = torch.full(shape, fill, dtype=x.dtype, device=x.device)
+        out[(slice(None),) * dim + (torch.tensor(keep).to(x.device),)] = x
+        return out
+    nan = float("nan")
+    return GenerateResult(tokens=spread(sub.tokens, 0, pad), first_logits=spread(sub.first_logits, 0, nan),
+                          step_logits=spread(sub.step_logits, 1, nan), dropped=tuple(bad),
+                          token_logprobs=spread(sub.token_logprobs, 0, nan))
+
+
+def _is_speech(seg) -> bool:
+    return isinstance(seg, tuple) and len(seg) == 3 and seg[0] == "speech"
+
+
 class CausalLMRuntimeMixin:
     """K9-K12 over a packed decoder (`self.llama`: LlamaHIP, `self.lm_cfg`: LlamaCfg, `self.ws`, `self.device`):
     prompt segments -> gather/interleave -> prefill -> greedy decode / teacher-forced logits.  Shared by the SALMONN
@@ -57,7 +78,7 @@ class CausalLMRuntimeMixin:
         for segs in prompts:
             before = len(flat)
             for seg in segs:
-                if isinstance(seg, tuple) and len(seg) == 3 and seg[0] == "speech":
+                if _is_speech(seg):
                     _, first, cnt = seg
                     if first < 0 or first + cnt > n_speech_rows:
                         raise ValueError(f"speech segment [{first},{first + cnt}) outside {n_speech_rows} speech rows")
@@ -76,8 +97,7 @@ class CausalLMRuntimeMixin:
     @staticmethod
     def _prompt_lengths(prompts: Sequence[Sequence[Segment]]) -> List[int]:
         """Positions per prompt (host arithmetic only; the validation of ``generate`` runs before anything is launched)."""
-        return [sum(seg[2] if (isinstance(seg, tuple) and len(seg) == 3 and seg[0] == "speech") else len(seg) for seg in segs)
-                for segs in prompts]
+        return [sum(seg[2] if _is_speech(seg) else len(seg) for seg in segs) for segs in prompts]
 
     def embed_prompts(self, prompts, speech: Optional[torch.Tensor], name: str = "ll_h"):
         rows = 0 if speech is None else speech.shape[0] * (speech.shape[1] if speech.dim() == 3 else 1)
@@ -103,27 +123,112 @@ class CausalLMRuntimeMixin:
         B.cross_entropy(logits, shifted_labels.to(device=self.device, dtype=I32), rows, mean)
         return mean
 
-    # --------------------------------------------------------------------------------------------
-    # K10 + K11: greedy generate
-    # --------------------------------------------------------------------------------------------
+    # ---- K10 + K11: generate — first the pieces that the greedy / sampled / constrained search and beam search share ----
     MAX_GRAPHS = 16            # captured decode graphs kept (one per batch shape / cache length / knob set); oldest dropped
+    prefill_chunk = int(os.environ.get("ICL_PREFILL_CHUNK", "128"))   # sequences per prefill pass (``_prefill_logits``)
+    beam_rows = 256            # decode rows (sequences x beams) per pass of beam search: the widest decode tile
 
     def _cache(self, n_seqs: int, max_len: int) -> KVCache:
         """K/V views over the workspace's one K and one V allocation (they grow to the largest n_seqs x max_len seen; a
         move bumps ``ws.generation``, which retires every captured graph)."""
         return KVCache(self.lm_cfg, n_seqs, max_len, self.ws, dtype=self.kv_dtype)
 
-    prefill_chunk = int(os.environ.get("ICL_PREFILL_CHUNK", "128"))   # sequences per prefill pass of generate() (see there)
+    def _cache_len(self, lens: List[int], max_new_tokens: int, multiple: int) -> int:
+        need = max(lens) + max_new_tokens
+        max_len = -(-need // multiple) * multiple
+        assert max_len <= self.lm_cfg.max_pos, f"prompt + new tokens ({need}) exceeds max_pos {self.lm_cfg.max_pos}"  # validated
+        return max_len
 
-    def _graph_lookup(self, gkey):
-        """(captured graph | None, warm?) for this key, after retiring everything captured or warmed under an older
-        workspace generation: a graph bakes raw pointers into workspace buffers and must not outlive a reallocation."""
-        gen = self.ws.generation
-        if self._graph_gen != gen:
-            self._graphs.clear()
-            self._graph_warm.clear()
-            self._graph_gen = gen
-        return self._graphs.get(gkey), gkey in self._graph_warm
+    def _prefill_logits(self, h, lens: List[int], cache: KVCache, last) -> torch.Tensor:
+        """Prefill in chunks of at most ``prefill_chunk`` sequences (the caller decodes ALL of them together: the decode GEMMs
+        stream the weights once per step whatever the row count — 256 rows cost 0.84 us each against 1.06 at 128 — while the
+        prefill GEMMs measured 1.3 % faster per utterance at 128 sequences than at 256; a sequence's arithmetic does not depend
+        on its neighbours in either phase, so the split changes no result).  Only the last position of every prompt is read
+        afterwards: the prefill writes those rows into ``last`` f32 [n, hidden] and trims its last layer to them
+        (LlamaHIP.prefill, last_rows_only).  Returns their logits, f32 [n, vocab]."""
+        r0 = 0
+        for b0 in range(0, len(lens), self.prefill_chunk):
+            b1 = min(len(lens), b0 + self.prefill_chunk)
+            r1 = r0 + sum(lens[b0:b1])
+            self.llama.prefill(self.ws, h[r0:r1], lens[b0:b1], cache.rows(b0, b1), last_rows_only=True, last_out=last[b0:b1])
+            r0 = r1
+        return self.llama.logits(self.ws, last, name="gen_logits")
+
+    def _step_tables(self, lens: List[int], steps: int):
+        """(position of the fed token, cache length after its append, sequence id) of every decode row — ``lens`` = its
+        prompt length — for each of ``steps`` decode steps: static buffers, so a captured graph can replay over them."""
+        ws, n = self.ws, len(lens)
+        pos_all, len_all, sid = ws.get("gen_pos", (steps, n), I32), ws.get("gen_len", (steps, n), I32), ws.get("gen_sid", (n,), I32)
+        pos_all.copy_(torch.tensor([[s + t for s in lens] for t in range(steps)], dtype=I32), non_blocking=True)
+        len_all.copy_(torch.tensor([[s + t + 1 for s in lens] for t in range(steps)], dtype=I32), non_blocking=True)
+        sid.copy_(torch.arange(n, dtype=I32), non_blocking=True)
+        return pos_all, len_all, sid
+
+    def _graph_reset(self) -> None:
+        """No captured decode graph and no warm key, as of the workspace's current generation."""
+        self._graphs, self._graph_warm, self._graph_gen = {}, set(), self.ws.generation
+
+    def _run_decode(self, gkey, decode_loop) -> None:
+        """Enqueue ``decode_loop()``.  It is launch-bound at small batch (~17 kernels x layers x steps), so with ``use_graphs``
+        a key's first call runs it eagerly (which sizes every workspace buffer), the second captures it into a HIP graph and
+        replays that, later ones replay — all pointers are workspace-stable and nothing inside synchronises or allocates.  A
+        graph bakes raw pointers into workspace buffers: a move (``ws.generation``) retires every graph and warm key."""
+        if not self.use_graphs:
+            return decode_loop()
+        if self._graph_gen != self.ws.generation:
+            self._graph_reset()
+        graph = self._graphs.get(gkey)
+        if graph is None and gkey not in self._graph_warm:
+            decode_loop()
+            if self._graph_gen != self.ws.generation:                # the eager pass may have grown buffers
+                self._graph_reset()
+            self._graph_warm.add(gkey)
+            return
+        if graph is None:
+            graph = torch.cuda.CUDAGraph()
+            torch.cuda.synchronize()
+            prof, B.GEMM_PROFILE = B.GEMM_PROFILE, None              # no timing events inside a stream capture
+            try:
+                with torch.cuda.graph(graph):
+                    decode_loop()
+            finally:
+                B.GEMM_PROFILE = prof
+            while len(self._graphs) >= self.MAX_GRAPHS:
+                self._graphs.pop(next(iter(self._graphs)))
+            self._graphs[gkey] = graph
+        graph.replay()
+
+    def _decode_tail(self, state, max_new_tokens: int, eos, pad: int, constraint, knobs, do_sample: bool, generator,
+                     sample_debug):
+        """``(tail, graph-key element, token log-probs | None)``: ``tail(logits, step)`` picks every row's token of one step
+        into ``state`` = (finished, tokens, next ids) — ``icl_argmax_fsm`` with a ``constraint``, the sampling kernel with
+        ``knobs`` = (temperature, top_k, top_p, repetition_penalty), else plain argmax.  Sets up the buffers only: every
+        argument was validated by ``generate``."""
+        c, ws = self.lm_cfg, self.ws
+        finished, toks, nxt = state
+        Bn = toks.shape[0]
+        if constraint is not None:
+            # the automaton's tables are uploaded once and kept; the rows' states restart from their start states on every call
+            # (outside the captured decode loop, like ``finished``), and the upload's id keys the graph
+            tables = constraint[0].upload(self.device)
+            fsm_state = ws.get("gen_fsm_state", (Bn,), I32)
+            fsm_state.copy_(torch.tensor(constraint[1], dtype=I32), non_blocking=True)
+            lps = ws.get("gen_token_logprobs", (Bn, max_new_tokens), F32)
+            return (lambda lg, step: B.argmax_fsm(lg, tables, fsm_state, max_new_tokens - step, eos, pad, finished, toks, step, nxt,
+                                                  out_logprob=lps, V=c.vocab)), ("fsm", tables.uid), lps
+        if knobs is None:
+            return (lambda lg, step: B.argmax_eos(lg, eos, pad, finished, toks, step, nxt, V=c.vocab)), None, None
+        uni = ws.get("gen_uniform", (max_new_tokens, Bn), F32)
+        if do_sample and generator is not None and generator.device.type != uni.device.type:
+            uni.copy_(torch.rand(uni.shape, generator=generator))      # a host generator: draw there, same stream of uniforms
+        elif do_sample:
+            uni.uniform_(0.0, 1.0, generator=generator)
+        else:
+            uni.zero_()
+        work = ws.get("gen_sample_work", (Bn, c.vocab), F32)
+        return (lambda lg, step: B.sample_eos(lg, work, uni[step], eos, pad, finished, toks, step, nxt, temperature=knobs[0],
+                                              top_k=knobs[1], top_p=knobs[2], repetition_penalty=knobs[3], V=c.vocab,
+                                              debug=sample_debug if step == 0 else None)), knobs, None
 
     def generate(self, prompts, speech: Optional[torch.Tensor], max_new_tokens: int = 10, eos_id: Optional[int] = None,
                  pad_id: Optional[int] = None, suppress_eos: bool = False, want_first_logits: bool = False,
@@ -156,7 +261,9 @@ class CausalLMRuntimeMixin:
         and decode step are the unconstrained ones.  Greedy only: sampling, a repetition penalty, beams and ``suppress_eos``
         together with a constraint, a ``max_new_tokens`` below a row's shortest answer, and a start-state list of the wrong
         length are ``ValueError``s raised before anything is launched."""
-        c, ws, dev = self.lm_cfg, self.ws, self.device
+        args = {k: v for k, v in locals().items() if k not in ("self", "prompts", "speech")}   # the keyword arguments, as given
+        c, ws = self.lm_cfg, self.ws
+        # ---- 1. validate: every caller error is raised here, before anything is launched
         if overlong not in ("raise", "drop"):
             raise ValueError(f"overlong must be 'raise' or 'drop', not {overlong!r}")
         if constraint is not None:
@@ -168,100 +275,24 @@ class CausalLMRuntimeMixin:
         if bad and (overlong == "raise" or len(bad) == len(plens)):
             raise ValueError(f"prompt + new tokens of row(s) {bad} ({[plens[b] + max_new_tokens for b in bad]} positions) "
                              f"exceed max_pos {c.max_pos}")
-        if bad:
-            keep = [b for b in range(len(plens)) if b not in set(bad)]
-            sub = self.generate([prompts[b] for b in keep], speech, max_new_tokens=max_new_tokens, eos_id=eos_id, pad_id=pad_id,
-                                suppress_eos=suppress_eos, want_first_logits=want_first_logits,
-                                cache_len_multiple=cache_len_multiple, do_sample=do_sample, temperature=temperature, top_p=top_p,
-                                top_k=top_k, repetition_penalty=repetition_penalty, generator=generator,
-                                sample_debug=sample_debug, want_step_logits=want_step_logits, num_beams=num_beams,
-                                length_penalty=length_penalty,
-                                constraint=None if constraint is None else (constraint[0], [constraint[1][b] for b in keep]))
-            n, kidx = len(plens), torch.tensor(keep)
-            toks = torch.full((n, sub.tokens.shape[1]), c.pad_id if pad_id is None else pad_id, dtype=torch.int64)
-            toks[kidx] = sub.tokens
-            first = steps = None
-            if sub.first_logits is not None:
-                first = torch.full((n, sub.first_logits.shape[1]), float("nan"), dtype=F32, device=dev)
-                first[kidx.to(dev)] = sub.first_logits
-            if sub.step_logits is not None:
-                steps = torch.full((sub.step_logits.shape[0], n, sub.step_logits.shape[2]), float("nan"), dtype=F32, device=dev)
-                steps[:, kidx.to(dev)] = sub.step_logits
-            lps = None
-            if sub.token_logprobs is not None:
-                lps = torch.full((n, sub.token_logprobs.shape[1]), float("nan"), dtype=F32)
-                lps[kidx] = sub.token_logprobs
-            return GenerateResult(tokens=toks, first_logits=first, step_logits=steps, dropped=tuple(bad), token_logprobs=lps)
         eos = c.eos_id if eos_id is None else eos_id            # an id, or HF's list form (one or two ids: binding._eos_pair)
         eos = tuple(int(e) for e in eos) if isinstance(eos, (tuple, list)) else int(eos)
         pad = c.pad_id if pad_id is None else pad_id
         if suppress_eos:
             eos = -1  # benchmark mode: exactly max_new_tokens per row
         assert max_new_tokens >= 1
+        knobs = None
         if num_beams != 1:
             if num_beams < 1:
                 raise ValueError(f"num_beams must be >= 1, not {num_beams}")
             if do_sample or want_step_logits:
                 raise NotImplementedError("beam search runs without sampling (HF's beam-sample mode) and without a per-step logits trace")
-            if num_beams > 8 or max_new_tokens > 64:      # the step kernel's state (include/icl_hip.h); refused before any launch
+            if num_beams > 8 or max_new_tokens > 64:      # the step kernel's state (include/icl_hip.h)
                 raise ValueError(f"beam search supports num_beams <= 8 and max_new_tokens <= 64 (got {num_beams}, {max_new_tokens})")
-            return self._generate_beam(prompts, speech, max_new_tokens, eos, pad, num_beams, float(length_penalty),
-                                       want_first_logits, cache_len_multiple, debug=beam_debug,
-                                       repetition_penalty=float(repetition_penalty))
-        h, lens = self.embed_prompts(prompts, speech)
-        Bn = len(lens)
-        need = max(lens) + max_new_tokens
-        max_len = -(-need // cache_len_multiple) * cache_len_multiple
-        assert max_len <= c.max_pos, f"prompt + new tokens ({need}) exceeds max_pos {c.max_pos}"   # validated above
-        cache = self._cache(Bn, max_len)
-        marks = getattr(self, "phase_marks", None)     # optional {name: torch.cuda.Event}: bench.py times prefill / decode with it
-        if marks is not None:
-            marks["prefill_start"].record()
-        # Prefill in chunks of at most ``prefill_chunk`` sequences, decode ALL of them together: the decode GEMMs stream the
-        # weights once per step whatever the row count (256 rows cost 0.84 us each against 1.06 at 128), while the prefill
-        # GEMMs measured 1.3 % faster per utterance at 128 sequences than at 256.  A sequence's arithmetic does not depend on
-        # its neighbours in either phase, so the split changes no result.
-        # Only the last position of every prompt is read from here on (final norm, LM head; decode reads the K/V cache): the
-        # prefill writes those rows into ``gen_last`` and trims its last layer to them (LlamaHIP.prefill, last_rows_only).
-        last = ws.get("gen_last", (Bn, c.hidden), F32)
-        if Bn <= self.prefill_chunk:
-            self.llama.prefill(ws, h, lens, cache, last_rows_only=True, last_out=last)
-        else:
-            r0 = 0
-            for b0 in range(0, Bn, self.prefill_chunk):
-                b1 = min(Bn, b0 + self.prefill_chunk)
-                r1 = r0 + sum(lens[b0:b1])
-                self.llama.prefill(ws, h[r0:r1], lens[b0:b1], cache.rows(b0, b1), last_rows_only=True, last_out=last[b0:b1])
-                r0 = r1
-        logits = self.llama.logits(ws, last, name="gen_logits")
-        first = logits.clone() if want_first_logits else None
-        trace = ws.get("gen_logits_trace", (max_new_tokens, Bn, c.vocab), F32) if want_step_logits else None
-        if trace is not None:
-            trace[0].copy_(logits)
-        if marks is not None:
-            marks["prefill_end"].record()
-        finished = ws.get("gen_finished", (Bn,), I32)
-        finished.zero_()
-        toks = ws.get("gen_tokens", (Bn, max_new_tokens), I32)
-        nxt = ws.get("gen_next", (Bn,), I32)
-        sampled = do_sample or repetition_penalty != 1.0
-        lps = None
-        if constraint is not None:
-            # the automaton's tables are uploaded once and kept; the rows' states restart from their start states on every call
-            # (outside the captured decode loop, like ``finished``), and the upload's id keys the graph below
-            tables = constraint[0].upload(dev)
-            fsm_state = ws.get("gen_fsm_state", (Bn,), I32)
-            fsm_state.copy_(torch.tensor(constraint[1], dtype=I32), non_blocking=True)
-            lps = ws.get("gen_token_logprobs", (Bn, max_new_tokens), F32)
-            knobs = ("fsm", tables.uid)
-
-            def tail(lg, step):
-                B.argmax_fsm(lg, tables, fsm_state, max_new_tokens - step, eos, pad, finished, toks, step, nxt, out_logprob=lps,
-                             V=c.vocab)
-        elif sampled:
+        elif do_sample or repetition_penalty != 1.0:
             # HF's TopKLogitsWarper clamps top_k to the vocabulary; 0 / None switch it off.  The kernel takes 1..SAMPLE_TOP_K_MAX, or
             # the vocabulary size for "off" (full-row normalisation, nucleus over the 1024 most likely tokens); anything else is
-            # a caller's argument error and is refused HERE, before a launch — never as a device-side failure
+            # a caller's argument error, never a device-side failure
             top_k = c.vocab if not top_k else min(int(top_k), c.vocab)
             if top_k < 1 or B.SAMPLE_TOP_K_MAX < top_k < c.vocab:
                 raise ValueError(f"top_k={top_k}: the sampling kernel supports 1..{B.SAMPLE_TOP_K_MAX}, or 0 / None / >= vocabulary "
@@ -270,34 +301,43 @@ class CausalLMRuntimeMixin:
                 raise ValueError(f"sampling knobs out of range: temperature={temperature} (> 0), top_p={top_p} (0 < p <= 1), "
                                  f"repetition_penalty={repetition_penalty} (> 0)")
             knobs = ((float(temperature), top_k, float(top_p)) if do_sample else (1.0, 1, 1.0)) + (float(repetition_penalty),)
-            uni = ws.get("gen_uniform", (max_new_tokens, Bn), F32)
-            if do_sample and generator is not None and generator.device.type != uni.device.type:
-                uni.copy_(torch.rand(uni.shape, generator=generator))      # a host generator: draw there, same stream of uniforms
-            elif do_sample:
-                uni.uniform_(0.0, 1.0, generator=generator)
-            else:
-                uni.zero_()
-            work = ws.get("gen_sample_work", (Bn, logits.shape[1]), F32)
-
-            def tail(lg, step):
-                B.sample_eos(lg, work, uni[step], eos, pad, finished, toks, step, nxt, temperature=knobs[0], top_k=knobs[1],
-                             top_p=knobs[2], repetition_penalty=knobs[3], V=c.vocab,
-                             debug=sample_debug if step == 0 else None)
-        else:
-            knobs = None
-
-            def tail(lg, step):
-                B.argmax_eos(lg, eos, pad, finished, toks, step, nxt, V=c.vocab)
+        # ---- 2. drop over-long rows: the same call over the rows that fit
+        if bad:
+            keep = [b for b in range(len(plens)) if b not in set(bad)]
+            if constraint is not None:
+                args["constraint"] = (constraint[0], [constraint[1][b] for b in keep])
+            return _undrop(self.generate([prompts[b] for b in keep], speech, **args), keep, bad, len(plens), pad)
+        # ---- 3. beams
+        if num_beams != 1:
+            return self._generate_beam(prompts, speech, max_new_tokens, eos, pad, num_beams, float(length_penalty),
+                                       want_first_logits, cache_len_multiple, debug=beam_debug,
+                                       repetition_penalty=float(repetition_penalty))
+        # ---- 4. prefill
+        h, lens = self.embed_prompts(prompts, speech)
+        Bn = len(lens)
+        max_len = self._cache_len(lens, max_new_tokens, cache_len_multiple)
+        cache = self._cache(Bn, max_len)
+        marks = getattr(self, "phase_marks", None)     # optional {name: torch.cuda.Event}: bench.py times prefill / decode with it
+        if marks is not None:
+            marks["prefill_start"].record()
+        logits = self._prefill_logits(h, lens, cache, ws.get("gen_last", (Bn, c.hidden), F32))
+        first = logits.clone() if want_first_logits else None
+        trace = ws.get("gen_logits_trace", (max_new_tokens, Bn, c.vocab), F32) if want_step_logits else None
+        if trace is not None:
+            trace[0].copy_(logits)
+        if marks is not None:
+            marks["prefill_end"].record()
+        # ---- 5. the tail of every step, 6. step 0 (on the prefill's logits)
+        finished, nxt = ws.get("gen_finished", (Bn,), I32), ws.get("gen_next", (Bn,), I32)
+        toks = ws.get("gen_tokens", (Bn, max_new_tokens), I32)
+        finished.zero_()
+        tail, tail_key, lps = self._decode_tail((finished, toks, nxt), max_new_tokens, eos, pad, constraint, knobs, do_sample,
+                                                generator, sample_debug)
         tail(logits, 0)
-        if max_new_tokens > 1:
-            steps = max_new_tokens - 1
-            # positions of the fed token / cache length after its append, per step: static buffers (graph-replayable)
-            pos_all = ws.get("gen_pos", (steps, Bn), I32)
-            len_all = ws.get("gen_len", (steps, Bn), I32)
-            sid = ws.get("gen_sid", (Bn,), I32)
-            pos_all.copy_(torch.tensor([[s + t for s in lens] for t in range(steps)], dtype=I32), non_blocking=True)
-            len_all.copy_(torch.tensor([[s + t + 1 for s in lens] for t in range(steps)], dtype=I32), non_blocking=True)
-            sid.copy_(torch.arange(Bn, dtype=I32), non_blocking=True)
+        # ---- 7. the decode steps
+        steps = max_new_tokens - 1
+        if steps:
+            pos_all, len_all, sid = self._step_tables(lens, steps)
 
             def decode_loop():
                 for t in range(steps):
@@ -305,35 +345,11 @@ class CausalLMRuntimeMixin:
                     if trace is not None:
                         trace[t + 1].copy_(lg)
                     tail(lg, t + 1)
-
-            # The decode loop is launch-bound at small batch (~17 kernels x layers x steps): after one eager pass that
-            # sizes every workspace buffer, it is captured ONCE per (batch, cache length, steps, eos, pad) into a HIP
-            # graph and replayed — all pointers are workspace-stable and nothing inside synchronises or allocates.
-            gkey = (Bn, max_len, steps, eos, pad, knobs, trace is not None, self.kv_dtype)
-            graph, warm = self._graph_lookup(gkey) if self.use_graphs else (None, False)
-            if graph is not None:
-                graph.replay()
-            elif warm:
-                g = torch.cuda.CUDAGraph()
-                torch.cuda.synchronize()
-                prof, B.GEMM_PROFILE = B.GEMM_PROFILE, None      # no timing events inside a stream capture
-                try:
-                    with torch.cuda.graph(g):
-                        decode_loop()
-                finally:
-                    B.GEMM_PROFILE = prof
-                while len(self._graphs) >= self.MAX_GRAPHS:
-                    self._graphs.pop(next(iter(self._graphs)))
-                self._graphs[gkey] = g
-                g.replay()
-            else:
-                decode_loop()
-                if self.use_graphs:
-                    self._graph_lookup(gkey)                     # the eager pass may have grown buffers: re-sync first
-                    self._graph_warm.add(gkey)
+            self._run_decode((Bn, max_len, steps, eos, pad, tail_key, trace is not None, self.kv_dtype), decode_loop)
         if marks is not None:
             marks["decode_end"].record()
-        out = toks.cpu().to(torch.int64)                                # the only D2H of the call (two with a constraint)
+        # ---- 8. collect: the first host sync of the call, and its only D2H (two with a constraint)
+        out = toks.cpu().to(torch.int64)
         width = max_new_tokens
         if B._eos_pair(eos)[0] >= 0:
             is_eos = torch.isin(out, torch.tensor([e for e in B._eos_pair(eos) if e >= 0]))
@@ -371,9 +387,6 @@ class CausalLMRuntimeMixin:
                              f"({[automaton.min_tokens(starts[b]) for b in short[:8]]} tokens): no complete label fits")
         return automaton, starts
 
-
-    beam_rows = 256            # decode rows (sequences x beams) per pass of beam search: the widest decode tile
-
     def _generate_beam(self, prompts, speech, max_new_tokens: int, eos: int, pad: int, K: int, length_penalty: float,
                        want_first_logits: bool, cache_len_multiple: int, debug: Optional[dict] = None,
                        repetition_penalty: float = 1.0) -> GenerateResult:
@@ -386,7 +399,7 @@ class CausalLMRuntimeMixin:
         rows whose search has ended keep stepping with their finished slots frozen (HF stops its loop instead: same result).
         ``debug`` (tests; single pass only): receives per step the logits the step scored, and the running sequences / parents /
         tokens it chose."""
-        c, ws, dev = self.lm_cfg, self.ws, self.device
+        c, ws = self.lm_cfg, self.ws
         n_rows = len(prompts)
         per_pass = max(1, self.beam_rows // K)
         if n_rows > per_pass:                                  # rows x beams beyond the decode tile: run the rows in groups
@@ -405,19 +418,10 @@ class CausalLMRuntimeMixin:
         h, lens = self.embed_prompts(prompts, speech)
         Bn, T = len(lens), max_new_tokens
         BK = Bn * K
-        need = max(lens) + T
-        max_len = -(-need // cache_len_multiple) * cache_len_multiple
-        assert max_len <= c.max_pos, f"prompt + new tokens ({need}) exceeds max_pos {c.max_pos}"   # validated by generate()
-        whole = self._cache(BK + Bn, max_len)                  # beams' sequences first, then the rows the prompts prefill into
+        # the beams' sequences first, then the rows the prompts prefill into
+        whole = self._cache(BK + Bn, self._cache_len(lens, T, cache_len_multiple))
         cache, pre = whole.rows(0, BK), whole.rows(BK, BK + Bn)
-        last = ws.get("gen_last", (Bn, c.hidden), F32)
-        r0 = 0
-        for b0 in range(0, Bn, self.prefill_chunk):
-            b1 = min(Bn, b0 + self.prefill_chunk)
-            r1 = r0 + sum(lens[b0:b1])
-            self.llama.prefill(ws, h[r0:r1], lens[b0:b1], pre.rows(b0, b1), last_rows_only=True, last_out=last[b0:b1])
-            r0 = r1
-        logits = self.llama.logits(ws, last, name="gen_logits")
+        logits = self._prefill_logits(h, lens, pre, ws.get("gen_last", (Bn, c.hidden), F32))
         first = logits.clone() if want_first_logits else None
         st = B.BeamState(ws.get, Bn, K, T, pad)
 
@@ -437,12 +441,7 @@ class CausalLMRuntimeMixin:
             for kv, sc in whole.planes():
                 B.kv_copy_spans(kv, kv, BK, src_seq=src, n_t=plen, src_scale=sc, dst_scale=sc)
             steps = T - 1
-            pos_all = ws.get("gen_pos", (steps, BK), I32)
-            len_all = ws.get("gen_len", (steps, BK), I32)
-            sid = ws.get("gen_sid", (BK,), I32)
-            pos_all.copy_(torch.tensor([[s + t for s in lens_rep] for t in range(steps)], dtype=I32), non_blocking=True)
-            len_all.copy_(torch.tensor([[s + t + 1 for s in lens_rep] for t in range(steps)], dtype=I32), non_blocking=True)
-            sid.copy_(torch.arange(BK, dtype=I32), non_blocking=True)
+            pos_all, len_all, sid = self._step_tables(lens_rep, steps)
             tmp_k = ws.get("beam_tmp_k", (c.n_layers, BK, c.kv_heads, steps, c.head_dim), cache.k.dtype)
             tmp_v = ws.get("beam_tmp_v", tuple(tmp_k.shape), cache.k.dtype)
             tmp_ks = tmp_vs = None
@@ -490,7 +489,7 @@ class SalmonnRuntime(CausalLMRuntimeMixin):
         if "llama" in parts:
             self.llama = LlamaHIP(pack_llama(sd, cfg.llama, self.device, consume=consume), self.device,
                                   weight_dtype=llm_weight_dtype)
-        self._graphs, self._graph_warm, self._graph_gen = {}, set(), 0
+        self._graph_reset()
 
     # --------------------------------------------------------------------------------------------
     # K1-K8: SALMONN.encode_speech

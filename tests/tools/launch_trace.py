@@ -7,12 +7,18 @@ recorder, and reduces what it saw to one sha256 per (config, weight mode, KV dty
 engines.py with the same digests make the same calls with the same operands in the same order — bit-identical results and
 the same device time by construction.  tests/test_launch_trace.py compares against tests/golden/llama_launch_trace.json.
 
+A second matrix pins the generation driver one level up (runtime/salmonn.py: ``generate`` with every decode tail, chunked
+prefill, ``overlong="drop"`` and beam search): one sha256 per case in tests/golden/generate_launch_trace.json.  Besides the
+launches, a generate trace holds the torch plumbing between them (every in-place op or ``clone`` on a device tensor, host
+tables by value), where the three ``phase_marks`` are recorded, and the shape of the result.
+
 Nothing is computed: the weights are ``torch.empty`` tensors on the ``meta`` device (real 7B dims cost no memory).  The only
 library entry point reached is icl_gemm_select_tile (``binding.rope_fusable``), which needs the built library but no GPU.
+The one device-to-host copy at the end of ``generate`` reads zeros (``Tensor.cpu`` of a ``meta`` tensor, inside the tool only).
 
-    python tests/tools/launch_trace.py                 compare with the fixture, list the groups that differ
-    python tests/tools/launch_trace.py --write         regenerate the fixture
-    python tests/tools/launch_trace.py --dump DIR      also write the full text of every case, one file per group
+    python tests/tools/launch_trace.py                 compare with both fixtures, list the groups / cases that differ
+    python tests/tools/launch_trace.py --write         regenerate both fixtures
+    python tests/tools/launch_trace.py --dump DIR      also write the full text of every case, one file per group / generate case
     python tests/tools/launch_trace.py --root TREE     trace TREE's package instead of this tree's (another checkout of the
                                                        repository; ICL_LIB_PATH names the built library if TREE has none)
 
@@ -23,17 +29,20 @@ from __future__ import annotations
 import argparse
 import contextlib
 import hashlib
+import importlib
 import inspect
 import json
 import os
 import sys
-from dataclasses import replace
+from dataclasses import fields, replace
 
 import torch
+from torch.utils._python_dispatch import TorchDispatchMode
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "llama_launch_trace.json")
+GEN_FIXTURE = os.path.join(ROOT, "tests", "golden", "generate_launch_trace.json")
 
 NOT_LAUNCHES = ("load_library", "rope_epilogue_ok", "rope_fusable", "device_cu_count")
 RETURNS_OUT = ("gemm", "gemm_rmsnorm", "gather_rows")        # wrappers whose result is their ``out`` operand
@@ -141,9 +150,15 @@ class Recorder:
             return repr(float(x))
         if isinstance(x, (tuple, list)):
             return "(" + ", ".join(self.enc(v) for v in x) + ")"
+        if isinstance(x, torch.Generator):
+            return "generator"
+        if type(x).__name__ in ("BeamState", "DeviceTables"):      # by their fields; uid is a process-global counter
+            return type(x).__name__ + "{" + ", ".join(f"{k}={self.enc(v)}" for k, v in sorted(vars(x).items()) if k != "uid") + "}"
         if isinstance(x, torch.Tensor):
             if id(x) in self.host_index:
                 return "i32" + repr(self.host_index[id(x)][0]).replace(" ", "")
+            if x.device.type != "meta":                            # a host table: by value
+                return f"host:{str(x.dtype).replace('torch.', '')}{x.tolist()!r}".replace(" ", "")
             st = x.untyped_storage()
             ordinal = self.storages.setdefault(st._cdata, (len(self.storages), st))[0]
             return (f"T{ordinal}:{str(x.dtype).replace('torch.', '')}{list(x.shape)}/{list(x.stride())}+{x.storage_offset()}"
@@ -158,9 +173,13 @@ class Recorder:
 
 @contextlib.contextmanager
 def recording(rec: Recorder):
-    """Every launching wrapper of runtime.binding appends (name, bound arguments) to ``rec.log``; ``engines._i32`` remembers the
-    values it was given, so index tensors built on the host are recorded by value."""
+    """Every launching wrapper of runtime.binding appends (name, bound arguments) to ``rec.log``; ``_i32`` (engines', under
+    every runtime module that holds the name) remembers the values it was given, so index tensors built on the host are
+    recorded by value."""
     B, _, E, _ = _modules()
+    pkg = E.__name__.rsplit(".", 1)[0]
+    importlib.import_module(pkg + ".salmonn")
+    holders = [m for n, m in sorted(sys.modules.items()) if n.startswith(pkg + ".") and "_i32" in vars(m)]
     names = [n for n, f in vars(B).items() if inspect.isfunction(f) and f.__module__ == B.__name__ and not n.startswith("_")
              and n not in NOT_LAUNCHES]
     saved = {n: getattr(B, n) for n in names}
@@ -185,12 +204,14 @@ def recording(rec: Recorder):
     try:
         for n, f in saved.items():
             setattr(B, n, wrapper(n, f))
-        E._i32 = i32
+        for m in holders:
+            m._i32 = i32
         yield rec
     finally:
         for n, f in saved.items():
             setattr(B, n, f)
-        E._i32 = real_i32
+        for m in holders:
+            m._i32 = real_i32
 
 
 def traced_workspace(rec: Recorder):
@@ -205,6 +226,10 @@ def traced_workspace(rec: Recorder):
             key = (name, dtype, bool(zero), shape[1:])
             rec.requests[key] = max(rec.requests.get(key, 0), numel)
             return super().get(name, shape, dtype, zero=zero)
+
+        def release(self, *names):
+            rec.log.append("ws.release(" + ", ".join(names) + ")")
+            super().release(*names)
     return TracedWorkspace("meta")
 
 
@@ -255,8 +280,141 @@ def digests(dump_dir=None):
     return out
 
 
-def load_fixture():
-    with open(FIXTURE) as f:
+# ---- the generation driver under trace --------------------------------------------------------------------------------------
+GEN_LENS = (5, 9, 7, 4, 6)                                   # prompt lengths, in positions
+
+
+class Plumbing(TorchDispatchMode):
+    """Logs every in-place aten op and every ``clone`` whose first argument is a ``meta`` tensor (zero_, fill_, copy_, uniform_,
+    index_put_, ...): what generate() does to device buffers between the launches."""
+
+    def __init__(self, rec: Recorder):
+        super().__init__()
+        self.rec = rec
+
+    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        name = func._schema.name.split("::")[1]
+        if (name.endswith("_") or name == "clone") and args and isinstance(args[0], torch.Tensor) and args[0].device.type == "meta":
+            enc = [self.rec.enc(a) for a in args] + [f"{k}={self.rec.enc(v)}" for k, v in sorted(kwargs.items())]
+            self.rec.log.append(f"torch.{name}(" + ", ".join(enc) + ")")
+        return func(*args, **kwargs)
+
+
+class Mark:
+    """Stands in for a torch.cuda.Event of ``phase_marks``."""
+
+    def __init__(self, rec: Recorder, name: str):
+        self.rec, self.name = rec, name
+
+    def record(self):
+        self.rec.log.append(f"mark {self.name}")
+
+
+@contextlib.contextmanager
+def meta_cpu_reads_zeros():
+    had, real = "cpu" in vars(torch.Tensor), torch.Tensor.cpu
+
+    def cpu(self, *a, **kw):
+        return torch.zeros(self.shape, dtype=self.dtype) if self.device.type == "meta" else real(self, *a, **kw)
+    torch.Tensor.cpu = cpu
+    try:
+        yield
+    finally:
+        if had:
+            torch.Tensor.cpu = real
+        else:
+            del torch.Tensor.cpu
+
+
+@contextlib.contextmanager
+def generate_recording(rec: Recorder):
+    with recording(rec), meta_cpu_reads_zeros(), Plumbing(rec):
+        yield rec
+
+
+def prompts_of(lens=GEN_LENS):
+    return [[list(range(3 + b, 3 + b + n))] for b, n in enumerate(lens)]
+
+
+def _automaton():
+    """0 -10-> 1 -11-> 2, 0 -12-> 2, 2 accepting (EOS id 2)."""
+    from icl_speech_text_llm_amd.runtime.constraints import LabelAutomaton
+    return LabelAutomaton([0, 2, 3, 4], [10, 12, 11, 2], [1, 2, 2, 2], {}, 260, 2)
+
+
+# name -> (attributes set on the runtime, prompt lengths, keyword arguments of generate(); a callable is built per run)
+GEN_CASES = {
+    "greedy4": ({}, GEN_LENS, dict(max_new_tokens=4)),
+    "greedy1": ({}, GEN_LENS, dict(max_new_tokens=1)),
+    "chunk2": (dict(prefill_chunk=2), GEN_LENS, dict(max_new_tokens=4)),
+    "chunk5": (dict(prefill_chunk=5), GEN_LENS, dict(max_new_tokens=4)),
+    "eos_pair_pad": ({}, GEN_LENS, dict(max_new_tokens=4, eos_id=[2, 7], pad_id=5)),
+    "suppress_eos": ({}, GEN_LENS, dict(max_new_tokens=4, suppress_eos=True)),
+    "first_and_step_logits": ({}, GEN_LENS, dict(max_new_tokens=4, want_first_logits=True, want_step_logits=True)),
+    "sample_seeded": ({}, GEN_LENS, dict(max_new_tokens=4, do_sample=True, top_k=5, top_p=0.9, temperature=0.7,
+                                         generator=lambda: torch.Generator().manual_seed(1234))),
+    "sample_global": ({}, GEN_LENS, dict(max_new_tokens=4, do_sample=True, top_k=5, top_p=0.9, temperature=0.7)),
+    "sample_top_k0": ({}, GEN_LENS, dict(max_new_tokens=4, do_sample=True, top_k=0, top_p=0.9, temperature=0.7)),
+    "repetition_penalty": ({}, GEN_LENS, dict(max_new_tokens=4, repetition_penalty=1.2)),
+    "constrained": ({}, GEN_LENS, dict(max_new_tokens=4, constraint=lambda: (_automaton(), [0, -1, 1, 0, -1]))),
+    "drop_overlong": ({}, (5, 9, 2167, 4, 6), dict(max_new_tokens=4, overlong="drop", want_first_logits=True)),
+    "speech_segment": ({}, GEN_LENS, dict(max_new_tokens=4)),
+    "beam3": ({}, GEN_LENS[:2], dict(max_new_tokens=3, num_beams=3)),
+    "beam3_three_passes": (dict(beam_rows=6), GEN_LENS, dict(max_new_tokens=3, num_beams=3)),
+    "beam3_repetition_penalty": ({}, GEN_LENS[:2], dict(max_new_tokens=3, num_beams=3, repetition_penalty=1.3)),
+}
+GEN_MATRIX = ([("tiny_h4", "bf16", name) for name in GEN_CASES]
+              + [(cname, kv, name) for cname, kv in (("tiny_h4", "fp8"), ("7b_gqa8_bias", "bf16")) for name in ("greedy4", "beam3")])
+
+
+def generate_runtime(cname: str, kv: str, rec: Recorder):
+    """A SalmonnRuntime over ``make_runtime``'s decoder and a traced workspace, on ``meta``, without graphs; its phase marks log."""
+    E = _modules()[2]
+    S = importlib.import_module(E.__name__.rsplit(".", 1)[0] + ".salmonn")
+    cfg = configs()[cname]
+    rt = object.__new__(S.SalmonnRuntime)
+    rt.lm_cfg, rt.llama, rt.ws, rt.device = cfg, make_runtime(cfg, "bf16", {}), traced_workspace(rec), torch.device("meta")
+    rt.use_graphs, rt.kv_dtype = False, kv
+    rt.phase_marks = {n: Mark(rec, n) for n in ("prefill_start", "prefill_end", "decode_end")}
+    return rt
+
+
+def run_generate(cname: str, kv: str, name: str) -> str:
+    """The canonical text of one generate() call: launches, plumbing and marks in order, workspace requests, the result."""
+    attrs, lens, kw = GEN_CASES[name]
+    kw = {k: v() if callable(v) else v for k, v in kw.items()}
+    rec = Recorder()
+    rt = generate_runtime(cname, kv, rec)
+    for k, v in attrs.items():
+        setattr(rt, k, v)
+    prompts, speech = prompts_of(lens), None
+    if name == "speech_segment":                                # row 0: two token ids, then speech rows 1..3
+        prompts[0], speech = [[3, 4], ("speech", 1, 3)], _e(1, 8, rt.lm_cfg.hidden, dtype=torch.float32)
+    with generate_recording(rec):
+        res = rt.generate(prompts, speech, **kw)
+    out = []
+    for f in fields(res):
+        v = getattr(res, f.name)
+        out.append(f"{f.name}=" + (f"{str(v.dtype).replace('torch.', '')}{list(v.shape)}@{v.device.type}" if isinstance(v, torch.Tensor)
+                                   else repr(v)))
+    rec.log.append("result " + " ".join(out))
+    return rec.text()
+
+
+def generate_digests(dump_dir=None):
+    out = {}
+    for case in GEN_MATRIX:
+        key, text = "/".join(case), run_generate(*case)
+        out[key] = hashlib.sha256(text.encode()).hexdigest()
+        if dump_dir is not None:
+            with open(os.path.join(dump_dir, "generate__" + key.replace("/", "__") + ".txt"), "w") as f:
+                f.write(text)
+    return out
+
+
+def load_fixture(path=FIXTURE):
+    with open(path) as f:
         return json.load(f)
 
 
@@ -272,20 +430,21 @@ def main(argv=None) -> int:
         return 2
     if a.dump:
         os.makedirs(a.dump, exist_ok=True)
-    got = digests(a.dump)
-    if a.write:
-        with open(FIXTURE, "w") as f:
-            json.dump(got, f, indent=1, sort_keys=True)
-            f.write("\n")
-        print(f"wrote {len(got)} digests")
-        return 0
-    want = load_fixture()
-    bad = sorted(k for k in set(got) | set(want) if got.get(k) != want.get(k))
-    for k in bad:
-        print("differs:", k)
-    print(f"{len(got) - len([k for k in bad if k in got])} of {len(got)} groups match")
+    bad = []
+    for what, path, got in (("groups", FIXTURE, digests(a.dump)), ("generate cases", GEN_FIXTURE, generate_digests(a.dump))):
+        if a.write:
+            with open(path, "w") as f:
+                json.dump(got, f, indent=1, sort_keys=True)
+                f.write("\n")
+            print(f"wrote {len(got)} digests ({what})")
+            continue
+        want = load_fixture(path)
+        differ = sorted(k for k in set(got) | set(want) if got.get(k) != want.get(k))
+        for k in differ:
+            print("differs:", k)
+        print(f"{len(got) - len([k for k in differ if k in got])} of {len(got)} {what} match")
+        bad += differ
     return 1 if bad else 0
-
 
 if __name__ == "__main__":
     sys.exit(main())
