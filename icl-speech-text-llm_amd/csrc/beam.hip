@@ -1,5 +1,5 @@
 // beam.hip — beam search bookkeeping on the device (gfx950): one step of HF's static-shaped beam search per launch, and the
-// K/V-cache span copy that stands in for HF's cache.reorder_cache.
+// K/V-cache span copies (bf16 cache, FP8 cache) that stand in for HF's cache.reorder_cache.
 //
 // Reference call site: models/custom_salmon.py:704-715 forwards num_beams / length_penalty to HF generate(inputs_embeds=...),
 // models/multi_task_model.py:142 sets them per task.  The algorithm restated here is transformers/generation/utils.py
@@ -218,6 +218,23 @@ __global__ __launch_bounds__(256) void beam_step_kernel(
   }
 }
 
+// Span r of a K/V-cache copy: n positions from st0 of sequence ss to dt0 of sequence ds.  Sequence ids and span starts come from
+// device state (the beam step's parent array): they are clamped to the arrays the caller described, so a corrupted id reads /
+// writes a wrong but EXISTING span — never memory outside the allocation.
+struct KvSpan {
+  int ss, ds, st0, dt0, n;
+};
+__device__ __forceinline__ KvSpan kv_span(int r, const int* src_seq, const int* src_t0, const int* dst_seq, const int* dst_t0,
+                                          const int* n_t, int n_fixed, int src_n_seqs, int dst_n_seqs, int src_len, int dst_len) {
+  KvSpan s;
+  s.ss = min(max(src_seq ? src_seq[r] : r, 0), src_n_seqs - 1);
+  s.ds = min(max(dst_seq ? dst_seq[r] : r, 0), dst_n_seqs - 1);
+  s.st0 = min(max(src_t0 ? src_t0[r] : 0, 0), src_len);
+  s.dt0 = min(max(dst_t0 ? dst_t0[r] : 0, 0), dst_len);
+  s.n = min(min(max(n_t ? n_t[r] : n_fixed, 0), src_len - s.st0), dst_len - s.dt0);
+  return s;
+}
+
 // Copy a span of positions of one (sequence, head) stream to another, for every layer and head: 16 B per thread.
 __global__ __launch_bounds__(256) void kv_copy_spans_kernel(
     const unsigned short* __restrict__ src, unsigned short* __restrict__ dst, int64_t s_layer, int64_t s_seq, int64_t s_head,
@@ -225,19 +242,32 @@ __global__ __launch_bounds__(256) void kv_copy_spans_kernel(
     const int* __restrict__ dst_seq, const int* __restrict__ dst_t0, const int* __restrict__ n_t, int n_fixed, int H, int D,
     int src_n_seqs, int dst_n_seqs, int src_len, int dst_len) {
   const int r = blockIdx.x / H, h = blockIdx.x % H, l = blockIdx.y;
-  // sequence ids and span starts come from device state (the beam step's parent array): they are clamped to the arrays the
-  // caller described, so a corrupted id reads / writes a wrong but EXISTING span — never memory outside the allocation
-  const int ss = min(max(src_seq ? src_seq[r] : r, 0), src_n_seqs - 1);
-  const int ds = min(max(dst_seq ? dst_seq[r] : r, 0), dst_n_seqs - 1);
-  const int st0 = min(max(src_t0 ? src_t0[r] : 0, 0), src_len);
-  const int dt0 = min(max(dst_t0 ? dst_t0[r] : 0, 0), dst_len);
-  const int n = min(min(max(n_t ? n_t[r] : n_fixed, 0), src_len - st0), dst_len - dt0);
-  const int64_t so = (int64_t)l * s_layer + (int64_t)ss * s_seq + (int64_t)h * s_head + (int64_t)st0 * D;
-  const int64_t dof = (int64_t)l * d_layer + (int64_t)ds * d_seq + (int64_t)h * d_head + (int64_t)dt0 * D;
+  const KvSpan s = kv_span(r, src_seq, src_t0, dst_seq, dst_t0, n_t, n_fixed, src_n_seqs, dst_n_seqs, src_len, dst_len);
+  const int64_t so = (int64_t)l * s_layer + (int64_t)s.ss * s_seq + (int64_t)h * s_head + (int64_t)s.st0 * D;
+  const int64_t dof = (int64_t)l * d_layer + (int64_t)s.ds * d_seq + (int64_t)h * d_head + (int64_t)s.dt0 * D;
   const u32x4* sp = (const u32x4*)(src + so);
   u32x4* dp = (u32x4*)(dst + dof);
-  const int chunks = n * D / 8;
+  const int chunks = s.n * D / 8;
   for (int i = threadIdx.x; i < chunks; i += 256) dp[i] = sp[i];
+}
+
+// The same for the two planes of an FP8 cache (include/icl_hip.h, "FP8 KV cache": a cache row is head_dim e4m3fn bytes, its f32
+// scale sits in a plane of its own, scale[seq][head][pos]): 16 B of row bytes and then one scale per thread.
+__global__ __launch_bounds__(256) void kv_copy_spans_fp8_kernel(
+    const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, const float* __restrict__ ssrc, float* __restrict__ sdst,
+    int64_t s_layer, int64_t s_seq, int64_t s_head, int64_t d_layer, int64_t d_seq, int64_t d_head, int64_t ss_layer, int64_t ss_seq,
+    int64_t ss_head, int64_t sd_layer, int64_t sd_seq, int64_t sd_head, const int* __restrict__ src_seq,
+    const int* __restrict__ src_t0, const int* __restrict__ dst_seq, const int* __restrict__ dst_t0, const int* __restrict__ n_t,
+    int n_fixed, int H, int D, int src_n_seqs, int dst_n_seqs, int src_len, int dst_len) {
+  const int r = blockIdx.x / H, h = blockIdx.x % H, l = blockIdx.y;
+  const KvSpan s = kv_span(r, src_seq, src_t0, dst_seq, dst_t0, n_t, n_fixed, src_n_seqs, dst_n_seqs, src_len, dst_len);
+  const u32x4* sp = (const u32x4*)(src + l * s_layer + s.ss * s_seq + h * s_head + (int64_t)s.st0 * D);
+  u32x4* dp = (u32x4*)(dst + l * d_layer + s.ds * d_seq + h * d_head + (int64_t)s.dt0 * D);
+  const int chunks = s.n * D / 16;
+  for (int i = threadIdx.x; i < chunks; i += 256) dp[i] = sp[i];
+  const float* ssp = ssrc + l * ss_layer + s.ss * ss_seq + h * ss_head + s.st0;
+  float* sdp = sdst + l * sd_layer + s.ds * sd_seq + h * sd_head + s.dt0;
+  for (int i = threadIdx.x; i < s.n; i += 256) sdp[i] = ssp[i];
 }
 
 }  // namespace
@@ -292,5 +322,36 @@ extern "C" int icl_kv_copy_spans_bf16(const void* src, void* dst, int64_t src_la
                      dst_layer_stride, dst_seq_stride, dst_head_stride, src_seq, src_t0, dst_seq, dst_t0, n_t, n_fixed, n_heads,
                      head_dim, src_n_seqs, dst_n_seqs, src_len, dst_len);
   ICL_CHECK_LAUNCH("icl_kv_copy_spans_bf16");
+  return ICL_OK;
+}
+
+extern "C" int icl_kv_copy_spans_fp8(const void* src, const float* src_scale, void* dst, float* dst_scale, int64_t src_layer_stride,
+                                     int64_t src_seq_stride, int64_t src_head_stride, int64_t dst_layer_stride, int64_t dst_seq_stride,
+                                     int64_t dst_head_stride, int64_t src_scale_layer_stride, int64_t src_scale_seq_stride,
+                                     int64_t src_scale_head_stride, int64_t dst_scale_layer_stride, int64_t dst_scale_seq_stride,
+                                     int64_t dst_scale_head_stride, const int32_t* src_seq, const int32_t* src_t0,
+                                     const int32_t* dst_seq, const int32_t* dst_t0, const int32_t* n_t, int32_t n_fixed, int32_t n_rows,
+                                     int32_t n_layers, int32_t n_heads, int32_t head_dim, int32_t src_n_seqs, int32_t dst_n_seqs,
+                                     int32_t src_len, int32_t dst_len, void* stream) {
+  ICL_CHECK_ARG(src && dst && src_scale && dst_scale, "icl_kv_copy_spans_fp8: NULL pointer");
+  ICL_CHECK_ARG(src_n_seqs > 0 && dst_n_seqs > 0 && src_len > 0 && dst_len > 0,
+                "icl_kv_copy_spans_fp8: src / dst extents (sequences, positions) must be > 0");
+  ICL_CHECK_ARG((src_seq || n_rows <= src_n_seqs) && (dst_seq || n_rows <= dst_n_seqs),
+                "icl_kv_copy_spans_fp8: n_rows=%d exceeds the %d / %d sequences of src / dst", n_rows, src_n_seqs, dst_n_seqs);
+  ICL_CHECK_ARG(n_rows > 0 && n_layers > 0 && n_heads > 0 && head_dim > 0 && head_dim % 16 == 0,
+                "icl_kv_copy_spans_fp8: bad sizes (head_dim must be a multiple of 16)");
+  ICL_CHECK_ARG(n_t || n_fixed >= 0, "icl_kv_copy_spans_fp8: n_fixed < 0");
+  ICL_CHECK_ARG(((uintptr_t)src | (uintptr_t)dst) % 16 == 0 &&
+                    (src_layer_stride | src_seq_stride | src_head_stride | dst_layer_stride | dst_seq_stride | dst_head_stride) % 16 == 0,
+                "icl_kv_copy_spans_fp8: byte planes and their strides must be 16-byte aligned");
+  ICL_CHECK_ARG(((uintptr_t)src_scale | (uintptr_t)dst_scale) % 4 == 0, "icl_kv_copy_spans_fp8: scale planes misaligned");
+  ICL_CHECK_ARG((int64_t)n_rows * n_heads < 0x7fffffffLL && n_layers <= 65535, "icl_kv_copy_spans_fp8: grid too large");
+  if (!n_t && n_fixed == 0) return ICL_OK;
+  hipLaunchKernelGGL(kv_copy_spans_fp8_kernel, dim3(n_rows * n_heads, n_layers), dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned char*)src, (unsigned char*)dst, src_scale, dst_scale, src_layer_stride, src_seq_stride,
+                     src_head_stride, dst_layer_stride, dst_seq_stride, dst_head_stride, src_scale_layer_stride, src_scale_seq_stride,
+                     src_scale_head_stride, dst_scale_layer_stride, dst_scale_seq_stride, dst_scale_head_stride, src_seq, src_t0,
+                     dst_seq, dst_t0, n_t, n_fixed, n_heads, head_dim, src_n_seqs, dst_n_seqs, src_len, dst_len);
+  ICL_CHECK_LAUNCH("icl_kv_copy_spans_fp8");
   return ICL_OK;
 }

@@ -65,7 +65,7 @@ __device__ __forceinline__ void rope_rot8(u32x4 lo, u32x4 hi, f32x4 c0, f32x4 c1
     ohi[j] = pack_bf16x2(__fadd_rn(__fmul_rn(b0, cA), __fmul_rn(a0, sA)), __fadd_rn(__fmul_rn(b1, cB), __fmul_rn(a1, sB)));
   }
 }
-// FP8 rounding rule shared by the weight packer (gemm_decode.hip) and the FP8 KV cache (kv_fp8.hip): the smallest e with
+// FP8 rounding rule shared by the weight packer (gemm_decode.hip) and the FP8 KV cache (rope_kv.hip, attn_decode.hip): the smallest e with
 // m <= 448 * 2^e (0 for m = 0), and RNE into OCP e4m3fn of a value |x| <= 448.
 __device__ __forceinline__ int fp8_row_exponent(float m) {
   if (m == 0.f) return 0;

@@ -1,79 +1,10 @@
-// elementwise.hip — HBM-bound glue kernels of the ICL path (gfx950): RoPE + KV append, embedding
-// gather/interleave, greedy argmax + EOS bookkeeping, LoRA down-projection, BEATs gate, the
-// window-level Q-Former cross attention and a generic axpby/cast.  All loads/stores are 8-16 B
-// per lane (Guideline 13); none of these is reshaped into a GEMM.
+// elementwise.hip — HBM-bound glue kernels of the ICL path (gfx950): embedding gather/interleave,
+// greedy argmax + EOS bookkeeping, LoRA down-projection, BEATs gate, the window-level Q-Former
+// cross attention and a generic axpby/cast.  All loads/stores are 8-16 B per lane (Guideline 13);
+// none of these is reshaped into a GEMM.
 #include "common.h"
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------
-// RoPE (HF rotate_half pairing) in place on q,k of a fused QKV row + KV-cache append.
-// One block per row; work items of 8 elements (16 B).
-__global__ __launch_bounds__(256) void rope_kv_kernel(unsigned short* qkv, int64_t ld, int64_t k_off,
-                                                       int64_t v_off, const float* cosT,
-                                                       const float* sinT, const int* pos,
-                                                       const int* seq_ids, unsigned short* kc,
-                                                       unsigned short* vc, int H, int Hkv, int D, int max_len) {
-  // H query heads; Hkv heads in the k / v blocks and in the cache (grouped-query attention: Hkv < H, icl_rope_kv_gqa_bf16)
-  const int64_t m = blockIdx.x;
-  const int p = pos[m];
-  const int half = D >> 1;
-  const int per_head = half >> 3;          // 8-element items per (tensor, head)
-  const int q_items = H * per_head;
-  const int rope_items = q_items + Hkv * per_head; // q and k
-  unsigned short* row = qkv + m * ld;
-  const int64_t cache_row = kc ? ((int64_t)seq_ids[m] * Hkv) * max_len + p : 0;
-  // Two rope items and two V items per thread per pass, ALL loads issued before the first use: with one small block per
-  // row the kernel is latency-bound on bytes in flight per thread (2.8 TB/s with the loads interleaved with their uses).
-  constexpr int U = 2;
-  const int v_items = vc ? Hkv * (D >> 3) : 0;
-  for (int base = threadIdx.x; base < rope_items || base < v_items; base += U * blockDim.x) {
-    u32x4 lo[U], hi[U], vv[U];
-    f32x4 c0[U], c1[U], s0[U], s1[U];
-    unsigned short* rb[U];
-    int i0s[U], hs[U], whichs[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int it = base + u * blockDim.x;
-      if (it < rope_items) {
-        const int which = it >= q_items;                // 0 = q, 1 = k
-        const int rem = it - which * q_items;
-        const int h = rem / per_head, i0 = (rem - h * per_head) * 8;
-        unsigned short* bp = row + (which ? k_off : 0) + h * D;
-        rb[u] = bp; i0s[u] = i0; hs[u] = h; whichs[u] = which;
-        lo[u] = *(const u32x4*)(bp + i0);
-        hi[u] = *(const u32x4*)(bp + i0 + half);
-        c0[u] = *(const f32x4*)(cosT + (int64_t)p * half + i0);
-        c1[u] = *(const f32x4*)(cosT + (int64_t)p * half + i0 + 4);
-        s0[u] = *(const f32x4*)(sinT + (int64_t)p * half + i0);
-        s1[u] = *(const f32x4*)(sinT + (int64_t)p * half + i0 + 4);
-      }
-      if (it < v_items) {
-        const int h = it / (D >> 3), i0 = (it - h * (D >> 3)) * 8;
-        vv[u] = *(const u32x4*)(row + v_off + h * D + i0);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int it = base + u * blockDim.x;
-      if (it < rope_items) {
-        u32x4 olo, ohi;
-        rope_rot8(lo[u], hi[u], c0[u], c1[u], s0[u], s1[u], olo, ohi);
-        *(u32x4*)(rb[u] + i0s[u]) = olo;
-        *(u32x4*)(rb[u] + i0s[u] + half) = ohi;
-        if (whichs[u] == 1 && kc) {
-          unsigned short* dst = kc + (cache_row + (int64_t)hs[u] * max_len) * D;
-          *(u32x4*)(dst + i0s[u]) = olo;
-          *(u32x4*)(dst + i0s[u] + half) = ohi;
-        }
-      }
-      if (it < v_items) {
-        const int h = it / (D >> 3), i0 = (it - h * (D >> 3)) * 8;
-        *(u32x4*)(vc + (cache_row + (int64_t)h * max_len) * D + i0) = vv[u];
-      }
-    }
-  }
-}
 
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void embed_gather_kernel(const int* src_idx, const unsigned short* table,
@@ -288,48 +219,6 @@ __global__ __launch_bounds__(256) void qformer_xattn_kernel(const unsigned short
 }
 
 }  // namespace
-
-static int rope_kv_launch(void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* cosT, const float* sinT,
-                          const int32_t* pos, const int32_t* seq_ids, void* kcache, void* vcache, int32_t M, int32_t n_heads,
-                          int32_t n_kv_heads, int32_t head_dim, int32_t max_len, void* stream) {
-  ICL_CHECK_ARG(qkv && cosT && sinT && pos, "icl_rope_kv_bf16: NULL pointer");
-  ICL_CHECK_ARG(M > 0 && n_heads > 0, "icl_rope_kv_bf16: M and n_heads must be > 0");
-  ICL_CHECK_ARG(head_dim % 16 == 0 && head_dim >= 16, "icl_rope_kv_bf16: head_dim=%d must be a multiple of 16", head_dim);
-  ICL_CHECK_ARG(ld % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0 && ((uintptr_t)qkv & 15) == 0,
-                "icl_rope_kv_bf16: qkv must be 16-byte aligned with ld/k_off/v_off multiples of 8");
-  ICL_CHECK_ARG(((uintptr_t)cosT & 15) == 0 && ((uintptr_t)sinT & 15) == 0, "icl_rope_kv_bf16: cos/sin misaligned");
-  ICL_CHECK_ARG((kcache == nullptr) == (vcache == nullptr), "icl_rope_kv_bf16: kcache and vcache must both be set or both NULL");
-  if (kcache) {
-    ICL_CHECK_ARG(seq_ids && max_len > 0, "icl_rope_kv_bf16: cache append needs seq_ids and max_len");
-    ICL_CHECK_ARG(((uintptr_t)kcache & 15) == 0 && ((uintptr_t)vcache & 15) == 0, "icl_rope_kv_bf16: cache misaligned");
-  }
-  hipLaunchKernelGGL(rope_kv_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, (unsigned short*)qkv, ld,
-                     k_off, v_off, cosT, sinT, pos, seq_ids, (unsigned short*)kcache,
-                     (unsigned short*)vcache, n_heads, n_kv_heads, head_dim, max_len);
-  ICL_CHECK_LAUNCH("icl_rope_kv_bf16");
-  return ICL_OK;
-}
-
-extern "C" int icl_rope_kv_bf16(void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* cosT,
-                                const float* sinT, const int32_t* pos, const int32_t* seq_ids,
-                                void* kcache, void* vcache, int32_t M, int32_t n_heads, int32_t head_dim,
-                                int32_t max_len, void* stream) {
-  return rope_kv_launch(qkv, ld, k_off, v_off, cosT, sinT, pos, seq_ids, kcache, vcache, M, n_heads, n_heads, head_dim, max_len,
-                        stream);
-}
-
-extern "C" int icl_rope_kv_gqa_bf16(void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* cosT,
-                                    const float* sinT, const int32_t* pos, const int32_t* seq_ids,
-                                    void* kcache, void* vcache, int32_t M, int32_t n_heads, int32_t n_kv_heads,
-                                    int32_t head_dim, int32_t max_len, void* stream) {
-  ICL_CHECK_ARG(n_heads > 0 && n_kv_heads > 0 && n_heads % n_kv_heads == 0,
-                "icl_rope_kv_gqa_bf16: n_heads=%d is not a multiple of n_kv_heads=%d", n_heads, n_kv_heads);
-  ICL_CHECK_ARG(k_off >= (int64_t)n_heads * head_dim && v_off >= k_off + (int64_t)n_kv_heads * head_dim &&
-                    ld >= v_off + (int64_t)n_kv_heads * head_dim,
-                "icl_rope_kv_gqa_bf16: the q | k | v column blocks must be disjoint inside a row");
-  return rope_kv_launch(qkv, ld, k_off, v_off, cosT, sinT, pos, seq_ids, kcache, vcache, M, n_heads, n_kv_heads, head_dim, max_len,
-                        stream);
-}
 
 extern "C" int icl_embed_gather_interleave(const int32_t* src_idx, const void* table, const float* speech,
                                            float* out, int32_t rows, int32_t H, int32_t vocab,

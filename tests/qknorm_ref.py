@@ -3,7 +3,7 @@
 QKNormOracle      LlamaOracle with the per-head q / k RMSNorm of Qwen3Attention between the projection and RoPE.
 qknorm_ref_bound  the float64 reference of the norm stage of icl_qknorm_rope_kv_bf16 and the bound of the kernel's f32 value.
 kernel_case       the inputs both test modules run the kernel (or its f32 emulation) on.
-qknorm_f32 / rope_f32 / emulate   a torch f32 emulation of the kernel in its own operation order (csrc/qk_norm.hip)."""
+qknorm_f32 / rope_f32 / emulate   a torch f32 emulation of the kernel in its own operation order (csrc/rope_kv.hip)."""
 from typing import Optional
 
 import torch
@@ -61,7 +61,7 @@ class QKNormOracle(om.LlamaOracle):
 def qknorm_ref_bound(x, gamma, eps):
     """(ref, e) of n = x rsqrt(mean(x^2) + eps) gamma over the last axis (length D = 64 or 128) as an f32 value, per element in
     float64.  x bf16 and gamma f32 are taken as data, eps is the f32 the C ABI passes.  With u = 2^-24 and the kernel's order
-    (csrc/qk_norm.hip):
+    (csrc/rope_kv.hip):
 
       * a bf16 square is exact in f32 (16 significant bits), so the sum of squares errs only in its additions.  A lane adds its
         eight squares in series (the first addition, to 0, is exact: 7 roundings); the D / 8 lane sums are folded by an xor
@@ -123,7 +123,7 @@ def rope_tables(D, max_len):
 
 # ---- f32 emulation of the kernel, in its order ------------------------------------------------------------------------------------
 def qknorm_f32(x, gamma, eps, *, use_eps=True, mean_over=None, gamma_by_chunk=False, round_bf16=True):
-    """The norm stage of qknorm_rope_kv_kernel on x [..., D] bf16 in f32: a lane's eight squares added in element order, the
+    """The norm stage of rope_kv_rows_kernel on x [..., D] bf16 in f32: a lane's eight squares added in element order, the
     xor butterfly over the D / 8 lanes, rsqrt(ss / D + eps), (x r) gamma, one bf16 rounding.  The keyword arguments are the
     one-mistake variants of test_qknorm.py."""
     D = x.shape[-1]

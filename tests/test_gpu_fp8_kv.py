@@ -94,7 +94,13 @@ def _check_appended(qkv, seq, pos, kq, vq, ks, vs, H, D, k_rows=None):
     assert bool((kq[untouched] == 0x55).all()) and bool((ks[untouched] == -1).all())
 
 
-@pytest.mark.parametrize("D,H", [(64, 4), (128, 2), (128, 32)])
+# (128, 11) and (64, 22): a ragged last pass of the two-head-rows-per-thread loop.  A pass is 32 head rows at head_dim 128 and 64 at
+# head_dim 64: the rotate form's 3 H = 33 / 66 items end in a second pass with one / two rows in slot 0 and slot 1 empty, the
+# append form's 2 H = 22 / 44 fill slot 1 of the only pass in part.
+DH_CASES = [(64, 4), (128, 2), (128, 32), (128, 11), (64, 22)]
+
+
+@pytest.mark.parametrize("D,H", DH_CASES)
 def test_prefill_append_bytes_and_scales_match_torch(D, H):
     B, qkv, seq, pos, kq, vq, ks, vs = _append_case(D, H, 37, 11, seed=D + H)
     B.kv_append_fp8(qkv, H * D, 2 * H * D, pos, seq, kq, vq, ks, vs, H, D, 11)
@@ -124,7 +130,7 @@ def test_edge_rows_bytes():
     assert torch.equal(kq[:, 0, 0], rb) and torch.equal(ks[:, 0, 0], rs) and torch.equal(vq, kq) and torch.equal(vs, ks)
 
 
-@pytest.mark.parametrize("D,H", [(64, 4), (128, 2), (128, 32)])
+@pytest.mark.parametrize("D,H", DH_CASES)
 def test_decode_rope_append_matches_torch_on_the_bf16_rotation(D, H):
     """icl_rope_kv_fp8: q rotated exactly as icl_rope_kv_bf16 rotates it, and the cache holds ref_q of the bf16-rotated k / v."""
     B, qkv, seq, pos, kq, vq, ks, vs = _append_case(D, H, 8, 16, seed=3 * D + H)
@@ -137,6 +143,31 @@ def test_decode_rope_append_matches_torch_on_the_bf16_rotation(D, H):
     B.rope_kv_fp8(qkv, hd, 2 * hd, cos, sin, pos, seq, kq, vq, ks, vs, H, D, T)
     assert torch.equal(qkv[:, :hd].view(torch.int16), ref[:, :hd].view(torch.int16))
     _check_appended(qkv, seq, pos, kq, vq, ks, vs, H, D, k_rows=ref.view(M, 3, H, D)[:, 1])
+
+
+def test_append_outside_the_cache_stores_nothing():
+    """icl_kv_append_fp8 at a position outside [0, max_len) stores nothing (the only form that reads no table at pos): rows at
+    positions -1 and max_len next to two rows that are appended, in planes with a slack sequence on either side, so that a
+    missing guard shows as a changed sentinel inside the allocation."""
+    B = _B()
+    M, H, D, T, n_seqs = 4, 2, 64, 4, 6
+    qkv = _rows((M, 3 * H * D), 41)
+    seq = torch.tensor([1, 2, 3, 4], dtype=torch.int32, device=DEV)
+    pos = torch.tensor([-1, T, 0, 3], dtype=torch.int32, device=DEV)
+    kq = torch.full((n_seqs, H, T, D), 0x55, dtype=torch.uint8, device=DEV)
+    vq = kq.clone()
+    ks = torch.full((n_seqs, H, T), -1.0, device=DEV)
+    vs = ks.clone()
+    B.kv_append_fp8(qkv, H * D, 2 * H * D, pos, seq, kq, vq, ks, vs, H, D, T)
+    written = torch.zeros(n_seqs, H, T, dtype=torch.bool, device=DEV)
+    for which, cq, cs in ((1, kq, ks), (2, vq, vs)):
+        rb, rs, _ = ref_q(qkv.view(M, 3, H, D)[:, which])
+        for m in (2, 3):
+            s, p = int(seq[m]), int(pos[m])
+            assert torch.equal(cq[s, :, p], rb[m]) and torch.equal(cs[s, :, p], rs[m]), (which, m)
+            written[s, :, p] = True
+        assert bool((cq[~written] == 0x55).all()) and bool((cs[~written] == -1).all()), which
+    assert int(written.sum()) == 2 * H
 
 
 def test_non_finite_rows_become_nan_and_stay_local():

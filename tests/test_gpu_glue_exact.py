@@ -1,4 +1,5 @@
-"""The glue kernels of csrc/elementwise.hip against float64, per element, at the shapes where their loops and launches change
+"""The glue kernels of csrc/elementwise.hip and rope_kv_kernel (csrc/rope_kv.hip) against float64, per element, at the shapes where
+their loops and launches change
 (`-m gpu`; every call goes through runtime/binding.py).  The bounds are the helpers of tests/fp64_bounds.py — each derived in
 its docstring, none fitted — and tests/test_glue_bounds.py shows on the CPU that an f32 emulation in the kernel's order passes
 them and that a kernel with one mistake does not.  bf16 outputs are judged by the interval check: out must lie in
