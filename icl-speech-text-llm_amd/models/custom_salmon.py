@@ -501,33 +501,46 @@ class CustomSALMONN(BaseModel):
     # ---- prompt wrap ------------------------------------------------------------------------------------
     def _segments(self, embeds, prompts: Sequence[str], num_examples, example_embeds):
         """Per-row segment lists for the K9 gather + the flat speech-row matrix they index."""
+        return self._segments_and_pieces(embeds, prompts, num_examples, example_embeds)[:2]
+
+    def _segments_and_pieces(self, embeds, prompts: Sequence[str], num_examples, example_embeds):
+        """``_segments`` plus, per row, the plan entry ``(kind, i)`` of every segment it emitted (an empty text part emits none):
+        piece p of a row IS segment p of its list, so the per-position piece ids (``piece_ids``) cannot disagree with the gather."""
         from ..runtime.salmonn import speech_segment
         max_examples = int(num_examples.max().item()) if num_examples is not None and len(num_examples) else 0
         speech_rows: List[torch.Tensor] = []
         n_rows = 0
-        all_segments = []
+        all_segments, all_pieces = [], []
         is_sqa = isinstance(embeds, tuple)
         for b, prompt in enumerate(prompts):
             parts = split_prompt(prompt, max_examples, example_embeds is not None, self.speech_placeholder, is_sqa=is_sqa)
             ids = [self.llama_tokenizer(p, padding="longest", return_tensors="pt", add_special_tokens=False)["input_ids"]
                    .reshape(-1).tolist() for p in parts]
             n_ex = len(example_embeds[b]) if (example_embeds is not None and b < len(example_embeds)) else None
-            segs = []
+            segs, pieces = [], []
             plan = (interleave_plan_sqa if is_sqa else interleave_plan)(len(parts), max_examples, n_ex, embeds is not None)
             for kind, i in plan:
                 if kind == "text":
                     if ids[i]:
                         segs.append(ids[i])
+                        pieces.append((kind, i))
                 else:
                     t = {"speech": lambda: embeds[b], "example": lambda: example_embeds[b][i],
                          "speech_q": lambda: embeds[0][b], "speech_d": lambda: embeds[1][b],
                          "example_q": lambda: example_embeds[b][i][0], "example_d": lambda: example_embeds[b][i][1]}[kind]()
                     speech_rows.append(t)
                     segs.append(speech_segment(n_rows, t.shape[0]))
+                    pieces.append((kind, i))
                     n_rows += t.shape[0]
             all_segments.append(segs)
+            all_pieces.append(pieces)
         speech = torch.cat(speech_rows, dim=0).to(device=self.device, dtype=torch.float32) if speech_rows else None
-        return all_segments, speech
+        return all_segments, speech, all_pieces
+
+    @staticmethod
+    def piece_ids(segs) -> List[int]:
+        """The piece of every position of one row's wrapped prompt: segment p of ``_segments`` covers its positions with id p."""
+        return [p for p, seg in enumerate(segs) for _ in range(seg[2] if isinstance(seg, tuple) else len(seg))]
 
     def custom_prompt_wrap(self, embeds, atts, prompts, num_examples=None, example_embeds=None, example_atts=None):
         segs, speech = self._segments(embeds, prompts, num_examples, example_embeds)
@@ -608,6 +621,26 @@ class CustomSALMONN(BaseModel):
         self.last_stage_seconds = {"speech_launch": t1 - t0, "segments": t2 - t1, "generate": time.perf_counter() - t2}
         self.batch_counter += 1
         return res
+
+    MAX_PIECES = 32        # segments the readout kernel sums (runtime.engines.MAX_READOUT_SEGMENTS): 14 non-SQA exemplars
+
+    def prompt_attention(self, samples: Dict[str, Any]) -> Dict[str, Any]:
+        """Where the last prompt position (the query that decides the first generated token) looks, per piece of the wrapped
+        prompt: ``{"mass": f32 [B, n_layers, n_heads, n_pieces] (CPU), "pieces": per row the list of (kind, i), "first_logits":
+        f32 [B, V] (device)}``.  A piece is one entry of ``interleave_plan`` / ``interleave_plan_sqa`` that the prompt wrap emits —
+        ``("text", i)``, ``("example", i)``, ``("speech", 0)`` or the SQA kinds; an empty text part emits nothing and gets no id —
+        and piece p of a row has id p; n_pieces is the largest row's count, a row with fewer pieces has exact zeros behind them.
+        ``first_logits`` are those of ``generate_ids(..., want_first_logits=True)``, bit for bit.  More than 32 pieces in a row
+        is a ``ValueError`` naming the row, raised before anything is launched on the decoder."""
+        samples = self._host_counts(samples)
+        speech_embeds, _, example_embeds, _ = self.get_speech_embeddings(samples)
+        num_examples = samples.get("num_examples", torch.zeros(len(samples["prompt"]), dtype=torch.long))
+        segs, speech, pieces = self._segments_and_pieces(speech_embeds, samples["prompt"], num_examples, example_embeds)
+        for b, pc in enumerate(pieces):
+            if len(pc) > self.MAX_PIECES:
+                raise ValueError(f"row {b}: {len(pc)} pieces in the wrapped prompt, the attention readout sums at most {self.MAX_PIECES}")
+        res = self.runtime.prompt_attention(segs, speech, [self.piece_ids(s) for s in segs], n_seg=max(len(pc) for pc in pieces))
+        return {"mass": res.mass, "pieces": pieces, "first_logits": res.first_logits}
 
     def _label_constraint(self, samples: Dict[str, Any]):
         """``(automaton, start states)`` for a batch that sets ``constrain_labels`` (one grammar per row, by its ``dataset_type``),

@@ -67,6 +67,8 @@ _SIGNATURES = {
                                      c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
     "icl_attn_decode_gqa_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                          c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "icl_attn_segmass_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
+                                      c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
     "icl_attn_decode_rope_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float,
                                           c_void_p]),
@@ -404,6 +406,28 @@ def attn_decode_gqa(q, kcache, vcache, out, lens, n_heads: int, n_kv_heads: int,
                                                    n_heads, n_kv_heads, head_dim, max_len, scale, _stream()),
            "icl_attn_decode_gqa_bf16")
     return out
+
+
+def attn_segmass(q, kcache, lens, seg, mass, n_heads: int, head_dim: int, max_len: int, scale: float, *, n_kv_heads: int = 0,
+                 q_rows=None, probs=None):
+    """The prompt-attention readout (icl_attn_segmass_bf16): the softmax weights of one query row per sequence over the K cache
+    [n_seqs, n_kv_heads, max_len, head_dim], summed per segment.  q: bf16 rows, already rotated — row ``q_rows[b]`` (int32; None:
+    row b) is sequence b's query; seg: uint8 [n_seqs, >= max_len], the segment of every key (>= n_seg: counted nowhere);
+    mass: f32 [n_seqs, n_heads, n_seg] (written); probs: None, or f32 [n_seqs, n_heads, >= max_len] (row b written up to lens[b])."""
+    _require_gpu(q, kcache, lens, seg, mass, q_rows, probs)
+    assert lens.dtype == torch.int32 and seg.dtype == torch.uint8 and mass.dtype == torch.float32 and q.dtype == torch.bfloat16
+    assert q_rows is None or q_rows.dtype == torch.int32
+    n_seqs = lens.numel()
+    assert seg.dim() == 2 and seg.shape[0] == n_seqs and seg.stride(1) == 1
+    assert mass.is_contiguous() and mass.dim() == 3 and mass.shape[0] == n_seqs and mass.shape[1] == n_heads
+    if probs is not None:
+        assert probs.dtype == torch.float32 and probs.dim() == 3 and tuple(probs.shape[:2]) == (n_seqs, n_heads)
+        assert probs.stride(2) == 1 and probs.stride(0) == n_heads * probs.stride(1)
+    _check(load_library().icl_attn_segmass_bf16(q.data_ptr(), q.stride(0), _ptr(q_rows), kcache.data_ptr(), lens.data_ptr(),
+                                                seg.data_ptr(), seg.stride(0), mass.shape[2], mass.data_ptr(), _ptr(probs),
+                                                probs.stride(1) if probs is not None else 0, n_seqs, n_heads, n_kv_heads,
+                                                head_dim, max_len, scale, _stream()), "icl_attn_segmass_bf16")
+    return mass
 
 
 def attn_decode_rope(qkv, k_off: int, v_off: int, cos, sin, pos, seq_ids, kcache, vcache, out, lens, n_heads: int,

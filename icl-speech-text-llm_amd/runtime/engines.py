@@ -608,8 +608,13 @@ class LlamaHIP:
 
     # ---- K10: prefill over ragged packed sequences ------------------------------------------------
     def prefill(self, ws: Workspace, h: torch.Tensor, seq_lens: List[int], cache: Optional["KVCache"] = None,
-                last_rows_only: bool = False, last_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                last_rows_only: bool = False, last_out: Optional[torch.Tensor] = None,
+                readout: Optional["AttnReadout"] = None) -> torch.Tensor:
         """h f32 [sum S_b, hidden] (modified in place) -> same buffer holding the final hidden states.
+
+        ``readout`` (needs ``last_rows_only`` and a bf16 cache): the prompt-attention readout.  In every layer, once q / k are
+        rotated and k is in the cache, one more launch (icl_attn_segmass_bf16) writes the last row's attention mass per key
+        segment into the layer's slice of ``readout``; nothing else changes, and without it the layers launch what they launch.
 
         ``last_rows_only`` (needs a cache): return only the final hidden state of the LAST row of every sequence, f32
         [len(seq_lens), hidden] (written into ``last_out`` when given) — what generation feeds to the final norm and the LM
@@ -624,6 +629,7 @@ class LlamaHIP:
             cu_h.append(cu_h[-1] + s)
         assert max(seq_lens) <= c.max_pos
         assert cache is not None or not last_rows_only, "prefill(last_rows_only=True) needs a KV cache"
+        assert readout is None or (last_rows_only and cache.dtype == "bf16"), "the attention readout reads the last rows' q and a bf16 K cache"
         pos = _i32([p for s in seq_lens for p in range(s)], dev)
         sid = _i32([b for b, s in enumerate(seq_lens) for _ in range(s)], dev)
         cu = _i32(cu_h, dev)
@@ -649,7 +655,8 @@ class LlamaHIP:
         for i, L in enumerate(w.layers):
             kc, vc, ks, vs = cache.layer(i) if cache is not None else (None, None, None, None)
             if trim and i == len(w.layers) - 1:
-                return self._last_layer_rows(ws, L, h, seq_lens, pos, sid, cu, kc, vc, max_len, last_idx, out)
+                return self._last_layer_rows(ws, L, h, seq_lens, pos, sid, cu, kc, vc, max_len, last_idx, out,
+                                             readout=None if readout is None else (readout, i))
             xn = self._xn(ws, L, h, M, "pf_", decode=False)
             qkv = ws.get("pf_qkv", (M, qkv_width(c)), BF16)
             att = ws.get("pf_att", (M, hd), BF16)
@@ -679,6 +686,8 @@ class LlamaHIP:
                 B.rope_kv(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, kc, vc, H, D, max_len, M=M)
             if fp8:
                 B.kv_append_fp8(qkv, k_off, v_off, pos, sid, kc, vc, ks, vs, H, D, max_len, M=M)
+            if readout is not None:     # the last rows of the QKV buffer are the queries; their keys are in the cache by now
+                readout.launch(i, qkv[:, :k_off], last_idx, kc, c, max_len)
             if in_cache:
                 B.attn_fwd(qkv[:, :hd], kc, vc, att, cu, maxS, H, D, D ** -0.5, causal=True, kv_cache_max_len=max_len)
             else:
@@ -688,7 +697,7 @@ class LlamaHIP:
         return B.gather_rows(h, last_idx, out) if last_rows_only else h
 
     def _last_layer_rows(self, ws: Workspace, L, h, seq_lens: List[int], pos, sid, cu, kc, vc, max_len: int,
-                         last_idx, hg) -> torch.Tensor:
+                         last_idx, hg, readout=None) -> torch.Tensor:
         """The last decoder layer of a prefill whose caller reads the last row of every sequence only: the layer's k / v are
         projected (and appended to the cache) for all M rows; q, the attention, o_proj, the post-attention norm and the MLP run
         on the len(seq_lens) gathered rows.  Exact, not approximate: every kernel here computes a row independently of its
@@ -713,6 +722,8 @@ class LlamaHIP:
         q = ws.get("pfl_q", (Bn, hd), BF16)
         B.gemm(xg, L.wqkv[:hd], q, bias=L.bqkv[:hd] if L.bqkv is not None else None, tile=3,
                rope=(hd, hd, *rope, _i32([s - 1 for s in seq_lens], dev), None, None, None, H, D, max_len))
+        if readout is not None:         # (AttnReadout, layer): the gathered rows' rotated q, one per sequence
+            readout[0].launch(readout[1], q, None, kc, c, max_len)
         att = ws.get("pfl_att", (Bn, hd), BF16)
         B.attn_fwd(q, kc, vc, att, cu, max(seq_lens), H, D, D ** -0.5, causal=True, kv_cache_max_len=max_len,
                    cu_q=_i32(list(range(Bn + 1)), dev))
@@ -786,6 +797,30 @@ class LlamaHIP:
             nxt = (layers[i + 1].rms1, xn_next) if i + 1 < len(layers) else (w.norm, xn_final)
             ready = self._attn_out_mlp(ws, L, h, xn, att, "dc_", sites, wsk, next_norm=nxt)
         return self.logits(ws, h, name="dc_logits", xn_ready=ready)
+
+
+MAX_READOUT_SEGMENTS = 32      # icl_attn_segmass_bf16: one thread per (head of a K/V group, segment)
+
+
+@dataclass
+class AttnReadout:
+    """Where ``LlamaHIP.prefill(readout=...)`` leaves the prompt-attention readout of its sequences, all on the device:
+    ``seg`` uint8 [n_seqs, >= cache max_len] the segment of every prompt position (>= n_seg: counted nowhere), ``lens`` int32
+    [n_seqs] the prompt lengths, ``mass`` f32 [n_layers, n_seqs, n_heads, n_seg] and ``probs`` None or f32 [n_layers, n_seqs,
+    n_heads, >= max_len] (written)."""
+    seg: torch.Tensor
+    lens: torch.Tensor
+    mass: torch.Tensor
+    probs: Optional[torch.Tensor] = None
+
+    def rows(self, b0: int, b1: int) -> "AttnReadout":
+        """The readout of sequences b0 .. b1-1 (views), for a prefill over that chunk of the batch (``KVCache.rows``)."""
+        return AttnReadout(self.seg[b0:b1], self.lens[b0:b1], self.mass[:, b0:b1],
+                           None if self.probs is None else self.probs[:, b0:b1])
+
+    def launch(self, layer: int, q: torch.Tensor, q_rows: Optional[torch.Tensor], kc: torch.Tensor, cfg, max_len: int) -> None:
+        B.attn_segmass(q, kc, self.lens, self.seg, self.mass[layer], cfg.n_heads, cfg.head_dim, max_len, cfg.head_dim ** -0.5,
+                       n_kv_heads=cfg.kv_heads, q_rows=q_rows, probs=None if self.probs is None else self.probs[layer])
 
 
 KV_DTYPES = ("bf16", "fp8")

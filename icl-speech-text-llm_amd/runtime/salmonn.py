@@ -18,7 +18,7 @@ import torch
 
 from . import binding as B
 from .config import SalmonnCfg
-from .engines import (BF16, F32, I32, BeatsHIP, KVCache, LlamaHIP, LogMel, SpeechQFormerHIP, WhisperEncoderHIP, Workspace, _i32,
+from .engines import (BF16, F32, I32, MAX_READOUT_SEGMENTS, AttnReadout, BeatsHIP, KVCache, LlamaHIP, LogMel, SpeechQFormerHIP, WhisperEncoderHIP, Workspace, _i32,
                       check_kv_dtype)
 from .packing import normalize_keys, pack_beats, pack_llama, pack_qformer, pack_whisper
 
@@ -37,6 +37,15 @@ class GenerateResult:
     dropped: Tuple[int, ...] = ()                # rows NOT generated (``overlong="drop"``): pad-filled tokens, NaN logits
     token_logprobs: Optional[torch.Tensor] = None   # f32 [B, width] on CPU, with a ``constraint`` only: log-probability of every
     #                                                 token among the candidates it was chosen from (0 after a row's EOS)
+
+
+@dataclass
+class PromptAttention:
+    """``prompt_attention``: where the prompt's last row — the query that decides the first generated token — looks."""
+    mass: torch.Tensor                  # f32 [B, n_layers, n_heads, n_seg] on CPU: attention mass per segment of the prompt
+    probs: Optional[torch.Tensor]       # None, or f32 [B, n_layers, n_heads, max_len] (device); row b is valid up to lens[b]
+    first_logits: torch.Tensor          # f32 [B, V] (device): generate(..., want_first_logits=True).first_logits, bit for bit
+    lens: List[int]                     # prompt lengths (positions)
 
 
 def _undrop(sub: GenerateResult, keep: List[int], bad: List[int], n: int, pad: int) -> GenerateResult:
@@ -139,7 +148,7 @@ class CausalLMRuntimeMixin:
         assert max_len <= self.lm_cfg.max_pos, f"prompt + new tokens ({need}) exceeds max_pos {self.lm_cfg.max_pos}"  # validated
         return max_len
 
-    def _prefill_logits(self, h, lens: List[int], cache: KVCache, last) -> torch.Tensor:
+    def _prefill_logits(self, h, lens: List[int], cache: KVCache, last, readout: Optional[AttnReadout] = None) -> torch.Tensor:
         """Prefill in chunks of at most ``prefill_chunk`` sequences (the caller decodes ALL of them together: the decode GEMMs
         stream the weights once per step whatever the row count — 256 rows cost 0.84 us each against 1.06 at 128 — while the
         prefill GEMMs measured 1.3 % faster per utterance at 128 sequences than at 256; a sequence's arithmetic does not depend
@@ -150,7 +159,8 @@ class CausalLMRuntimeMixin:
         for b0 in range(0, len(lens), self.prefill_chunk):
             b1 = min(len(lens), b0 + self.prefill_chunk)
             r1 = r0 + sum(lens[b0:b1])
-            self.llama.prefill(self.ws, h[r0:r1], lens[b0:b1], cache.rows(b0, b1), last_rows_only=True, last_out=last[b0:b1])
+            self.llama.prefill(self.ws, h[r0:r1], lens[b0:b1], cache.rows(b0, b1), last_rows_only=True, last_out=last[b0:b1],
+                               readout=None if readout is None else readout.rows(b0, b1))
             r0 = r1
         return self.llama.logits(self.ws, last, name="gen_logits")
 
@@ -358,6 +368,67 @@ class CausalLMRuntimeMixin:
         return GenerateResult(tokens=out[:, :width].contiguous(), first_logits=first,
                               step_logits=trace.clone() if trace is not None else None,
                               token_logprobs=lps.cpu()[:, :width].contiguous() if lps is not None else None)
+
+    # ---- the prompt-attention readout: generate()'s prefill plus one launch per layer ----
+    IGNORE_SEGMENT = 255       # a segment id that is counted nowhere, whatever n_seg is
+
+    def prompt_attention(self, prompts, speech: Optional[torch.Tensor], segments: Sequence[Sequence[int]],
+                         want_probs: bool = False, n_seg: Optional[int] = None, cache_len_multiple: int = 64) -> PromptAttention:
+        """Where the last prompt row (the query that decides the first generated token) looks: its attention mass in every
+        layer and head, summed over each segment of the prompt — what ``output_attentions=True`` of a transformers decoder gives
+        for that row, reduced per segment (``[B, n_layers, n_heads, n_seg]`` floats; the full last-row weights with
+        ``want_probs``).
+
+        ``segments``: one sequence of ints per prompt, as long as the prompt's positions: the segment (0 .. n_seg - 1) of every
+        position; an id >= n_seg (``IGNORE_SEGMENT``) is counted nowhere.  ``n_seg`` defaults to 1 + the largest id below
+        ``IGNORE_SEGMENT``; at most 32.
+
+        Runs the prefill ``generate`` runs (same kernels, same KV cache, last rows only, same chunks), with one more launch per
+        layer (icl_attn_segmass_bf16) between the K append and the attention, so ``first_logits`` are ``generate``'s bit for bit.
+        ``ValueError`` before any launch: the FP8 KV cache (its prefill attends to unrounded k, the cache does not hold what the
+        attention saw), a segment list of the wrong length, ids outside 0..255, more than 32 segments, a prompt over max_pos."""
+        c, ws = self.lm_cfg, self.ws
+        if self.kv_dtype != "bf16":
+            raise ValueError(f"prompt_attention needs the bf16 KV cache (llm_kv_dtype={self.kv_dtype!r}: the FP8 prefill attends to "
+                             "unrounded k / v, so the cache does not hold the keys the attention saw)")
+        plens = self._prompt_lengths(prompts)
+        if len(segments) != len(plens):
+            raise ValueError(f"{len(segments)} segment lists for {len(plens)} prompts")
+        rows = []
+        for b, (sg, n) in enumerate(zip(segments, plens)):
+            if len(sg) != n:
+                raise ValueError(f"segments[{b}] has {len(sg)} entries, the prompt of row {b} has {n} positions")
+            sg = torch.as_tensor(sg, dtype=torch.int64).reshape(-1)
+            if n and (int(sg.min()) < 0 or int(sg.max()) > 255):
+                raise ValueError(f"segments[{b}]: segment ids are 0..255 ({self.IGNORE_SEGMENT} = counted nowhere)")
+            rows.append(sg)
+        if n_seg is None:
+            n_seg = 1 + max(int(sg[sg < self.IGNORE_SEGMENT].max()) if bool((sg < self.IGNORE_SEGMENT).any()) else 0 for sg in rows)
+        if not 1 <= int(n_seg) <= MAX_READOUT_SEGMENTS:
+            raise ValueError(f"{n_seg} segments: the readout kernel sums at most {MAX_READOUT_SEGMENTS}")
+        n_seg = int(n_seg)
+        limit = c.max_pos // cache_len_multiple * cache_len_multiple
+        bad = [b for b, n in enumerate(plens) if n + 1 > limit]
+        if bad:
+            raise ValueError(f"prompt of row(s) {bad} ({[plens[b] for b in bad]} positions, + 1 for the cache) exceeds max_pos {c.max_pos}")
+        h, lens = self.embed_prompts(prompts, speech)
+        Bn = len(lens)
+        max_len = self._cache_len(lens, 1, cache_len_multiple)
+        cache = self._cache(Bn, max_len)
+        seg = torch.full((Bn, max_len), self.IGNORE_SEGMENT, dtype=torch.uint8)
+        for b, sg in enumerate(rows):
+            seg[b, :sg.numel()] = sg.to(torch.uint8)
+        seg_d = ws.get("pa_seg", (Bn, max_len), torch.uint8)
+        seg_d.copy_(seg, non_blocking=True)
+        mass = ws.get("pa_mass", (c.n_layers, Bn, c.n_heads, n_seg), F32)
+        probs = ws.get("pa_probs", (c.n_layers, Bn, c.n_heads, max_len), F32) if want_probs else None
+        if probs is not None:
+            probs.zero_()           # the kernel leaves a row's tail untouched
+        readout = AttnReadout(seg_d, _i32(lens, self.device), mass, probs)
+        logits = self._prefill_logits(h, lens, cache, ws.get("gen_last", (Bn, c.hidden), F32), readout=readout)
+        return PromptAttention(mass=mass.cpu().transpose(0, 1).contiguous(),
+                               probs=None if probs is None else probs.transpose(0, 1).clone(),
+                               first_logits=logits.clone(), lens=list(lens))
 
     def _check_constraint(self, constraint, n_rows: int, max_new_tokens: int, eos_id, do_sample: bool, repetition_penalty: float,
                           num_beams: int, suppress_eos: bool):

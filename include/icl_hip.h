@@ -223,6 +223,29 @@ int icl_attn_decode_gqa_bf16(const void* Q, int64_t ldq, const void* Kc, const v
                              const int32_t* lens, int32_t n_seqs, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim,
                              int32_t max_len, float scale, void* stream);
 
+/* ---- prompt-attention readout: softmax weights of one query row per sequence, summed per key segment ----
+ * What output_attentions=True of a transformers decoder gives for the last prompt row, reduced to what a few-shot study reads:
+ * how much of the row's attention falls on each piece of the prompt.  V is never read.
+ *   Q      bf16, already rotated (and normalised, for a QK-norm decoder); head h of sequence b at column h * head_dim of row
+ *          q_rows[b] (q_rows NULL: row b).  ldq % 8 == 0, ldq >= n_heads * head_dim.
+ *   Kc     the bf16 K cache of the decode kernels, [n_seqs][n_kv_heads][max_len][head_dim]; query head h reads K/V head
+ *          h / (n_heads / n_kv_heads); n_kv_heads 0 = n_heads.  Rows at or past lens[b] (>= 1) are never read.
+ *   seg    seg[b * ld_seg + j] = the segment of key j; an id >= n_seg counts nowhere; entries at or past lens[b] are never read.
+ *   s_j = scale * sum_d q_d k_jd (f32),  p_j = exp(s_j - max s) / sum_i exp(s_i - max s),
+ *   mass[b][h][g] = sum_{j < lens[b], seg_j = g} p_j  (f32 [n_seqs][n_heads][n_seg]; a segment without a key is exactly 0.0f),
+ *   probs[b][h][j] = p_j for j < lens[b] (f32 [n_seqs][n_heads][ld_probs], the rest untouched), or NULL.
+ * head_dim 64 or 128 multi-head; grouped (2 <= G <= 8 query heads per K/V head) at head_dim 128, one workgroup per (sequence,
+ * K/V head) loading a key row once for its G heads.  Two passes over K: the bytes of one icl_attn_decode_bf16 launch.
+ * No atomics, every sum in a fixed order that depends on the sequence's own length only: a row's mass and probs are
+ * bit-identical alone and in any batch.
+ * ICL_EINVAL (before any launch): a NULL Q / Kc / lens / seg / mass, n_seg outside 1..32, head_dim not 64 / 128, n_kv_heads not
+ * dividing n_heads, G > 8, G > 1 at head_dim 64, ld_seg < max_len, probs with ld_probs < max_len, a scale that is not finite.
+ */
+int icl_attn_segmass_bf16(const void* Q, int64_t ldq, const int32_t* q_rows, const void* Kc, const int32_t* lens,
+                          const uint8_t* seg, int64_t ld_seg, int32_t n_seg, float* mass, float* probs, int64_t ld_probs,
+                          int32_t n_seqs, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int32_t max_len, float scale,
+                          void* stream);
+
 /* ---- K11: the decode step's RoPE + KV-cache append + attention as ONE launch --------------------
  * icl_rope_kv_bf16 (M = n_seqs rows, one new position each) followed by icl_attn_decode_bf16, fused: qkv bf16 [n_seqs][ld] holds
  * the QKV projection's raw q | k | v row of every sequence (column blocks at 0 | k_off | v_off, n_heads*head_dim wide);
