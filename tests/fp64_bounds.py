@@ -1,6 +1,6 @@
 """Per-element error bounds against float64, shared by test_gpu_prefill_gemm.py, test_gpu_norm_exact.py and (on the CPU, without
 the kernels) test_fp64_bounds.py.  Not a test module and not a conftest: plain functions over torch tensors on any device.
-The constants and the comparison come from test_gpu_decode_plan.py (u = 2^-24, C_DOT = 2, _bf16_ulp, _assert_within).
+The constants and the comparison of every such test live here (u = 2^-24, C_DOT = 2, bf16_ulp, assert_within, _dot).
 
 GEMM  (pre = a @ W^T + bias in float64, mag = |a| @ |W|^T, K the depth; every bound is for the kernel's f32 value)
   e_pre                = C_DOT K u mag + u |pre| + 2u |bias|
@@ -22,11 +22,30 @@ import math
 
 import torch
 
-from test_gpu_decode_plan import C_DOT, U, _assert_within, _bf16_ulp  # noqa: F401  (re-exported)
-
+U = 2.0 ** -24
+C_DOT = 2
 GELU_SLOPE = 1.13       # sup |gelu'(x)| = 1.1290
 GELU_ABS = 1.5e-6       # csrc/common.h: |gelu_erf2 - exact| <= 1.5e-6 absolute
 SILU_SLOPE = 1.1        # sup |silu'(x)| = 1.0998
+
+
+def bf16_ulp(x):
+    """Spacing of bf16 numbers at |x| (float64; subnormals counted at the smallest normal)."""
+    m = x.abs().clamp_min(2.0 ** -126)
+    return torch.exp2(torch.floor(torch.log2(m)) - 7)
+
+
+def _dot(a, w64, w64abs):
+    a64 = a.double()
+    return a64 @ w64.t(), a64.abs() @ w64abs.t()
+
+
+def assert_within(got, ref, bound, what):
+    bad = ~((got.double() - ref).abs() <= bound)      # NaN (an element never written) counts as outside
+    if bad.any():
+        r, c = [int(v) for v in bad.nonzero()[0]]
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements outside the bound, first at "
+                             f"[{r}, {c}]: got {float(got[r, c])} ref {float(ref[r, c])} bound {float(bound[r, c])}")
 
 
 def gelu64(x):
@@ -88,7 +107,7 @@ def swiglu_ref_bound(dot, mag, K, *, bias=None):
 
 
 def bf16_out_bound(bound, ref, out):
-    return bound + _bf16_ulp(torch.maximum(ref.abs(), out.double().abs()))
+    return bound + bf16_ulp(torch.maximum(ref.abs(), out.double().abs()))
 
 
 def within(got, ref, bound):

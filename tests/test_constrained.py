@@ -1,7 +1,6 @@
 """CPU: opt-in label-constrained greedy decoding — the automaton builder (runtime/constraints.py), the refusals of
 ``generate(constraint=...)``, the CLI flag and the ``icl_argmax_fsm`` entry point's surface.  The kernel and the model path are
-checked in tests/test_gpu_constrained.py, against ``fsm_step_reference`` below."""
-import math
+checked in tests/test_gpu_constrained.py, against ``fsm_step_reference`` of tests/decoder_support.py."""
 import os
 import re
 import shutil
@@ -11,34 +10,9 @@ import numpy as np
 import pytest
 import torch
 
+from decoder_support import GOLDEN as G
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "tests", "golden")
-
-
-# ---- the yardstick: one step of icl_argmax_fsm in plain numpy, following include/icl_hip.h literally --------------------------
-def fsm_step_reference(row, state, steps_left, auto):
-    """(logits row f32 [V], state, steps_left, automaton) -> (token, next state, log-prob as f64) of an UNFINISHED row.
-    ``auto`` needs ``state_off`` / ``edge_tok`` / ``edge_next`` / ``state_dist`` (int sequences) and ``n_states``."""
-    row = np.asarray(row, dtype=np.float32)
-    off, etok, enext, dist = (np.asarray(x).astype(np.int64) for x in (auto.state_off, auto.edge_tok, auto.edge_next, auto.state_dist))
-    with np.errstate(all="ignore"):
-        if not 0 <= state < auto.n_states:                    # free row (-1), or a corrupt id handled as free
-            ok = ~np.isnan(row)
-            if not ok.any():
-                return 0, state, float("nan")
-            x = np.where(ok, row, -np.inf).astype(np.float64)
-            tok = int(np.argmax(x))                           # first index of the maximum
-            m = x[tok]
-            lp = (x[tok] - m) - math.log(np.exp(x[ok] - m).sum()) if np.isfinite(m) else float("nan")
-            return tok, state, lp
-        cand = [e for e in range(off[state], off[state + 1]) if dist[enext[e]] <= steps_left - 1]
-        assert cand, "the budget precondition steps_left >= state_dist[state] is the caller's"
-        x = np.array([row[etok[e]] for e in cand], dtype=np.float64)
-        x[np.isnan(x)] = -np.inf
-        k = int(np.argmax(x))                                 # edges are sorted by token id: first maximum = lowest token id
-        m = x[k]
-        lp = (x[k] - m) - math.log(np.exp(x - m).sum()) if np.isfinite(m) else float("nan")
-        return int(etok[cand[k]]), int(enext[cand[k]]), lp
 
 
 def all_typed():

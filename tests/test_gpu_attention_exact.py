@@ -48,33 +48,13 @@ import itertools
 import pytest
 import torch
 
+from gpu_support import DEV, B, dev, stop_after_a_device_fault  # noqa: F401  (fixtures)
 from oracle import attention as oa
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 SPAN = 8                  # rel_span of the bias probe: the clamp is live in every sequence longer than 8
 FORMS = list(itertools.product((64, 128), (False, True), (False, True), (False, True)))     # D, causal, kv_lens, bias
-
-
-@pytest.fixture(scope="module")
-def B():
-    import icl_speech_text_llm_amd.runtime.binding as b
-    b.load_library()
-    return b
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_a_device_fault():
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:       # nothing more may be launched on a faulted device
-        pytest.exit(f"device fault: {e}", returncode=3)
-
-
-def _dev(*xs):
-    return tuple(x.to(DEV) for x in xs)
 
 
 def _report(kernel, data, worst):
@@ -112,11 +92,11 @@ def test_prefill(B, D, causal, kvl, bias, H):
     name = f"attn_fwd D={D} causal={int(causal)} kv_lens={int(kvl)} bias={int(bias)} H={H}"
 
     # count and peak probes (the bias forms run them with a zero table: the weights must not move), packed and cache layout
-    q, k, v = _dev(*oa.probe_count(lens, H, D))
+    q, k, v = dev(*oa.probe_count(lens, H, D))
     R = oa.prefill_ref(q, k, v, lens, H, D, scale, **rkw)
     for cache in (False, True):
         oa.assert_count(_fwd(B, q, k, v, lens, H, D, cache=cache, **kw, **zero), R, f"{name} cache={int(cache)}")
-    q, k, v = _dev(*oa.probe_peak(lens, H, D, causal=causal, kv_lens=kv_lens, head_offset=H - 3))
+    q, k, v = dev(*oa.probe_peak(lens, H, D, causal=causal, kv_lens=kv_lens, head_offset=H - 3))
     R = oa.prefill_ref(q, k, v, lens, H, D, scale, **rkw)
     for cache in (False, True):
         oa.assert_exact(_fwd(B, q, k, v, lens, H, D, cache=cache, **kw, **zero), R, None, f"{name} cache={int(cache)}")
@@ -125,7 +105,7 @@ def test_prefill(B, D, causal, kvl, bias, H):
     rnd = dict(rel_bias=torch.randn(H, 2 * span - 1, generator=g).to(DEV), rel_gate=gate, rel_span=span) if bias else {}
     over = []
     for data in ("normal", "offset"):
-        q, k, v = _dev(*oa.random_data(lens, H, D, offset=data == "offset"))
+        q, k, v = dev(*oa.random_data(lens, H, D, offset=data == "offset"))
         R = oa.prefill_ref(q, k, v, lens, H, D, scale, **rkw, **rnd)
         out = _fwd(B, q, k, v, lens, H, D, **kw, **rnd)
         bad, worst = oa.fails_bound(out, R, D, r_P)                      # asserted at the end: the checks below still run
@@ -147,7 +127,7 @@ def test_prefill(B, D, causal, kvl, bias, H):
                 print(f"{name}: NaN V rows in [kv_len, len) -> {nan_rows} of {total} output rows NaN")
 
     if bias:
-        q, k, v, table, bgate = _dev(*oa.probe_bias(lens, H, D, span))
+        q, k, v, table, bgate = dev(*oa.probe_bias(lens, H, D, span))
         bkw = dict(rel_bias=table, rel_gate=bgate, rel_span=span)
         R = oa.prefill_ref(q, k, v, lens, H, D, scale, **rkw, **bkw)
         rows, rest = oa.bias_exact_rows(lens, H, causal, kv_lens)
@@ -179,12 +159,12 @@ def test_suffix(B, H):
         B.attn_fwd(q[idx].contiguous(), k, v, out, cu_t, max(lens), H, D, scale, causal=True, cu_q=cu_q)
         return out.view(-1, H, D)
 
-    q, k, v = _dev(*oa.probe_count(lens, H, D))
+    q, k, v = dev(*oa.probe_count(lens, H, D))
     oa.assert_count(suffix(q, k, v), oa.prefill_ref(q, k, v, lens, H, D, scale, causal=True).rows(idx), "suffix")
-    q, k, v = _dev(*oa.probe_peak(lens, H, D, causal=True, head_offset=H - 3))
+    q, k, v = dev(*oa.probe_peak(lens, H, D, causal=True, head_offset=H - 3))
     oa.assert_exact(suffix(q, k, v), oa.prefill_ref(q, k, v, lens, H, D, scale, causal=True).rows(idx), None, "suffix")
     for data in ("normal", "offset"):
-        q, k, v = _dev(*oa.random_data(lens, H, D, offset=data == "offset"))
+        q, k, v = dev(*oa.random_data(lens, H, D, offset=data == "offset"))
         out = suffix(q, k, v)
         R = oa.prefill_ref(q, k, v, lens, H, D, scale, causal=True).rows(idx)
         _report(f"attn_fwd_suffix H={H}", data, oa.assert_bound(out, R, D, oa.R_P["prefill128"], f"suffix {data}"))
@@ -201,7 +181,7 @@ def test_prefill_unaligned_out(B):
     idx = torch.cat([torch.arange(cu[s + 1] - ql, cu[s + 1]) for s, ql in enumerate(qlens)]).to(DEV)
     cu_q = torch.tensor(oa.cu_of(qlens), dtype=torch.int32, device=DEV)
     for D, causal, sfx in ((64, False, False), (128, True, False), (128, True, True)):
-        q, k, v = _dev(*oa.random_data(lens, H, D))
+        q, k, v = dev(*oa.random_data(lens, H, D))
         rows, hd = (sum(qlens), H * D) if sfx else (sum(lens), H * D)
         kw = dict(causal=causal, cu_q=cu_q) if sfx else dict(causal=causal)
         if sfx:
@@ -256,14 +236,14 @@ def test_decode(B, kernel, D, H, reps):
         assert bool(torch.isnan(obuf[:, :8].float()).all()) and bool(torch.isnan(obuf[:, 8 + hd:].float()).all()), f"{name}: wrote outside O"
         return out.reshape(n, H, D), oa.decode_ref(ql, kc, vc, lens, H, D, scale)
 
-    out, R = run(*_dev(*oa.probe_count(lens, H, D)))
+    out, R = run(*dev(*oa.probe_count(lens, H, D)))
     oa.assert_count(out, R, name)
-    out, R = run(*_dev(*oa.probe_peak(lens, H, D, causal=True, head_offset=reps - 1)))
+    out, R = run(*dev(*oa.probe_peak(lens, H, D, causal=True, head_offset=reps - 1)))
     oa.assert_exact(out, R, None, name)
     if reps == 1:
         assert bool((R.tgt[:, 0] == torch.tensor(lens, device=DEV) - 1).all())     # head 0: the target is the appended position
     for data in ("normal", "offset"):
-        out, R = run(*_dev(*oa.random_data(lens, H, D, offset=data == "offset")))
+        out, R = run(*dev(*oa.random_data(lens, H, D, offset=data == "offset")))
         _report(name, data, oa.assert_bound(out, R, D, oa.R_P["decode"], f"{name} {data}"))
 
 
@@ -283,10 +263,10 @@ def test_qformer(B, win):
         B.qformer_window_xattn(ql, kv, v_off, out, n_audio, wpa, win, rpa, H, 0.125)
         return out.view(n_win, H, 64), oa.qformer_ref(ql, kv, v_off, n_audio, wpa, win, rpa, H, 0.125)
 
-    out, R = run(*_dev(*oa.probe_count(lens, H, 64)))
+    out, R = run(*dev(*oa.probe_count(lens, H, 64)))
     oa.assert_count(out, R, f"qformer win={win}")
-    out, R = run(*_dev(*oa.probe_peak(lens, H, 64, causal=True)))
+    out, R = run(*dev(*oa.probe_peak(lens, H, 64, causal=True)))
     oa.assert_exact(out, R, None, f"qformer win={win}")
     for data in ("normal", "offset"):
-        out, R = run(*_dev(*oa.random_data(lens, H, 64, offset=data == "offset")))
+        out, R = run(*dev(*oa.random_data(lens, H, 64, offset=data == "offset")))
         _report(f"qformer_window_xattn win={win}", data, oa.assert_bound(out, R, 64, oa.R_P["qformer"], f"qformer win={win} {data}"))

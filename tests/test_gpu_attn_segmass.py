@@ -26,28 +26,13 @@ import pytest
 import torch
 
 import attn_segmass_ref as sr
+from decoder_support import salmonn_batch
+from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 PARITY_RATIO = 1.25
 NAN = float("nan")
-
-
-@pytest.fixture(scope="module")
-def B():
-    import icl_speech_text_llm_amd.runtime.binding as b
-    b.load_library()
-    return b
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_a_device_fault():
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:       # nothing more may be launched on a faulted device
-        pytest.exit(f"device fault: {e}", returncode=3)
 
 
 def _launch(B, q, kc, lens, seg, n_seg, H, Hkv, D, *, probs=True, q_rows=None):
@@ -290,10 +275,9 @@ def test_runtime_refusals(env):
 # the plugin
 # ------------------------------------------------------------------------------------------------------------------
 def test_plugin():
-    from test_gpu_plugin import _batch
     from icl_speech_text_llm_amd.models.model_factory import ModelFactory
     model = ModelFactory.create_model("salmonn", device="cuda", arch="tiny", low_resource=True, llama_path="none", lora_alpha=32).eval()
-    b = _batch(model, "speech", n=2, bs=2, num_examples=2)
+    b = salmonn_batch(model, "speech", n=2, bs=2, num_examples=2)
     b = {k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
     out = model.prompt_attention(dict(b))
     assert set(out) == {"mass", "pieces", "first_logits"}

@@ -1,5 +1,5 @@
 """`-m gpu`: opt-in label-constrained greedy decoding — the ``icl_argmax_fsm`` kernel against the numpy stepper of
-tests/test_constrained.py (integer results exact; log-probabilities within 1e-5 * max(1, |lp|) of the stepper's f64 value on the
+tests/decoder_support.py (integer results exact; log-probabilities within 1e-5 * max(1, |lp|) of the stepper's f64 value on the
 same f32 logits: f32 epsilon is 6e-8 and a value is a subtraction, one exp and one add per candidate and one log, so a few 1e-7
 relative is expected, up to ~1e-6 for a free row's 32 001 - 156 032-term sum with per-lane partial sums; 1e-5 leaves a margin of
 about ten and still catches a missing max-subtraction or a wrong candidate set, which cost >= 1e-2), and the runtime / plugin /
@@ -12,10 +12,10 @@ import numpy as np
 import pytest
 import torch
 
-from test_constrained import G, fsm_step_reference
+from decoder_support import GOLDEN as G, fsm_step_reference, qwen_chat_batch, row_prompts, salmonn_batch
+from gpu_support import DEV, stop_after_a_device_fault  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 EOS, PAD = 2, 400
 
 
@@ -204,10 +204,6 @@ def env():
     return _runtime()
 
 
-def _prompts(cfg, lens, seed=99):
-    return [[np.random.default_rng(seed + i).integers(3, cfg.llama.vocab - 1, n).tolist()] for i, n in enumerate(lens)]
-
-
 def _check_against_stepper(res, a, starts, T):
     """The emitted tokens are the constrained arg-max of the logits the GPU itself produced; log-probs within the kernel bound."""
     tokens, lps, logits = res.tokens.numpy(), res.token_logprobs.numpy(), res.step_logits.cpu().numpy()
@@ -238,7 +234,7 @@ def test_generate_follows_the_automaton_on_the_logits_the_gpu_produced(env, auto
     cfg, rt = env
     T, lens = 10, [21, 40, 33, 17, 25, 30, 19, 28, 36, 22, 31]
     names, starts = _mixed(auto, len(lens))
-    prompts = _prompts(cfg, lens)
+    prompts = row_prompts(cfg.llama.vocab, lens, seed=99)
     free = rt.generate(prompts, None, max_new_tokens=T, eos_id=EOS, pad_id=PAD, want_first_logits=True)
     assert free.token_logprobs is None
     res = rt.generate(prompts, None, max_new_tokens=T, eos_id=EOS, pad_id=PAD, want_first_logits=True, want_step_logits=True,
@@ -261,7 +257,7 @@ def test_eager_capture_replay_agree_and_a_second_automaton_gets_its_own_graph(en
     rt._graphs.clear(); rt._graph_warm.clear()
     T, lens = 10, [21, 40, 33, 18]
     names, starts = _mixed(auto, len(lens))
-    prompts = _prompts(cfg, lens, seed=7)
+    prompts = row_prompts(cfg.llama.vocab, lens, seed=7)
     outs = [rt.generate(prompts, None, max_new_tokens=T, eos_id=EOS, pad_id=PAD, constraint=(auto, starts)) for _ in range(3)]
     assert len(rt._graphs) == 1
     assert all(torch.equal(outs[0].tokens, o.tokens) and torch.equal(outs[0].token_logprobs, o.token_logprobs) for o in outs[1:])
@@ -284,22 +280,23 @@ def test_three_tokens_on_hvb_end_on_a_complete_label_list(env, auto):
     lens = [20, 31, 26, 40, 23, 35]
     s0 = auto.starts["hvb"]
     assert auto.min_tokens(s0) == 3
-    res = rt.generate(_prompts(cfg, lens, seed=3), None, max_new_tokens=3, eos_id=EOS, pad_id=PAD, constraint=(auto, [s0] * len(lens)),
+    prompts = row_prompts(cfg.llama.vocab, lens, seed=3)
+    res = rt.generate(prompts, None, max_new_tokens=3, eos_id=EOS, pad_id=PAD, constraint=(auto, [s0] * len(lens)),
                       want_step_logits=True)
     _check_against_stepper(res, auto, [s0] * len(lens), 3)
     for row in res.tokens.tolist():
         assert auto.accepts(s0, row) and len(row) == 3 and EOS not in row[:2]
     with pytest.raises(ValueError, match="shortest answer"):
-        rt.generate(_prompts(cfg, lens, seed=3), None, max_new_tokens=2, eos_id=EOS, pad_id=PAD, constraint=(auto, [s0] * len(lens)))
+        rt.generate(prompts, None, max_new_tokens=2, eos_id=EOS, pad_id=PAD, constraint=(auto, [s0] * len(lens)))
 
 
 def test_fp8_weights_and_fp8_cache_run_constrained(auto):
     cfg, rt = _runtime(llm_weight_dtype="fp8", llm_kv_dtype="fp8")
     T, lens = 10, [21, 40, 33, 17, 25]
     names, starts = _mixed(auto, len(lens))
+    prompts = row_prompts(cfg.llama.vocab, lens, seed=99)
     for _ in range(3):                                                      # eager, capture, replay
-        res = rt.generate(_prompts(cfg, lens), None, max_new_tokens=T, eos_id=EOS, pad_id=PAD, want_step_logits=True,
-                          constraint=(auto, starts))
+        res = rt.generate(prompts, None, max_new_tokens=T, eos_id=EOS, pad_id=PAD, want_step_logits=True, constraint=(auto, starts))
         _check_against_stepper(res, auto, starts, T)
 
 
@@ -308,10 +305,9 @@ def test_qwen_runtime_decodes_constrained():
     from icl_speech_text_llm_amd.models.model_factory import ModelFactory
     from icl_speech_text_llm_amd.runtime.constraints import grammar_of
     from icl_speech_text_llm_amd.utils.evaluation_utils import clean_prediction
-    import test_gpu_qwen as tq
     m = ModelFactory.create_model("qwen2", device="cuda", arch="tiny", model_path="none").eval()
     m.generation_config["max_new_tokens"] = 24
-    enc, prompt_len, _ = tq._batch(m)
+    enc, prompt_len, _ = qwen_chat_batch(m)
     batch = {"input_ids": enc.input_ids[:, :prompt_len], "attention_mask": enc.attention_mask[:, :prompt_len],
              "input_features": enc.input_features, "feature_attention_mask": enc.feature_attention_mask}
     plain = m.generate_ids(dict(batch), want_first_logits=True)
@@ -336,9 +332,8 @@ def _valid_answer(text, dataset_type):
 
 def test_plugin_key_constrains_and_its_absence_changes_nothing():
     from icl_speech_text_llm_amd.models.model_factory import ModelFactory
-    import test_gpu_plugin as tp
     m = ModelFactory.create_model("salmonn", device="cuda", arch="tiny", low_resource=True, llama_path="none", lora_alpha=32).eval()
-    b = tp._batch(m, "text", n=4, bs=4)
+    b = salmonn_batch(m, "text", n=4, bs=4)
     b = {k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
     b["max_new_tokens"] = 48
     never = m.generate_ids(dict(b), want_first_logits=True)

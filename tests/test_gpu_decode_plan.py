@@ -21,11 +21,11 @@ import dataclasses
 import pytest
 import torch
 
+from fp64_bounds import C_DOT, U, _dot, assert_within, bf16_ulp
+from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-U = 2.0 ** -24
-C_DOT = 2
 GUARD = 4096
 BATCHES = (1, 8, 9, 64, 65, 128, 129, 255, 256, 257)
 MODELS = ("llama2_7b", "llama2_13b", "qwen2_7b")
@@ -36,13 +36,6 @@ def _cfg(model):
     from icl_speech_text_llm_amd.runtime.config import QwenAudioCfg, SalmonnCfg
     return {"llama2_7b": SalmonnCfg.llama2_7b().llama, "llama2_13b": SalmonnCfg.llama2_13b().llama,
             "qwen2_7b": QwenAudioCfg().llm}[model]
-
-
-@pytest.fixture(scope="module")
-def B():
-    import icl_speech_text_llm_amd.runtime.binding as b
-    b.load_library()
-    return b
 
 
 _RT = {}
@@ -74,25 +67,6 @@ def _runtimes(model):
 def _rand(shape, seed, dtype=torch.bfloat16):
     g = torch.Generator(DEV).manual_seed(seed)
     return torch.randn(shape, generator=g, device=DEV).to(dtype)
-
-
-def _bf16_ulp(x):
-    """Spacing of bf16 numbers at |x| (float64; subnormals counted at the smallest normal)."""
-    m = x.abs().clamp_min(2.0 ** -126)
-    return torch.exp2(torch.floor(torch.log2(m)) - 7)
-
-
-def _dot(a, w64, w64abs):
-    a64 = a.double()
-    return a64 @ w64.t(), a64.abs() @ w64abs.t()
-
-
-def _assert_within(got, ref, bound, what):
-    bad = ~((got.double() - ref).abs() <= bound)      # NaN (an element never written) counts as outside
-    if bad.any():
-        r, c = [int(v) for v in bad.nonzero()[0]]
-        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements outside the bound, first at "
-                             f"[{r}, {c}]: got {float(got[r, c])} ref {float(ref[r, c])} bound {float(bound[r, c])}")
 
 
 def _rms64(c, gamma, eps):
@@ -156,7 +130,7 @@ def test_decode_step_gemm_launches_against_fp64(B, model, Bn, mode):
     b = L.bqkv.double() if L.bqkv is not None else torch.zeros(3 * hd, dtype=torch.float64, device=DEV)
     ref = ref + b
     e = C_DOT * ka * U * mag + U * ref.abs() + 2 * U * b.abs()
-    _assert_within(qkv, ref, e + _bf16_ulp(torch.maximum(ref.abs(), qkv.double().abs())), f"qkv {p}")
+    assert_within(qkv, ref, e + bf16_ulp(torch.maximum(ref.abs(), qkv.double().abs())), f"qkv {p}")
 
     # ---- o: h += att @ Wo^T in place (f32), xn = rmsnorm(h) * rms2 (fused) --------------------------------------------
     p = plan.sites["o"]
@@ -172,9 +146,9 @@ def test_decode_step_gemm_launches_against_fp64(B, model, Bn, mode):
     launched.append(("o", p))
     ref, mag = _dot(att, *_w64(L.wo))
     ref = ref + h0.double()
-    _assert_within(h, ref, C_DOT * hd * U * mag + U * ref.abs() + 2 * U * h0.double().abs(), f"o C {p}")
+    assert_within(h, ref, C_DOT * hd * U * mag + U * ref.abs() + 2 * U * h0.double().abs(), f"o C {p}")
     xr = _rms64(h, L.rms2, c.rms_eps)
-    _assert_within(xo[:, :hd], xr, _bf16_ulp(torch.maximum(xr.abs(), xo[:, :hd].double().abs())), f"o xn {p}")
+    assert_within(xo[:, :hd], xr, bf16_ulp(torch.maximum(xr.abs(), xo[:, :hd].double().abs())), f"o xn {p}")
     assert bool((xo[:, hd:] == 7.0).all()), "o: xn written past N"
 
     # ---- gu: act = silu(gate) * up, gate / up interleaved in blocks of 16 rows (bf16 out) ---------------------------------
@@ -192,7 +166,7 @@ def test_decode_step_gemm_launches_against_fp64(B, model, Bn, mode):
     eg = C_DOT * hd * U * gmag + U * gate.abs()
     eu = C_DOT * hd * U * umag + U * up.abs()
     e = 1.1 * eg * (up.abs() + eu) + sg.abs() * eu + U * (16 + 4 * gate.abs()) * ref.abs()
-    _assert_within(act, ref, e + _bf16_ulp(torch.maximum(ref.abs(), act.double().abs())), f"gu {p}")
+    assert_within(act, ref, e + bf16_ulp(torch.maximum(ref.abs(), act.double().abs())), f"gu {p}")
 
     # ---- down: h += act @ Wdown^T in place (f32), xn = rmsnorm(h) * the next norm's gamma (fused) ------------------------
     p = plan.sites["down"]
@@ -207,9 +181,9 @@ def test_decode_step_gemm_launches_against_fp64(B, model, Bn, mode):
     launched.append(("down", p))
     ref, mag = _dot(a_in, *_w64(L.wdown))
     ref = ref + h0.double()
-    _assert_within(h, ref, C_DOT * I * U * mag + U * ref.abs() + 2 * U * h0.double().abs(), f"down C {p}")
+    assert_within(h, ref, C_DOT * I * U * mag + U * ref.abs() + 2 * U * h0.double().abs(), f"down C {p}")
     xr = _rms64(h, rt.w.norm, c.rms_eps)
-    _assert_within(xd, xr, _bf16_ulp(torch.maximum(xr.abs(), xd.double().abs())), f"down xn {p}")
+    assert_within(xd, xr, bf16_ulp(torch.maximum(xr.abs(), xd.double().abs())), f"down xn {p}")
 
     torch.cuda.synchronize()
     assert bool(torch.isnan(ws_all[plan.workspace:]).all()), "a split-K launch wrote past the planned workspace"
@@ -231,14 +205,14 @@ def test_lm_head_launch_against_fp64(B, model):
         out = torch.full((R, c.vocab), float("nan"), device=DEV)
         B.gemm(xf, rt.w.lm_head, out, tile=p.tile)
         ref, mag = _dot(xf, *w64)
-        _assert_within(out, ref, C_DOT * c.hidden * U * mag + U * ref.abs(), f"lm_head R={R} {p}")
+        assert_within(out, ref, C_DOT * c.hidden * U * mag + U * ref.abs(), f"lm_head R={R} {p}")
         # logits() itself: the final norm, then the same launch
         h = _rand((R, c.hidden), 22, torch.float32)
         ws = E.Workspace(DEV)
         got = rt.logits(ws, h, name="t_logits")
         xn = ws.get("t_logits_xn", (R, c.hidden), torch.bfloat16)
         ref, mag = _dot(xn, *w64)
-        _assert_within(got, ref, C_DOT * c.hidden * U * mag + U * ref.abs(), f"logits() R={R}")
+        assert_within(got, ref, C_DOT * c.hidden * U * mag + U * ref.abs(), f"logits() R={R}")
     _W64.clear()
 
 
@@ -282,10 +256,10 @@ def test_gemm_rmsnorm_split1_contract(B, tile, M, wide):
     if M > 64 or wide:
         assert torch.equal(x1.view(torch.int16), x2.view(torch.int16))
     d = (x1.double() - x2.double()).abs()
-    assert bool((d <= _bf16_ulp(torch.maximum(x1.double().abs(), x2.double().abs()))).all()), float(d.max())
+    assert bool((d <= bf16_ulp(torch.maximum(x1.double().abs(), x2.double().abs()))).all()), float(d.max())
     # and against float64: C = R + a @ W^T, xn = the RMSNorm of that C
     ref = res.double() + a.double() @ w.double().t()
-    _assert_within(c1, ref, C_DOT * K * U * (a.double().abs() @ w.double().abs().t()) + U * ref.abs() + 2 * U * res.double().abs(),
+    assert_within(c1, ref, C_DOT * K * U * (a.double().abs() @ w.double().abs().t()) + U * ref.abs() + 2 * U * res.double().abs(),
                    "C")
     xr = _rms64(c1, gamma, eps)
-    _assert_within(x1, xr, _bf16_ulp(torch.maximum(xr.abs(), x1.double().abs())), "xn")
+    assert_within(x1, xr, bf16_ulp(torch.maximum(xr.abs(), x1.double().abs())), "xn")

@@ -10,6 +10,8 @@ import textwrap
 
 import pytest
 
+from gpu_support import stop_after_a_device_fault  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
 
 CHILD = textwrap.dedent("""

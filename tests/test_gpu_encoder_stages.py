@@ -27,30 +27,14 @@ import pytest
 import torch
 
 import encoder_stage_check as sc
+from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
 from oracle import audio_frontend as af
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 RAGGED = [480000 + 12345, 3200, 16000 * 3 + 123]
 PADDED = [16000 * 3 + 123, 16000 * 5]
 QWEN_MEL_LENS = [3000, 1000, 999, 2, 1]
-
-
-@pytest.fixture(scope="module")
-def B():
-    import icl_speech_text_llm_amd.runtime.binding as b
-    b.load_library()
-    return b
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_a_device_fault():
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:       # nothing more may be launched on a faulted device
-        pytest.exit(f"device fault: {e}", returncode=3)
 
 
 def _wavs(lens, L=None, seed=1234):                     # as tests/test_gpu_models.py::_wavs

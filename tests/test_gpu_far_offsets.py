@@ -13,7 +13,7 @@ region), the entry point runs on the far views, then again on a compact twin (sa
 alignment, same ld % 8, same sequence count: the launcher picks the same kernel), and
   1. the far outputs are bit-identical to the twin's (no tolerance: address arithmetic does not change arithmetic),
   2. the twin is within the project's existing fp64 bound of that kernel (tests/fp64_bounds.py, oracle/attention.py,
-     tests/qknorm_ref.py; the fp8 forms by their bit-identity anchor, ref_q of tests/test_gpu_fp8_kv.py),
+     tests/qknorm_ref.py; the fp8 forms by their bit-identity anchor, ref_q of tests/fp8_ref.py),
   3. every compared window outside the expected outputs is bit-equal to its pre-launch clone (margins, the near window where a
      truncated write would land, inputs).
 
@@ -63,7 +63,7 @@ Substituted, and why (the binding is not widened for a test):
     needs a thousand qkv rows, which do not fit at a far row stride); packed prefill rows likewise have lens [1, 1].
 Not covered: beats_patchify / beats_posconv_pack, whose indices are bounded by clip counts no workload reaches; the load-time
 packers (pack_decode_weights, pack_fp8_weights) and spec_to_xt, which the issue does not list.
-ref_q (the fp8 contract's rounding) is imported from tests/test_gpu_fp8_kv.py, where it lives.
+ref_q (the fp8 contract's rounding) is imported from tests/fp8_ref.py, where it lives.
 
 Wall time of the module on MI355X: 7 s (85 tests; 5 s between the arena's allocation and its release).  Nothing reads or fills
 more than its windows; the slowest cases are the grid-walk ones, whose twins are 84 MB.
@@ -75,20 +75,15 @@ import pytest
 import torch
 
 import far_layout as fl
+from decoder_support import GOLDEN, fsm_step_reference
+from fp8_ref import ref_q
+from gpu_support import DEV, B, dev, stop_after_a_device_fault  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 DT = {"f32": torch.float32, "bf16": torch.bfloat16, "u8": torch.uint8, "i32": torch.int32}
 F32, BF16, I32, U8 = torch.float32, torch.bfloat16, torch.int32, torch.uint8
 EPS = 1e-5
-
-
-@pytest.fixture(scope="module")
-def B():
-    import icl_speech_text_llm_amd.runtime.binding as b
-    b.load_library()
-    return b
 
 
 @pytest.fixture(scope="module")
@@ -103,15 +98,6 @@ def arena():
     del a
     torch.cuda.empty_cache()
     print(f"\nfar-offset module wall time: {time.time() - t0:.1f} s")
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_a_device_fault():
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:       # nothing more may be launched on a faulted device
-        pytest.exit(f"device fault: {e}", returncode=3)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -221,10 +207,6 @@ class Mem:
         return outs, bad
 
 
-def _dev(*xs):
-    return tuple(x.to(DEV) for x in xs)
-
-
 def run_case(B, arena, case, launch, check):
     """The twin launch and the three assertions."""
     mf = Mem(case, True, arena)
@@ -262,7 +244,7 @@ def _norm_params(N):
 
 
 def _launch_norm(B, c, m):
-    g, b = _dev(*_norm_params(c.p["N"]))
+    g, b = dev(*_norm_params(c.p["N"]))
     has = {o.name for o in c.ops}
     x, y = m.rows2d("x"), m.rows2d("y")
     if c.p["rms"]:
@@ -281,7 +263,7 @@ def _check_norm(B, c, m, outs, aux):
     ref, e = fb.norm_ref_bound(m.input2d("x"), g, b, EPS, rms=c.p["rms"], res=res, alpha=0.5)
     if y.dtype == BF16:
         e = fb.bf16_out_bound(e, ref, y)
-    fb._assert_within(y, ref, e, c.name)
+    fb.assert_within(y, ref, e, c.name)
     if "y2" in has:
         assert torch.equal(_bits(_stack(outs, "y2", 2)), _bits(y.to(BF16))), f"{c.name}: out2 != bf16(out)"
 
@@ -306,7 +288,7 @@ def _rope_args(c):
 def _launch_rope(B, c, m, name=None, pos=None):
     import qknorm_ref as qr
     H, Hkv, D, k_off, v_off, cos, sin, gq, gk = _rope_args(c)
-    cos, sin, gq, gk = _dev(cos, sin, gq, gk)
+    cos, sin, gq, gk = dev(cos, sin, gq, gk)
     p = torch.tensor(c.p["pos"] if pos is None else pos, dtype=I32, device=DEV)
     sid = torch.tensor(m.meta("kc", "ids"), dtype=I32, device=DEV)
     qkv, kc, vc = m.rows2d("qkv"), m.ptr("kc"), m.ptr("vc")
@@ -326,7 +308,6 @@ def _launch_rope(B, c, m, name=None, pos=None):
 def _check_rope(B, c, m, outs, aux):
     import fp64_bounds as fb
     import qknorm_ref as qr
-    from test_gpu_fp8_kv import ref_q
     H, Hkv, D, k_off, v_off, cos, sin, gq, gk = _rope_args(c)
     M = c.p["M"]
     orig = m.input2d("qkv")
@@ -415,7 +396,7 @@ def _launch_glue(B, c, m):
     elif c.name == "lora_down":
         B.lora_down(m.rows2d("x"), c.p["K0"], m.rows2d("a"), c.p["r"], 2.0)
     else:
-        w, b, a = _dev(*_gate_params())
+        w, b, a = dev(*_gate_params())
         B.beats_gate(m.rows2d("qkv"), w, b, a, m.ptr("gate")[:2 * c.p["H"]], c.p["H"])
 
 
@@ -431,7 +412,7 @@ def _check_glue(B, c, m, outs, aux):
     elif c.name.startswith("axpby_cast"):
         out = _stack(outs, "out", 2)
         ref, e = fb.axpby_ref_bound(m.input2d("x"), 0.3, m.input2d("add"))
-        _interval(fb, out, ref, e, c.name) if out.dtype == BF16 else fb._assert_within(out, ref, e, c.name)
+        _interval(fb, out, ref, e, c.name) if out.dtype == BF16 else fb.assert_within(out, ref, e, c.name)
     elif c.name == "embed_gather_interleave":
         want = torch.stack([m.inputs[(nm, i)].float() for nm, i in c.p["order"]])
         assert torch.equal(_bits(_stack(outs, "out", 8)), _bits(want)), f"{c.name}: rows are not the table's / the speech rows"
@@ -444,7 +425,7 @@ def _check_glue(B, c, m, outs, aux):
     else:
         H = c.p["H"]
         ref, e = fb.gate_ref_bound(m.input2d("qkv").view(2, H, 64), *_gate_params())
-        fb._assert_within(_stack(outs, "gate", 2), ref, e, c.name)
+        fb.assert_within(_stack(outs, "gate", 2), ref, e, c.name)
 
 
 @pytest.mark.parametrize("case", fl.group("glue"), ids=lambda c: c.name)
@@ -485,11 +466,10 @@ def _automaton():
     """The label automaton of tests/test_gpu_constrained.py (every typed task of the 401-token test tokenizer)."""
     if not _FSM:
         import os
-        from test_constrained import G
         from icl_speech_text_llm_amd.data.task_configs import DatasetType
         from icl_speech_text_llm_amd.runtime.constraints import build_label_automaton
         from icl_speech_text_llm_amd.utils.tokenization import load_llama_tokenizer
-        a = build_label_automaton(load_llama_tokenizer(os.path.join(G, "llama_spm"), 401), list(DatasetType))
+        a = build_label_automaton(load_llama_tokenizer(os.path.join(GOLDEN, "llama_spm"), 401), list(DatasetType))
         start = next(s for s in a.starts.values() if s >= 0 and a.min_tokens(s) <= FSM_STEPS_LEFT)
         _FSM.update(a=a, states=[start, -1])                    # row 0 constrained from a start state, row 1 free
     return _FSM["a"], _FSM["states"]
@@ -541,7 +521,6 @@ def _check_tail(B, c, m, outs, aux):
     import fp64_bounds as fb
     x = m.input2d("logits")
     if c.name == "argmax_fsm":
-        from test_constrained import fsm_step_reference
         a, states = _automaton()
         for b in range(2):                          # the numpy stepper; the log-probability bound of tests/test_gpu_constrained.py
             t, n, lp = fsm_step_reference(x[b].numpy(), states[b], FSM_STEPS_LEFT, a)
@@ -571,7 +550,7 @@ def _check_tail(B, c, m, outs, aux):
         assert aux["tokens"][:, [0, 2, 3]].eq(-5).all()
         return
     ref, e, mref, me = fb.ce_ref_bound(x, torch.tensor([3, c.p["V"] - 1], dtype=I32))
-    fb._assert_within(aux["row_loss"], ref, e, c.name)
+    fb.assert_within(aux["row_loss"], ref, e, c.name)
     assert abs(float(aux["mean_loss"]) - mref) <= me
 
 
@@ -607,7 +586,7 @@ def _gemm_weights(c):
 def _launch_gemm(B, c, m):
     N, K, tile, split_k, epi = (c.p[k] for k in ("N", "K", "tile", "split_k", "epi"))
     has = {o.name for o in c.ops}
-    w, bias = _dev(*_gemm_weights(c))
+    w, bias = dev(*_gemm_weights(c))
     kw = dict(split_k=split_k, N=N, K=K)
     if "w" in has:
         w = m.rows2d("w")
@@ -655,7 +634,7 @@ def _check_gemm(B, c, m, outs, aux):
         ref, e = fb.gemm_ref_bound(dot, mag, K)
     if got.dtype == BF16:
         e = fb.bf16_out_bound(e, ref, got)
-    fb._assert_within(got, ref, e, c.name)
+    fb.assert_within(got, ref, e, c.name)
 
 
 @pytest.mark.parametrize("case", fl.group("gemm"), ids=lambda c: c.name)
@@ -665,7 +644,7 @@ def test_gemm(B, arena, case):
 
 def _launch_gemm_rmsnorm(B, c, m):
     N, K, tile, split_k = (c.p[k] for k in ("N", "K", "tile", "split_k"))
-    w, _ = _dev(*_gemm_weights(c))
+    w, _ = dev(*_gemm_weights(c))
     gamma = _norm_params(N)[0].to(DEV)
     ws = torch.full((split_k * 2 * N,), float("nan"), dtype=F32, device=DEV) if split_k > 1 else None
     B.gemm_rmsnorm(m.rows2d("a"), w, m.rows2d("c"), gamma, EPS, m.rows2d("xn"), residual=m.rows2d("r"), split_k=split_k,
@@ -677,10 +656,10 @@ def _check_gemm_rmsnorm(B, c, m, outs, aux):
     (dot, mag), _ = _gemm_ref(B, c, m)
     got, xn = _stack(outs, "c", 2), _stack(outs, "xn", 2)
     ref, e = fb.gemm_ref_bound(dot, mag, c.p["K"], residual=m.input2d("r"))
-    fb._assert_within(got, ref, e, c.name + " C")
+    fb.assert_within(got, ref, e, c.name + " C")
     gamma = _norm_params(c.p["N"])[0]
     nref, ne = fb.norm_ref_bound(got, gamma, None, EPS, rms=True)          # the row the kernel normalised, taken as data
-    fb._assert_within(xn, nref, fb.bf16_out_bound(ne, nref, xn), c.name + " xn")
+    fb.assert_within(xn, nref, fb.bf16_out_bound(ne, nref, xn), c.name + " xn")
 
 
 @pytest.mark.parametrize("case", fl.group("gemm_rmsnorm"), ids=lambda c: c.name)
@@ -689,7 +668,7 @@ def test_gemm_rmsnorm(B, arena, case):
 
 
 def _launch_gemm_batched(B, c, m):
-    w, bias = _dev(*_gemm_weights(c))
+    w, bias = dev(*_gemm_weights(c))
 
     has = {o.name for o in c.ops}
     M, epi = c.p["M"], c.p["epi"]
@@ -716,7 +695,7 @@ def _check_gemm_batched(B, c, m, outs, aux):
         ref, e = fb.gemm_ref_bound(dot, mag, K, bias=bias, residual=res, gelu=epi == "bias_gelu_res")
     if got.dtype == BF16:
         e = fb.bf16_out_bound(e, ref, got)
-    fb._assert_within(got.reshape(2 * M, -1), ref.reshape(2 * M, -1), e.reshape(2 * M, -1), c.name)
+    fb.assert_within(got.reshape(2 * M, -1), ref.reshape(2 * M, -1), e.reshape(2 * M, -1), c.name)
 
 
 @pytest.mark.parametrize("case", fl.group("gemm_batched"), ids=lambda c: c.name)
@@ -798,8 +777,7 @@ def test_decode_attention_gqa(B, arena, case):
 
 def _fp8_rows(c, which, i):
     """(bytes, scales, x') of the GRID_ROWS cache rows of checked sequence i of the K (which = "k") or V plane: the contract's
-    rounding (ref_q of tests/test_gpu_fp8_kv.py) of seeded bf16 rows of very different magnitudes."""
-    from test_gpu_fp8_kv import ref_q
+    rounding (ref_q of tests/fp8_ref.py) of seeded bf16 rows of very different magnitudes."""
     g = _gen(c.name, which, i)
     mag = torch.exp2(torch.randint(-6, 3, (fl.GRID_ROWS, 1), generator=g).float())
     return ref_q((torch.randn(fl.GRID_ROWS, c.p["D"], generator=g) * mag).to(BF16))
@@ -859,7 +837,7 @@ def _fused_args(c):
 
 def _launch_fused(B, c, m):
     H, D, hd, cos, sin, pos, lens = _fused_args(c)
-    cos, sin, pos, lens = _dev(cos, sin, pos, lens)
+    cos, sin, pos, lens = dev(cos, sin, pos, lens)
     sid = torch.tensor(m.meta("kc", "ids"), dtype=I32, device=DEV)
     if c.p["fp8"]:
         B.attn_decode_rope_fp8(m.rows2d("qkv"), hd, 2 * hd, cos, sin, pos, sid, m.ptr("kc"), m.ptr("vc"), m.ptr("ks"), m.ptr("vs"),
@@ -893,7 +871,6 @@ def _check_fused(B, c, m, outs, aux):
 
 def _fused_fp8_stripe(c, which, i):
     """(bytes, scales, x') of stripe i (sequence i // H, head i % H) of the K or V plane: the contract's rounding of seeded rows."""
-    from test_gpu_fp8_kv import ref_q
     g = _gen(c.name, which, i)
     mag = torch.exp2(torch.randint(-6, 3, (fl.FUSED_MAXLEN, 1), generator=g).float())
     return ref_q((torch.randn(fl.FUSED_MAXLEN, c.p["D"], generator=g) * mag).to(BF16))
@@ -912,7 +889,6 @@ ROW_DATA["decode_rope"] = _fused_row_data
 def _check_fused_fp8(B, c, m, outs):
     """The fp8 form's anchor (tests/test_gpu_fp8_kv.py): rope_kv on a bf16 cache holding x', the appended rows replaced by their
     fp8 rounding, then the bf16 kernel of the fp8 kernel's lane mapping: output and appended bytes / scales bit for bit."""
-    from test_gpu_fp8_kv import ref_q
     H, D, hd, cos, sin, pos, lens = _fused_args(c)
     T = fl.FUSED_MAXLEN
     qkv = m.input2d("qkv")
@@ -1189,13 +1165,13 @@ def _check_frontend(B, c, m, outs, aux):
         x = m.inputs[("wav", i)][:L].numpy()
         if c.name == "logmel_whisper":
             ref, e = fb.whisper_ref_bound(torch.from_numpy(af.whisper_logmel(x, N_MEL, as_f64=True)))
-            fb._assert_within(aux["spec"][i], ref, e, f"{c.name} clip {i}")
+            fb.assert_within(aux["spec"][i], ref, e, f"{c.name} clip {i}")
         else:
             mean, std = float(np.float32(af.FBANK_MEAN)), float(np.float32(af.FBANK_STD))
             ref, e = fb.kaldi_ref_bound(torch.from_numpy(af.kaldi_fbank(x, mean, std, as_f64=True)))
             nf = af.kaldi_num_frames(L)
             assert ref.shape[0] == nf and bool(torch.isnan(aux["out"][i, nf:]).all())
-            fb._assert_within(aux["out"][i, :nf], ref, e, f"{c.name} clip {i}")
+            fb.assert_within(aux["out"][i, :nf], ref, e, f"{c.name} clip {i}")
     if c.name == "logmel_whisper":                                    # xt is the exact image of spec
         want = torch.zeros_like(aux["xt"])
         want[:, 1:-1, :N_MEL] = aux["spec"].transpose(1, 2).to(BF16)
@@ -1234,7 +1210,7 @@ def _fused_gemm_args(c):
 
 def _launch_fused_gemm(B, c, m):
     H, D, hd, w, bias, (cos, sin), pos = _fused_gemm_args(c)
-    w, bias, cos, sin, pos = _dev(w, bias, cos, sin, pos)
+    w, bias, cos, sin, pos = dev(w, bias, cos, sin, pos)
     sid = torch.tensor(m.meta("kc", "ids"), dtype=I32, device=DEV)
     B.gemm(m.rows2d("a"), w, m.rows2d("c"), bias=bias, tile=3,
            rope=(hd, 2 * hd, cos, sin, pos, sid, m.ptr("kc"), m.ptr("vc"), H, D, fl.ROPE_MAXLEN))
@@ -1245,7 +1221,7 @@ def _check_fused_gemm(B, c, m, outs, aux):
     icl_rope_kv_bf16, each held to float64 by its own case above."""
     H, D, hd, w, bias, (cos, sin), pos = _fused_gemm_args(c)
     M = c.p["M"]
-    w, bias, cos, sin, pos = _dev(w, bias, cos, sin, pos)
+    w, bias, cos, sin, pos = dev(w, bias, cos, sin, pos)
     ref = torch.full((M, 3 * hd), float("nan"), dtype=BF16, device=DEV)
     B.gemm(m.input2d("a").to(DEV), w, ref, bias=bias, tile=3)
     kc = torch.full((M, H, fl.ROPE_MAXLEN, D), float("nan"), dtype=BF16, device=DEV)

@@ -9,40 +9,12 @@ import os
 import pytest
 import torch
 
+from decoder_support import same_generation, stream_prompts
+from fp8_ref import ref_pack, ref_q
+from fp64_bounds import C_DOT, U, _dot, assert_within, bf16_ulp
+from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-
-
-def _B():
-    import icl_speech_text_llm_amd.runtime.binding as B
-    return B
-
-
-def pow2(e: torch.Tensor) -> torch.Tensor:
-    """2^e as float64, built from its bits (exact; torch.ldexp / exp2 on the device go through an inexact pow)."""
-    return ((e.to(torch.int64) + 1023) << 52).view(torch.float64)
-
-
-def ref_quant(w: torch.Tensor):
-    """Torch reference of the numerics contract: (q bytes uint8 [N, K], scales f32 [N] = 2^e, W' bf16 [N, K])."""
-    wf = w.double()
-    m = wf.abs().amax(1)
-    mant, ex = torch.frexp(m)
-    e = torch.where(mant <= 0.875, ex - 9, ex - 8)
-    e = torch.where(m == 0, torch.zeros_like(e), e)
-    q = (wf * pow2(-e)[:, None]).float().to(torch.float8_e4m3fn)            # exact scaling, then torch's RNE rounding
-    wd = (q.double() * pow2(e)[:, None]).to(torch.bfloat16)
-    return q.view(torch.uint8), pow2(e).float(), wd
-
-
-def ref_pack(q: torch.Tensor) -> torch.Tensor:
-    """q [N, K] uint8 row-major -> the fp8 decode-packed layout (rows padded to 16; 16-B pieces of two 32-wide k-steps)."""
-    N, K = q.shape
-    Np = (N + 15) // 16 * 16
-    qp = torch.zeros(Np, K, dtype=torch.uint8, device=q.device)
-    qp[:N] = q
-    # q[16 nt + fr][64 j + 32 h + 8 fq + i] -> piece (nt, j, lane = fq * 16 + fr), byte h * 8 + i
-    return qp.view(Np // 16, 16, K // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5).reshape(Np, K)
 
 
 def _weights(N, K, seed, scale=0.02):
@@ -61,21 +33,19 @@ SHAPES = {
 
 @pytest.mark.parametrize("model", sorted(SHAPES))
 @pytest.mark.parametrize("which", ["qkv", "o", "gu", "down"])
-def test_packer_matches_torch_reference(model, which):
-    B = _B()
+def test_packer_matches_torch_reference(B, model, which):
     N, K = SHAPES[model][which]
     w = _weights(N, K, seed=sorted(SHAPES).index(model) * 4 + ["qkv", "o", "gu", "down"].index(which))
     src = w.clone()
     q, s, wd = B.pack_fp8_weights(w)
-    rq, rs, rwd = ref_quant(w)
+    rq, rs, rwd = ref_q(w)
     assert torch.equal(s, rs)
     assert torch.equal(q, ref_pack(rq))
     assert torch.equal(wd.view(torch.int16), rwd.view(torch.int16))
     assert torch.equal(w.view(torch.int16), src.view(torch.int16))     # the source is left alone (out-of-place form)
 
 
-def test_packer_ragged_zero_row_tiny_row_and_in_place():
-    B = _B()
+def test_packer_ragged_zero_row_tiny_row_and_in_place(B):
     N, K = 1000, 576
     w = _weights(N, K, seed=5)
     w[7] = 0
@@ -84,7 +54,7 @@ def test_packer_ragged_zero_row_tiny_row_and_in_place():
     w[10, 5] = 448.0                       # exactly the top of the e4m3 range: e = 0
     w[11, 5] = 452.0                       # just above (bf16 has no 449): e = 1
     q, s, wd = B.pack_fp8_weights(w)
-    rq, rs, rwd = ref_quant(w)
+    rq, rs, rwd = ref_q(w)
     assert float(s[7]) == 1.0 and float(s[10]) == 1.0 and float(s[11]) == 2.0
     assert torch.equal(s, rs) and torch.equal(q, ref_pack(rq))      # ref_pack zero-fills the padding rows of the last block
     assert torch.equal(wd.view(torch.int16), rwd.view(torch.int16))
@@ -101,18 +71,16 @@ def test_packer_ragged_zero_row_tiny_row_and_in_place():
 
 
 @pytest.mark.parametrize("bad", [float("nan"), float("inf"), float("-inf")])
-def test_packer_rejects_non_finite(bad):
-    B = _B()
+def test_packer_rejects_non_finite(B, bad):
     w = _weights(64, 128, seed=1)
     w[33, 77] = bad
     with pytest.raises(B.IclError, match="non-finite"):
         B.pack_fp8_weights(w)
 
 
-def test_every_finite_e4m3_code_reads_back_exactly():
+def test_every_finite_e4m3_code_reads_back_exactly(B):
     """All 254 finite e4m3fn codes (subnormals, both zeros and both signs included), at scale 1 and at scale 2^-20, through the
     packer and the fp8-weight kernel against one-hot activations: the kernel's output is W' itself."""
-    B = _B()
     codes = torch.tensor([c for c in range(256) if c not in (0x7F, 0xFF)], dtype=torch.uint8)
     vals = codes.view(torch.float8_e4m3fn).float()
     assert vals.numel() == 254 and torch.isfinite(vals).all()
@@ -125,7 +93,7 @@ def test_every_finite_e4m3_code_reads_back_exactly():
     w = w.to(torch.bfloat16).to(DEV)
     q, s, wd = B.pack_fp8_weights(w)
     assert torch.equal(wd.float(), w.float())                       # every value is already its own FP8 rounding
-    rq = ref_quant(w)[0]
+    rq = ref_q(w)[0]
     assert torch.equal(rq[:254, 1].cpu(), codes) and torch.equal(q, ref_pack(rq))
     a = torch.zeros(2, K, dtype=torch.bfloat16, device=DEV)
     a[0, 0] = 1
@@ -139,10 +107,9 @@ def test_every_finite_e4m3_code_reads_back_exactly():
 _CACHE = {}
 
 
-def _packed(model, which):
+def _packed(B, model, which):
     key = (model, which)
     if key not in _CACHE:
-        B = _B()
         N, K = SHAPES[model][which]
         w = _weights(N, K, seed=len(_CACHE) + 11)
         q, s, wd = B.pack_fp8_weights(w)
@@ -160,10 +127,9 @@ CASES = [(model, epi) for model in sorted(SHAPES) for epi in ("none", "bias", "s
 
 
 @pytest.mark.parametrize("model,epi", CASES)
-def test_fp8w_kernel_is_bit_identical_to_tile6_on_w_prime(model, epi):
-    B = _B()
+def test_fp8w_kernel_is_bit_identical_to_tile6_on_w_prime(B, model, epi):
     which = {"none": "qkv", "bias": "qkv", "swiglu": "gu", "residual": "down", "rmsnorm": "o"}[epi]
-    q, s, wd, dp = _packed(model, which)
+    q, s, wd, dp = _packed(B, model, which)
     N, K = SHAPES[model][which]
     g = torch.Generator(device=DEV).manual_seed(N + K)
     for M in (1, 2, 5, 8, 24, 64):
@@ -209,14 +175,12 @@ def test_fp8w_kernel_is_bit_identical_to_tile6_on_w_prime(model, epi):
 
 
 @pytest.mark.parametrize("K", [64, 192, 576])
-def test_fp8w_tile6_tile4_bit_identical_on_small_shapes(K):
+def test_fp8w_tile6_tile4_bit_identical_on_small_shapes(B, K):
     """The three weight forms of the skinny kernel (fp8 decode-packed, tile 6 on the decode-packed W', tile 4 on row-major W') at
     the sizes where their K walks differ most: K = 64 / 192 / 576 gives waves an empty k-step range, a single half-pair, and ranges
     that start or end inside a k-pair; N = 40 / 264 / 96 leaves the last n-tile ragged or absent; M covers 1, 2 and 4 row blocks.
-    Outputs start as NaN, and the fp8 form is held to test_gpu_decode_plan's per-element fp64 bound, so the three cannot agree
+    Outputs start as NaN, and the fp8 form is held to the per-element fp64 bound of test_gpu_decode_plan.py, so the three cannot agree
     on a wrong answer."""
-    from test_gpu_decode_plan import C_DOT, U, _assert_within, _bf16_ulp, _dot
-    B = _B()
     g = torch.Generator(device=DEV).manual_seed(77 + K)
     for epi, Ns in (("plain", (16, 40, 264)), ("bias_res", (16, 40, 264)), ("swiglu", (32, 96))):
         for N in Ns:
@@ -253,16 +217,15 @@ def test_fp8w_tile6_tile4_bit_identical_on_small_shapes(K):
                 B.gemm(a, dp, o6, tile=6, N=N, K=K, **kw)
                 B.gemm(a, wd, o4, tile=4, N=N, K=K, **kw)
                 if odt == torch.bfloat16:
-                    bound = bound + _bf16_ulp(torch.maximum(ref.abs(), o8.double().abs()))
-                _assert_within(o8, ref, bound, f"fp8w {what}")
+                    bound = bound + bf16_ulp(torch.maximum(ref.abs(), o8.double().abs()))
+                assert_within(o8, ref, bound, f"fp8w {what}")
                 bits = torch.int16 if odt == torch.bfloat16 else torch.int32
                 assert torch.equal(o8.view(bits), o6.view(bits)), ("fp8w != tile 6", what)
                 assert torch.equal(o4.view(bits), o6.view(bits)), ("tile 4 != tile 6", what)
 
 
-def test_fp8w_kernel_argument_checks():
-    B = _B()
-    q, s, wd, dp = _packed("llama7b", "o")
+def test_fp8w_kernel_argument_checks(B):
+    q, s, wd, dp = _packed(B, "llama7b", "o")
     a = torch.zeros(65, 4096, dtype=torch.bfloat16, device=DEV)
     out = torch.empty(65, 4096, dtype=torch.bfloat16, device=DEV)
     with pytest.raises(B.IclError, match="M <= 64"):
@@ -270,12 +233,6 @@ def test_fp8w_kernel_argument_checks():
 
 
 # ---- model level: fp8 mode == the bf16 model on W' ------------------------------------------------------------------------
-def _prompts(vocab, lens, seed):
-    import numpy as np
-    rng = np.random.default_rng(seed)
-    return [[rng.integers(3, vocab - 2, n).tolist()] for n in lens]
-
-
 def _pair(kind):
     """(runtime in fp8 mode, runtime in bf16 mode holding the fp8 runtime's W' matrices)."""
     from icl_speech_text_llm_amd.runtime import synth
@@ -292,11 +249,10 @@ def _pair(kind):
         lm = cfg.llm
     r8 = R(cfg, dict(sd), device=DEV, llm_weight_dtype="fp8")
     rb = R(cfg, dict(sd), device=DEV)
-    B = _B()
     for L8, Lb in zip(r8.llama.w.layers, rb.llama.w.layers):
         assert L8.decode_packed is None and L8.fp8 is not None           # no bf16 decode copy is made at load in fp8 mode
         for (q, s), name in zip(L8.fp8, ("wqkv", "wo", "wgu", "wdown")):
-            rq, rs, rwd = ref_quant(getattr(Lb, name))
+            rq, rs, rwd = ref_q(getattr(Lb, name))
             assert torch.equal(getattr(L8, name).view(torch.int16), rwd.view(torch.int16)), name
             assert torch.equal(s, rs) and torch.equal(q, ref_pack(rq)), name
             setattr(Lb, name, getattr(L8, name).clone())
@@ -310,36 +266,30 @@ def pair(request):
     return _pair(request.param)
 
 
-def _same(a, b):
-    assert torch.equal(a.tokens.cpu(), b.tokens.cpu())
-    if a.first_logits is not None:
-        assert torch.equal(a.first_logits, b.first_logits)
-
-
 @pytest.mark.parametrize("lens", [[37], [33, 90, 61, 12, 5, 70, 44, 21], [9 + 7 * i for i in range(16)]])
 def test_model_greedy_matches_bf16_on_w_prime(pair, lens):
     r8, rb, lm = pair
-    prompts = _prompts(lm.vocab, lens, seed=len(lens))
+    prompts = stream_prompts(lm.vocab, lens, seed=len(lens))
     kw = dict(max_new_tokens=8, suppress_eos=True, want_first_logits=True)
-    _same(r8.generate(prompts, None, **kw), rb.generate(prompts, None, **kw))
+    same_generation(r8.generate(prompts, None, **kw), rb.generate(prompts, None, **kw))
 
 
 def test_model_sampled_and_beam_match_bf16_on_w_prime(pair):
     r8, rb, lm = pair
-    prompts = _prompts(lm.vocab, [40, 23], seed=3)
+    prompts = stream_prompts(lm.vocab, [40, 23], seed=3)
     outs = []
     for rt in (r8, rb):
         gen = torch.Generator(device=DEV).manual_seed(1234)
         outs.append(rt.generate(prompts, None, max_new_tokens=8, do_sample=True, temperature=0.8, top_p=0.9, top_k=50,
                                 generator=gen, want_first_logits=True, suppress_eos=True))
-    _same(*outs)
+    same_generation(*outs)
     beams = [rt.generate(prompts[:1], None, max_new_tokens=6, suppress_eos=True, num_beams=4, want_first_logits=True) for rt in (r8, rb)]
-    _same(*beams)
+    same_generation(*beams)
 
 
 def test_model_forward_logits_match_bf16_on_w_prime(pair):
     r8, rb, lm = pair
-    prompts = _prompts(lm.vocab, [37, 150, 64], seed=9)
+    prompts = stream_prompts(lm.vocab, [37, 150, 64], seed=9)
     l8, n8 = r8.forward_logits(prompts, None)
     l8 = l8.clone()
     lb, nb = rb.forward_logits(prompts, None)
@@ -360,7 +310,7 @@ def test_fp8_decode_differs_from_bf16_only_by_the_weight_rounding(pair):
         from icl_speech_text_llm_amd.runtime.salmonn import SalmonnRuntime as R
         cfg = SalmonnCfg.tiny(use_beats=True, lora=True)
         orig = R(cfg, synth.salmonn_state(cfg, seed=0, jitter=True), device=DEV)
-    prompts = _prompts(lm.vocab, [50], seed=4)
+    prompts = stream_prompts(lm.vocab, [50], seed=4)
     a = r8.generate(prompts, None, max_new_tokens=1, suppress_eos=True, want_first_logits=True).first_logits
     b = orig.generate(prompts, None, max_new_tokens=1, suppress_eos=True, want_first_logits=True).first_logits
     err = _rel(a, b)
@@ -404,10 +354,10 @@ def test_plugin_fp8_mode_and_reload_requantizes():
            if k.endswith("proj.weight")}
     m.load_state_dict(new, strict=False)
     L = m.runtime.llama.w.layers[0]
-    assert torch.equal(L.wo.view(torch.int16), ref_quant(new["llama_model.model.layers.0.self_attn.o_proj.weight"].to(DEV))[2].view(torch.int16))
+    assert torch.equal(L.wo.view(torch.int16), ref_q(new["llama_model.model.layers.0.self_attn.o_proj.weight"].to(DEV))[2].view(torch.int16))
     wsd = _w_prime_state_dict(m)
     assert torch.equal(wsd["llama_model.model.layers.0.mlp.up_proj.weight"].view(torch.int16),
-                       ref_quant(new["llama_model.model.layers.0.mlp.up_proj.weight"].to(DEV))[2].cpu().view(torch.int16))
+                       ref_q(new["llama_model.model.layers.0.mlp.up_proj.weight"].to(DEV))[2].cpu().view(torch.int16))
 
 
 def test_cli_fp8_writes_the_same_files_as_bf16_on_w_prime(tmp_path):

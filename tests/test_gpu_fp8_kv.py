@@ -12,31 +12,12 @@ import numpy as np
 import pytest
 import torch
 
+from decoder_support import same_generation, stream_prompts
+from fp8_ref import edge_rows, ref_q
+from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 BF16 = torch.bfloat16
-
-
-def _B():
-    import icl_speech_text_llm_amd.runtime.binding as B
-    return B
-
-
-def pow2(e: torch.Tensor) -> torch.Tensor:
-    """2^e as float64, built from its bits (exact)."""
-    return ((e.to(torch.int64) + 1023) << 52).view(torch.float64)
-
-
-def ref_q(x: torch.Tensor):
-    """Torch reference of the contract for rows x bf16 [..., D]: (bytes uint8 [..., D], scales f32 [...] = 2^e, x' bf16)."""
-    xf = x.double()
-    m = xf.abs().amax(-1)
-    mant, ex = torch.frexp(m)
-    e = torch.where(mant <= 0.875, ex - 9, ex - 8)
-    e = torch.where(m == 0, torch.zeros_like(e), e)
-    q = (xf * pow2(-e)[..., None]).float().to(torch.float8_e4m3fn)
-    xp = (q.double() * pow2(e)[..., None]).to(BF16)
-    return q.view(torch.uint8), pow2(e).float(), xp
 
 
 def _rows(shape, seed, spread=(-10, 4)):
@@ -46,28 +27,11 @@ def _rows(shape, seed, spread=(-10, 4)):
     return (torch.randn(shape, device=DEV, generator=g) * mag).to(BF16)
 
 
-def _edge_rows(D):
-    """The contract's edge rows: all-zero, one nonzero, amax exactly 448 * 2^e, e4m3 subnormal range, negative zero, ties."""
-    r = torch.zeros(8, D, dtype=torch.float64)
-    r[1, 5] = -3.0                                    # a single nonzero
-    r[2] = torch.linspace(-1, 1, D)
-    r[2, 7] = 448 * 2.0 ** -3                         # amax exactly at 448 * 2^e
-    r[3] = torch.linspace(-1, 1, D) * 2.0 ** -10      # q in the e4m3 subnormal range (< 2^-6) next to the row maximum
-    r[3, 0] = 448 * 2.0 ** -3
-    r[4] = -0.0                                       # negative zero everywhere (amax 0: e = 0, bytes 0x80)
-    r[5, ::3] = -0.0
-    r[5, 1] = 1e-3
-    r[6] = 448 * 2.0 ** 5 + torch.arange(D) * 2.0 ** 3    # rounding ties of the 3-bit mantissa
-    r[7] = torch.randn(D, generator=torch.Generator().manual_seed(7)) * 2.0 ** 40
-    return r.to(BF16).to(DEV)
-
-
 # ---- quantize-append ---------------------------------------------------------------------------------------------------------
 def _append_case(D, H, M, T, seed):
-    B = _B()
     hd = H * D
     qkv = _rows((M, 3, H, D), seed).reshape(M, 3 * hd)
-    ed = _edge_rows(D)
+    ed = edge_rows(D).to(DEV)
     qkv.view(M, 3, H, D)[: len(ed) // 2, 1, 0] = ed[::2]
     qkv.view(M, 3, H, D)[: len(ed) // 2, 2, H - 1] = ed[1::2]
     g = torch.Generator().manual_seed(seed)
@@ -77,7 +41,7 @@ def _append_case(D, H, M, T, seed):
     vq = kq.clone()
     ks = torch.full((M, H, T), -1.0, device=DEV)
     vs = ks.clone()
-    return B, qkv, seq, pos, kq, vq, ks, vs
+    return qkv, seq, pos, kq, vq, ks, vs
 
 
 def _check_appended(qkv, seq, pos, kq, vq, ks, vs, H, D, k_rows=None):
@@ -101,17 +65,16 @@ DH_CASES = [(64, 4), (128, 2), (128, 32), (128, 11), (64, 22)]
 
 
 @pytest.mark.parametrize("D,H", DH_CASES)
-def test_prefill_append_bytes_and_scales_match_torch(D, H):
-    B, qkv, seq, pos, kq, vq, ks, vs = _append_case(D, H, 37, 11, seed=D + H)
+def test_prefill_append_bytes_and_scales_match_torch(B, D, H):
+    qkv, seq, pos, kq, vq, ks, vs = _append_case(D, H, 37, 11, seed=D + H)
     B.kv_append_fp8(qkv, H * D, 2 * H * D, pos, seq, kq, vq, ks, vs, H, D, 11)
     _check_appended(qkv, seq, pos, kq, vq, ks, vs, H, D)
 
 
-def test_edge_rows_bytes():
+def test_edge_rows_bytes(B):
     """The edge rows through the kernel, spelled out: zero row -> scale 1 and zero bytes, -0 -> 0x80, 448 * 2^e -> 0x7e."""
-    B = _B()
     D, H = 64, 1
-    ed = _edge_rows(D)
+    ed = edge_rows(D).to(DEV)
     qkv = torch.zeros(len(ed), 3 * D, dtype=BF16, device=DEV)
     qkv[:, D:2 * D] = ed
     qkv[:, 2 * D:] = ed
@@ -131,9 +94,9 @@ def test_edge_rows_bytes():
 
 
 @pytest.mark.parametrize("D,H", DH_CASES)
-def test_decode_rope_append_matches_torch_on_the_bf16_rotation(D, H):
+def test_decode_rope_append_matches_torch_on_the_bf16_rotation(B, D, H):
     """icl_rope_kv_fp8: q rotated exactly as icl_rope_kv_bf16 rotates it, and the cache holds ref_q of the bf16-rotated k / v."""
-    B, qkv, seq, pos, kq, vq, ks, vs = _append_case(D, H, 8, 16, seed=3 * D + H)
+    qkv, seq, pos, kq, vq, ks, vs = _append_case(D, H, 8, 16, seed=3 * D + H)
     T, hd, M = 16, H * D, 8
     cos, sin = _rope_tables(64, D)
     ref = qkv.clone()
@@ -145,11 +108,10 @@ def test_decode_rope_append_matches_torch_on_the_bf16_rotation(D, H):
     _check_appended(qkv, seq, pos, kq, vq, ks, vs, H, D, k_rows=ref.view(M, 3, H, D)[:, 1])
 
 
-def test_append_outside_the_cache_stores_nothing():
+def test_append_outside_the_cache_stores_nothing(B):
     """icl_kv_append_fp8 at a position outside [0, max_len) stores nothing (the only form that reads no table at pos): rows at
     positions -1 and max_len next to two rows that are appended, in planes with a slack sequence on either side, so that a
     missing guard shows as a changed sentinel inside the allocation."""
-    B = _B()
     M, H, D, T, n_seqs = 4, 2, 64, 4, 6
     qkv = _rows((M, 3 * H * D), 41)
     seq = torch.tensor([1, 2, 3, 4], dtype=torch.int32, device=DEV)
@@ -170,10 +132,9 @@ def test_append_outside_the_cache_stores_nothing():
     assert int(written.sum()) == 2 * H
 
 
-def test_non_finite_rows_become_nan_and_stay_local():
-    B = _B()
+def test_non_finite_rows_become_nan_and_stay_local(B):
     D, H, M, T = 128, 4, 6, 8
-    _, qkv, seq, pos, kq, vq, ks, vs = _append_case(D, H, M, T, seed=5)
+    qkv, seq, pos, kq, vq, ks, vs = _append_case(D, H, M, T, seed=5)
     qkv.view(M, 3, H, D)[0, 1, 2, 17] = float("nan")
     qkv.view(M, 3, H, D)[1, 2, 0, 3] = float("inf")
     qkv.view(M, 3, H, D)[2, 1, 1, 0] = float("-inf")
@@ -236,10 +197,9 @@ GRID = [(1, 4), (7, 4), (256, 4), (256, 8)]
 
 @pytest.mark.parametrize("D", [64, 128])
 @pytest.mark.parametrize("n,H", GRID)
-def test_attn_decode_fp8_is_bit_identical_to_bf16_on_x_prime(D, n, H):
+def test_attn_decode_fp8_is_bit_identical_to_bf16_on_x_prime(B, D, n, H):
     """Bit for bit against the bf16 kernel with the fp8 kernel's 16-element lane mapping (icl_attn_decode_bf16_epl16) on a bf16
     cache of x'; within 1e-3 (relative L2) of the production 8-element kernel, whose score partial sums run in another order."""
-    B = _B()
     T = 392
     kq, vq, ks, vs, kx, vx = _cache(n, H, T, D, seed=n * 31 + H + D)
     lens = torch.tensor(_lens(n, T, n), dtype=torch.int32, device=DEV)
@@ -257,10 +217,9 @@ def test_attn_decode_fp8_is_bit_identical_to_bf16_on_x_prime(D, n, H):
 
 @pytest.mark.parametrize("D", [64, 128])
 @pytest.mark.parametrize("n,H", GRID)
-def test_fused_rope_attn_decode_fp8_serves_the_rounded_row(D, n, H):
+def test_fused_rope_attn_decode_fp8_serves_the_rounded_row(B, D, n, H):
     """icl_attn_decode_rope_fp8 against the bf16 kernels: rope_kv on a bf16 cache holding x', the appended rows then replaced by
     x' in torch, the same-mapping bf16 attention over the cache rows the seq_ids select.  Output and appended bytes bit for bit."""
-    B = _B()
     T, hd = 392, H * D
     kq, vq, ks, vs, kx, vx = _cache(n, H, T, D, seed=n * 7 + H + D)
     lens_l = _lens(n, T, n + 1)
@@ -292,8 +251,7 @@ def test_fused_rope_attn_decode_fp8_serves_the_rounded_row(D, n, H):
     assert torch.equal(kq, kq0) and torch.equal(ks, ks0)                         # nothing else of the cache was written
 
 
-def test_kv_copy_spans_fp8_moves_bytes_and_scales():
-    B = _B()
+def test_kv_copy_spans_fp8_moves_bytes_and_scales(B):
     L, n, H, T, D = 3, 5, 2, 20, 128
     kq = torch.randint(0, 255, (L, n, H, T, D), dtype=torch.uint8, device=DEV)
     ks = torch.randn(L, n, H, T, device=DEV)
@@ -314,11 +272,6 @@ def test_kv_copy_spans_fp8_moves_bytes_and_scales():
 
 
 # ---- model level --------------------------------------------------------------------------------------------------------------
-def _prompts(vocab, lens, seed):
-    rng = np.random.default_rng(seed)
-    return [[rng.integers(3, vocab - 2, n).tolist()] for n in lens]
-
-
 def _runtime(kind, kv, wdt="bf16"):
     from icl_speech_text_llm_amd.runtime import synth
     from icl_speech_text_llm_amd.runtime.config import QwenAudioCfg, SalmonnCfg
@@ -380,19 +333,13 @@ def pair(request):
     return r8, rb, lm
 
 
-def _same(a, b):
-    assert torch.equal(a.tokens.cpu(), b.tokens.cpu())
-    if a.first_logits is not None:
-        assert torch.equal(a.first_logits, b.first_logits)
-
-
 LENS = [[37], [33, 90, 61, 12, 5, 70, 44, 21], [9 + 7 * i for i in range(16)]]
 
 
 @pytest.mark.parametrize("lens", LENS, ids=["b1", "b8", "b16"])
 def test_first_step_logits_are_bit_identical_to_bf16_mode(pair, lens):
     r8, rb, lm = pair
-    prompts = _prompts(lm.vocab, lens, seed=len(lens))
+    prompts = stream_prompts(lm.vocab, lens, seed=len(lens))
     kw = dict(max_new_tokens=1, suppress_eos=True, want_first_logits=True)
     assert torch.equal(r8.generate(prompts, None, **kw).first_logits, rb.generate(prompts, None, **kw).first_logits)
 
@@ -402,22 +349,22 @@ def test_greedy_step_logits_match_the_x_prime_reference(pair, lens):
     """<= 8 rows: decode runs icl_rope_kv_fp8 + icl_attn_decode_fp8; 16 rows: the fused icl_attn_decode_rope_fp8 — both against
     the bf16 kernels on x' (the reference always runs the stand-alone rope_kv).  Graph-captured fp8 decode included."""
     r8, rb, lm = pair
-    prompts = _prompts(lm.vocab, lens, seed=len(lens) + 100)
+    prompts = stream_prompts(lm.vocab, lens, seed=len(lens) + 100)
     kw = dict(max_new_tokens=9, suppress_eos=True, want_first_logits=True, want_step_logits=True)
     a = r8.generate(prompts, None, **kw)
     a2 = r8.generate(prompts, None, **kw)               # the second call replays the captured graph
     with xprime_reference(rb):
         b = rb.generate(prompts, None, **kw)
     plain = rb.generate(prompts, None, **kw)
-    _same(a, b)
-    _same(a2, b)
+    same_generation(a, b)
+    same_generation(a2, b)
     assert torch.equal(a.step_logits, b.step_logits) and torch.equal(a2.step_logits, b.step_logits)
     assert not torch.equal(a.step_logits, plain.step_logits)          # the cache really was rounded
 
 
 def test_fused_and_unfused_fp8_decode_agree_and_graph_equals_eager(pair):
     r8, _, lm = pair
-    prompts = _prompts(lm.vocab, [9 + 5 * i for i in range(12)], seed=5)
+    prompts = stream_prompts(lm.vocab, [9 + 5 * i for i in range(12)], seed=5)
     kw = dict(max_new_tokens=6, suppress_eos=True, want_step_logits=True)
     fused = r8.generate(prompts, None, **kw)
     r8.use_graphs, r8.llama.fuse_decode_rope = False, False
@@ -428,13 +375,13 @@ def test_fused_and_unfused_fp8_decode_agree_and_graph_equals_eager(pair):
     finally:
         del r8.use_graphs, r8.llama.fuse_decode_rope
     for o in (eager_unfused, eager_fused):
-        _same(fused, o)
+        same_generation(fused, o)
         assert torch.equal(fused.step_logits, o.step_logits)
 
 
 def test_sampled_and_beam_match_the_x_prime_reference(pair):
     r8, rb, lm = pair
-    prompts = _prompts(lm.vocab, [40, 23], seed=3)
+    prompts = stream_prompts(lm.vocab, [40, 23], seed=3)
 
     def sampled(rt):
         gen = torch.Generator(device=DEV).manual_seed(1234)
@@ -447,18 +394,18 @@ def test_sampled_and_beam_match_the_x_prime_reference(pair):
         del r8.use_graphs
     with xprime_reference(rb):
         b = sampled(rb)
-    _same(a, b)
+    same_generation(a, b)
     kw = dict(max_new_tokens=6, suppress_eos=True, num_beams=4, want_first_logits=True)
     a = r8.generate(prompts, None, **kw)
     with xprime_reference(rb):
         b = rb.generate(prompts, None, **kw)
-    _same(a, b)
+    same_generation(a, b)
 
 
 @pytest.mark.parametrize("chunk", [1, 3])
 def test_chunked_prefill_gives_the_same_bits(pair, chunk):
     r8, _, lm = pair
-    prompts = _prompts(lm.vocab, [17, 40, 9, 33, 21, 5, 28], seed=11)
+    prompts = stream_prompts(lm.vocab, [17, 40, 9, 33, 21, 5, 28], seed=11)
     kw = dict(max_new_tokens=5, suppress_eos=True, want_first_logits=True, want_step_logits=True)
     whole = r8.generate(prompts, None, **kw)
     r8.prefill_chunk = chunk
@@ -467,7 +414,7 @@ def test_chunked_prefill_gives_the_same_bits(pair, chunk):
         beams = r8.generate(prompts[:3], None, max_new_tokens=4, suppress_eos=True, num_beams=4)
     finally:
         del r8.prefill_chunk
-    _same(whole, part)
+    same_generation(whole, part)
     assert torch.equal(whole.step_logits, part.step_logits)
     assert torch.equal(beams.tokens, r8.generate(prompts[:3], None, max_new_tokens=4, suppress_eos=True, num_beams=4).tokens)
 

@@ -25,11 +25,11 @@ import pytest
 import torch
 
 import fp64_bounds as fb
+from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
 from oracle import audio_frontend as af
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 T = af.N_FRAMES
 
@@ -39,22 +39,6 @@ W_WIDTH = 500008
 K_CLIPS = [(399, "noise"), (400, "dc"), (559, "tone"), (560, "full"), (400 + 160 * 15, "floor"), (400 + 160 * 16, "noise"),
            (400 + 160 * 63, "tone"), (400 + 160 * 64, "dc"), (48000, "noise")]
 MEAN32, STD32 = float(np.float32(af.FBANK_MEAN)), float(np.float32(af.FBANK_STD))     # what the kernel receives
-
-
-@pytest.fixture(scope="module")
-def B():
-    import icl_speech_text_llm_amd.runtime.binding as b
-    b.load_library()
-    return b
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_a_device_fault():
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:       # nothing more may be launched on a faulted device
-        pytest.exit(f"device fault: {e}", returncode=3)
 
 
 def _report(kernel, data, worst):

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import stop_after_a_device_fault  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
 
 

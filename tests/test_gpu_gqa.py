@@ -10,37 +10,18 @@ and 3.68e-3 (12 rows), the multi-head twin the same to four digits (ratio 1.000)
 (Qwen2 decoder); FP8 weight mode 3.37e-3 / 3.71e-3 against the oracle on W'."""
 from dataclasses import replace
 
-import numpy as np
 import pytest
 import torch
 
+from decoder_support import llama_oracle, row_prompts, teacher_forced_check
+from fp8_ref import w_prime_state
+from gpu_support import DEV, B, dev, stop_after_a_device_fault  # noqa: F401  (fixtures)
 from oracle import attention as oa
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 D = 128
 PARITY_RATIO = 1.25       # the project's margin between two runs that differ only in summation order
-
-
-@pytest.fixture(scope="module")
-def B():
-    import icl_speech_text_llm_amd.runtime.binding as b
-    b.load_library()
-    return b
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_a_device_fault():
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:       # nothing more may be launched on a faulted device
-        pytest.exit(f"device fault: {e}", returncode=3)
-
-
-def _dev(*xs):
-    return tuple(x.to(DEV) for x in xs)
 
 
 def _expand(x, Hkv, G):
@@ -63,7 +44,7 @@ def _gqa_data(kind, lens, Hkv, G, causal=True):
     else:
         q = oa.random_data(lens, H, D, offset=kind == "offset")[0]
         _, k, v = oa.random_data(lens, Hkv, D, oa.SEED + 1, offset=kind == "offset")
-    return _dev(q, k, v)
+    return dev(q, k, v)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -245,40 +226,6 @@ def _twin_state(sd, c, prefix):
     return out
 
 
-def _oracle(sd, c, prefix, rnd=True):
-    from oracle import models as om
-    lsd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
-    return om.LlamaOracle(lsd, c.n_heads, c.rms_eps, c.rope_theta, c.lora_scale, rnd=om.bf16_round if rnd else None,
-                          n_kv_heads=c.kv_heads)
-
-
-def _prompts(vocab, lens, seed):
-    return [[np.random.default_rng(seed + i).integers(3, vocab - 1, n).tolist()] for i, n in enumerate(lens)]
-
-
-def _teacher_forced_check(rt, ob, prompts, tag):
-    """The criteria of test_llama_generate_matches_oracle: the oracle is teacher-forced along the GPU's own 10 tokens; every GPU
-    choice is within 2x that step's logit error of the oracle's arg-max, and equal to it wherever the margin exceeds 4x the error.
-    Returns the worst step rel-L2."""
-    res = rt.generate(prompts, None, max_new_tokens=10, suppress_eos=True, want_first_logits=True, want_step_logits=True)
-    assert res.tokens.shape == (len(prompts), 10) and torch.equal(res.step_logits[0], res.first_logits)
-    worst = 0.0
-    for i, segs in enumerate(prompts):
-        toks = res.tokens[i]
-        tf = ob.teacher_forced_logits(ob.embed(torch.tensor(segs[0]))[None], toks[None])[0]
-        g = res.step_logits[:, i].cpu()
-        for t in range(10):
-            err = float((g[t] - tf[t]).abs().max())
-            worst = max(worst, float((g[t] - tf[t]).norm() / tf[t].norm()))
-            top2 = tf[t].topk(2)
-            chosen = int(toks[t])
-            assert float(top2.values[0] - tf[t, chosen]) <= 2 * err + 1e-6, (tag, i, t, chosen, int(top2.indices[0]), err)
-            assert int(g[t].argmax()) == chosen
-            if float(top2.values[0] - top2.values[1]) > 4 * err:
-                assert chosen == int(top2.indices[0]), (tag, i, t)
-    return worst
-
-
 @pytest.fixture(scope="module")
 def gqa_env():
     from icl_speech_text_llm_amd.runtime import synth
@@ -300,10 +247,10 @@ def test_decoder_chain(gqa_env, lens):
     today's path against the same oracle logits, and the GQA run's worst step rel-L2 is within PARITY_RATIO of the twin's."""
     cfg, sd, rt, twin = gqa_env
     assert rt.llama.w.layers[0].wqkv.shape == (1024, 576) and twin.llama.w.layers[0].wqkv.shape == (1536, 576)
-    prompts = _prompts(cfg.llama.vocab, lens, seed=7)
-    ob = _oracle(sd, cfg.llama, "llama_model.")
-    e_gqa = _teacher_forced_check(rt, ob, prompts, "gqa")
-    e_twin = _teacher_forced_check(twin, ob, prompts, "twin")
+    prompts = row_prompts(cfg.llama.vocab, lens, seed=7)
+    ob = llama_oracle(sd, cfg.llama, "llama_model.")
+    e_gqa = teacher_forced_check(rt, ob, prompts, "gqa")
+    e_twin = teacher_forced_check(twin, ob, prompts, "twin")
     print(f"decoder chain {len(lens)} rows: worst step rel-L2 gqa {e_gqa:.3e}, multi-head twin {e_twin:.3e}, ratio {e_gqa / e_twin:.3f}")
     assert e_gqa <= PARITY_RATIO * e_twin
 
@@ -312,8 +259,8 @@ def test_forward_logits_and_sampling(gqa_env):
     """Teacher-forced forward (no cache: packed q | k | v rows) against the oracle, and a sampled run (the sampling kernels never
     see heads: it only has to run and repeat under the same generator seed)."""
     cfg, sd, rt, twin = gqa_env
-    prompts = _prompts(cfg.llama.vocab, [37, 150, 64], seed=3)
-    ob = _oracle(sd, cfg.llama, "llama_model.")
+    prompts = row_prompts(cfg.llama.vocab, [37, 150, 64], seed=3)
+    ob = llama_oracle(sd, cfg.llama, "llama_model.")
     want = torch.cat([ob.forward(ob.embed(torch.tensor(p[0]))[None])[0][0] for p in prompts])
     rel = lambda a: float((a.float().cpu() - want).norm() / want.norm())
     got, n = rt.forward_logits(prompts, None)
@@ -336,7 +283,7 @@ def test_margin_weights_greedy_and_beam():
     sd = synth.salmonn_state(cfg, seed=1, parts=("llama",), margin=True)
     rt = SalmonnRuntime(cfg, dict(sd), device=DEV, parts=("llama",))
     for lens in ([33, 90, 61, 12], [20 + 3 * i for i in range(12)]):
-        prompts = _prompts(cfg.llama.vocab, lens, seed=21)
+        prompts = row_prompts(cfg.llama.vocab, lens, seed=21)
         gen = rt.generate(prompts, None, max_new_tokens=8, suppress_eos=True)
         for b, p in enumerate(prompts):
             chain, t = [], p[0][-1]
@@ -344,48 +291,12 @@ def test_margin_weights_greedy_and_beam():
                 t = synth.margin_successor(sd, t)
                 chain.append(t)
             assert gen.tokens[b].tolist() == chain, (len(lens), b)
-    prompts = _prompts(cfg.llama.vocab, [33, 90, 61], seed=21)
+    prompts = row_prompts(cfg.llama.vocab, [33, 90, 61], seed=21)
     beams = rt.generate(prompts, None, max_new_tokens=5, suppress_eos=True, num_beams=3)
-    ob = _oracle(sd, cfg.llama, "llama_model.")
+    ob = llama_oracle(sd, cfg.llama, "llama_model.")
     for b, p in enumerate(prompts):
         want = ob.generate_beam(ob.embed(torch.tensor(p[0]))[None], 5, -1, cfg.llama.pad_id, 3, 1.0)
         assert beams.tokens[b, :want.shape[1]].tolist() == want[0].tolist(), b
-
-
-def _pow2(e):
-    return ((e.to(torch.int64) + 1023) << 52).view(torch.float64)
-
-
-def _w_prime(w):
-    """README's rule of the FP8 weight mode, per row, on the CPU: W' = e4m3fn(W / 2^e) * 2^e."""
-    wf = w.double()
-    m = wf.abs().amax(1)
-    mant, ex = torch.frexp(m)
-    e = torch.where(mant <= 0.875, ex - 9, ex - 8)
-    e = torch.where(m == 0, torch.zeros_like(e), e)
-    q = (wf * _pow2(-e)[:, None]).float().to(torch.float8_e4m3fn)
-    return (q.double() * _pow2(e)[:, None]).to(torch.bfloat16)
-
-
-def _w_prime_state(sd, c):
-    """The checkpoint of the bf16 model that computes on W': the packed GEMM weights rounded row by row, split back out."""
-    from icl_speech_text_llm_amd.runtime.packing import pack_llama, qkv_row_blocks
-    w = pack_llama(dict(sd), c, "cpu")
-    h, I, r = c.hidden, c.ffn, c.lora_rank
-    out = dict(sd)
-    for i, L in enumerate(w.layers):
-        p = f"llama_model.model.layers.{i}."
-        wqkv = _w_prime(L.wqkv).float()
-        for n, (r0, nr) in zip(("q_proj", "k_proj", "v_proj"), qkv_row_blocks(c)):
-            out[p + f"self_attn.{n}.weight"] = wqkv[r0:r0 + nr, :h]
-            if n in c.lora_targets:
-                ti = c.lora_targets.index(n)
-                out[p + f"self_attn.{n}.lora_B.weight"] = wqkv[r0:r0 + nr, h + ti * r:h + (ti + 1) * r]
-        gu = _w_prime(L.wgu).float().view(I // 16, 2, 16, h)
-        out[p + "mlp.gate_proj.weight"], out[p + "mlp.up_proj.weight"] = gu[:, 0].reshape(I, h), gu[:, 1].reshape(I, h)
-        out[p + "self_attn.o_proj.weight"] = _w_prime(L.wo).float()
-        out[p + "mlp.down_proj.weight"] = _w_prime(L.wdown).float()
-    return out
 
 
 def test_fp8_weight_mode_on_the_gqa_model(gqa_env):
@@ -394,13 +305,13 @@ def test_fp8_weight_mode_on_the_gqa_model(gqa_env):
     from icl_speech_text_llm_amd.runtime.salmonn import SalmonnRuntime
     cfg, sd, _, _ = gqa_env
     r8 = SalmonnRuntime(cfg, dict(sd), device=DEV, parts=("llama",), llm_weight_dtype="fp8")
-    wsd = _w_prime_state(sd, cfg.llama)
+    wsd = w_prime_state(sd, cfg.llama)
     for L, i in zip(r8.llama.w.layers, range(2)):
         want = torch.cat([wsd[f"llama_model.model.layers.{i}.self_attn.{n}_proj.weight"] for n in "qkv"])
         assert torch.equal(L.wqkv[:, :512].float().cpu(), want)
-    ob = _oracle(wsd, cfg.llama, "llama_model.")
+    ob = llama_oracle(wsd, cfg.llama, "llama_model.")
     for lens in ([33, 90, 61, 12], [33, 90, 61, 12, 5, 70, 44, 21, 9, 57, 28, 16]):
-        e = _teacher_forced_check(r8, ob, _prompts(cfg.llama.vocab, lens, seed=7), f"fp8w {len(lens)} rows")
+        e = teacher_forced_check(r8, ob, row_prompts(cfg.llama.vocab, lens, seed=7), f"fp8w {len(lens)} rows")
         print(f"fp8 weight mode, gqa, {len(lens)} rows: worst step rel-L2 vs the oracle on W' {e:.3e}")
 
 
@@ -462,8 +373,8 @@ def test_qwen_gqa_forward_matches_oracle():
     assert sd["language_model.model.layers.0.self_attn.k_proj.lora_B.weight"].shape == (256, 8)
     rt = QwenAudioRuntime(cfg, dict(sd), device=DEV)
     twin = QwenAudioRuntime(replace(cfg, llm=replace(cfg.llm, n_kv_heads=None)), _twin_state(sd, cfg.llm, "language_model."), device=DEV)
-    prompts = _prompts(cfg.llm.vocab - 1, [37, 150, 64], seed=9)          # below the audio token id
-    ob = _oracle(sd, cfg.llm, "language_model.")
+    prompts = row_prompts(cfg.llm.vocab - 1, [37, 150, 64], seed=9)          # below the audio token id
+    ob = llama_oracle(sd, cfg.llm, "language_model.")
     want = torch.cat([ob.forward(ob.embed(torch.tensor(p[0]))[None])[0][0] for p in prompts])
     rel = lambda a: float((a.float().cpu() - want).norm() / want.norm())
     e_gqa = rel(rt.forward_logits(prompts, None)[0])

@@ -6,16 +6,9 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
-
-
-@pytest.fixture(scope="module")
-def B():
-    import icl_speech_text_llm_amd.runtime.binding as b
-    b.load_library()
-    return b
 
 
 def _rand_bf16(*shape, scale=1.0, seed=0):

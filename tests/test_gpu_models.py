@@ -10,8 +10,10 @@ import numpy as np
 import pytest
 import torch
 
+from decoder_support import row_prompts
+from gpu_support import DEV, stop_after_a_device_fault  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 
 
 def _rel(got, ref):
@@ -111,16 +113,10 @@ def _llama_oracle(cfg, sd, rnd=None):
 
 def _prompts(cfg, lens, n_speech=0, seed=99):
     from icl_speech_text_llm_amd.runtime.salmonn import speech_segment
-    out = []
-    for i, n in enumerate(lens):
-        rng = np.random.default_rng(seed + i)
-        ids = rng.integers(3, cfg.llama.vocab - 1, n).tolist()
-        if n_speech:
-            k = n // 2
-            out.append([ids[:k], speech_segment(i * n_speech, n_speech), ids[k:]])
-        else:
-            out.append([ids])
-    return out
+    rows = row_prompts(cfg.llama.vocab, lens, seed)
+    if not n_speech:
+        return rows
+    return [[ids[:len(ids) // 2], speech_segment(i * n_speech, n_speech), ids[len(ids) // 2:]] for i, (ids,) in enumerate(rows)]
 
 
 def test_llama_forward_logits_and_loss(env):

@@ -28,21 +28,19 @@ import pytest
 import torch
 
 import fp64_bounds as fb
+from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 SENT = 7.0
 EPS = 1e-5
 WORST = {"norms": 0.0, "where": ""}
 NS = (768, 772, 1280, 1284, 1536, 4096, 5120, 5124, 8192)
 
 
-@pytest.fixture(scope="module")
-def B():
-    import icl_speech_text_llm_amd.runtime.binding as b
-    b.load_library()
-    yield b
+@pytest.fixture(scope="module", autouse=True)
+def _report_worst():
+    yield
     print(f"\nworst err/bound, norms: {WORST['norms']:.4f} ({WORST['where']})")
 
 
@@ -82,7 +80,7 @@ def _check(out, x, g, b, what, rms=False, res=None, alpha=1.0, chunk=4096):
         ref, e = fb.norm_ref_bound(x[sl], g, b, EPS, rms=rms, res=None if res is None else res[sl], alpha=alpha)
         if out.dtype == torch.bfloat16:
             e = fb.bf16_out_bound(e, ref, out[sl])
-        fb._assert_within(out[sl], ref, e, f"{what}, rows from {r0}")
+        fb.assert_within(out[sl], ref, e, f"{what}, rows from {r0}")
         ratio = fb.worst_ratio(out[sl], ref, e)
         if ratio > WORST["norms"]:
             WORST["norms"], WORST["where"] = ratio, what

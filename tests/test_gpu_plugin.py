@@ -6,7 +6,9 @@ import os
 import numpy as np
 import pytest
 import torch
-from torch.utils.data import DataLoader
+
+from decoder_support import salmonn_batch
+from gpu_support import stop_after_a_device_fault  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -18,16 +20,6 @@ def model():
     return m.eval()
 
 
-def _batch(model, fewshot_mode, input_mode="speech_only", n=2, bs=2, num_examples=2, secs=3.0, vary=True):
-    from icl_speech_text_llm_amd.data.model_processors import get_processor
-    from icl_speech_text_llm_amd.data.synthetic_dataset import SyntheticICLDataset
-    from icl_speech_text_llm_amd.data.task_configs import DatasetType
-    proc = get_processor("salmonn", model.input_processor, model.llama_tokenizer)
-    ds = SyntheticICLDataset(proc, [DatasetType.VOXCELEB], n_items=n, fewshot_mode=fewshot_mode, input_mode=input_mode,
-                             audio_seconds=secs, num_examples=num_examples, vary_length=vary)
-    return next(iter(DataLoader(ds, batch_size=bs, collate_fn=proc.collate_batch)))
-
-
 def _oracle_llama(model, rnd):
     from oracle import models as om
     sd = {k[len("llama_model."):]: v.float().cpu() for k, v in model.salmonn.state_dict().items() if k.startswith("llama_model.")}
@@ -37,7 +29,7 @@ def _oracle_llama(model, rnd):
 
 def test_generate_output_text_and_speech_fewshot(model):
     for few in ("text", "speech"):
-        b = _batch(model, few)
+        b = salmonn_batch(model, few)
         out = model.generate_output({k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()})
         assert isinstance(out, list) and len(out) == 2 and all(isinstance(s, str) for s in out)
     assert model.batch_counter == 2
@@ -47,7 +39,7 @@ def test_one_overlong_row_costs_its_own_utterance_only(model):
     """a prompt over max_pos fails ITS row, validated on the host before any launch — the other
     rows of the batch are generated as if it were not there (the reference runs batch 1: one long prompt costs one utterance,
     inference/inference.py:370-373).  Batch of 4, row 1 made 2600 byte-tokens long (tiny model: max_pos 2048)."""
-    b = _batch(model, "text", n=4, bs=4)
+    b = salmonn_batch(model, "text", n=4, bs=4)
     b = {k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
     good = model.generate_ids(dict(b), want_first_logits=True)
     assert good.dropped == () and model.last_dropped_rows == ()
@@ -74,7 +66,7 @@ def test_beam_search_through_the_plugins(model):
     (models/multi_task_model.py:142) reach the beam kernels; the plugin's answer is the runtime's and the oracle's."""
     from oracle import models as om
     from icl_speech_text_llm_amd.models.model_factory import ModelFactory
-    b = _batch(model, "text", n=2, bs=2)
+    b = salmonn_batch(model, "text", n=2, bs=2)
     b = {k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
     greedy = model.generate_ids(dict(b))
     beams = model.generate_ids(dict(b, num_beams=3, length_penalty=1.0, max_new_tokens=6), want_first_logits=True)
@@ -95,7 +87,7 @@ def test_beam_search_through_the_plugins(model):
     tasks = {"beamed": {"max_new_tokens": 4, "num_beams": 2}}
     m = ModelFactory.create_model("salmonn", multi_task=True, task_configs=tasks, default_task="beamed", device="cuda",
                                   arch="tiny", llama_path="none").eval()
-    bb = dict(_batch(m.model, "text", n=2, bs=2))
+    bb = dict(salmonn_batch(m.model, "text", n=2, bs=2))
     bb = {k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in bb.items()}
     bb["task"] = ["beamed", "beamed"]
     out = m.generate_output(bb)
@@ -106,14 +98,14 @@ def test_clips_longer_than_30_seconds_keep_their_extra_windows(model):
     """SALMONN pads the SHORTER of the Whisper / BEATs streams (external package; call site models/custom_salmon.py:420-430): the
     feature extractor truncates Whisper's input to 30 s = 1500 frames, BEATs sees the whole collated waveform, so a 30.8 s batch
     carries 1536 frames -> 90 speech tokens per clip instead of 88, in the prompt and in the generated answer's context."""
-    b = _batch(model, "speech", n=2, bs=2, num_examples=1, secs=30.8, vary=False)
+    b = salmonn_batch(model, "speech", n=2, bs=2, num_examples=1, secs=30.8, vary=False)
     b = {k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
     sp, sa, ee, ea = model.get_speech_embeddings(dict(b))
     assert sp.shape[:2] == (2, 90) and sa.shape == (2, 90) and ee[0][0].shape[0] == 90 and ea[0][0].shape[0] == 90
     assert bool(torch.isfinite(sp).all())
     out = model.generate_output(dict(b))
     assert len(out) == 2
-    short = _batch(model, "speech", n=2, bs=2, num_examples=1, secs=3.0, vary=False)
+    short = salmonn_batch(model, "speech", n=2, bs=2, num_examples=1, secs=3.0, vary=False)
     short = {k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in short.items()}
     assert model.get_speech_embeddings(short)[0].shape[:2] == (2, 88)
     # a 3 s clip collated with the 30.8 s one: the reference's BEATs sees BOTH at the collated width (padding mask), so the short
@@ -140,7 +132,7 @@ def test_clips_longer_than_30_seconds_keep_their_extra_windows(model):
 
 def test_get_speech_embeddings_matches_oracle_batch1(model):
     from oracle import audio_frontend as af, models as om
-    b = _batch(model, "speech", n=1, bs=1, num_examples=2, vary=True)
+    b = salmonn_batch(model, "speech", n=1, bs=1, num_examples=2, vary=True)
     sp, sa, ee, ea = model.get_speech_embeddings(dict(b))
     assert sp.shape == (1, 88, model.cfg.llama.hidden) and sa.shape == (1, 88) and sa.dtype == torch.long
     assert len(ee) == 1 and len(ee[0]) == 2 and ee[0][0].shape == (88, model.cfg.llama.hidden)
@@ -169,7 +161,7 @@ def test_get_speech_embeddings_matches_oracle_batch1(model):
 def test_forward_loss_logits_labels(model):
     from icl_speech_text_llm_amd.models.custom_salmon import build_labels
     from oracle import models as om
-    b = _batch(model, "text", n=1, bs=1)
+    b = salmonn_batch(model, "text", n=1, bs=1)
     out = model.forward({k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()})
     logits, labels, loss = out["logits"], out["labels"], out["loss"]
     B, S, V = logits.shape
@@ -192,7 +184,7 @@ def test_forward_loss_logits_labels(model):
 
 
 def test_ragged_batch_and_equal_length_wrap(model):
-    b = _batch(model, "text", n=2, bs=2)
+    b = salmonn_batch(model, "text", n=2, bs=2)
     assert len(set(len(p) for p in b["prompt"])) >= 1
     out = model.generate_output({k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()})
     assert len(out) == 2
@@ -367,7 +359,7 @@ def test_multi_task_model_applies_per_task_generation_knobs():
     m = ModelFactory.create_model("salmonn", multi_task=True, task_configs=tasks, default_task="short", device="cuda",
                                   arch="tiny", llama_path="none").eval()
     assert m.current_task == "short" and m.llama_tokenizer is m.model.llama_tokenizer
-    b = _batch(m.model, "text", n=2, bs=2)
+    b = salmonn_batch(m.model, "text", n=2, bs=2)
     b = {k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
     ids_short = [m.llama_tokenizer(t, add_special_tokens=False)["input_ids"] for t in m.generate_output(dict(b))]
     assert b.get("max_new_tokens") is None

@@ -13,21 +13,19 @@ import pytest
 import torch
 
 import fp64_bounds as fb
+from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 SENT = 7.0
 GUARD_TOP, GUARD_BOT = 8, 3
 EPIS = ("plain", "gelu", "res", "gelu_res", "swiglu")
 RATIOS = {}
 
 
-@pytest.fixture(scope="module")
-def B():
-    import icl_speech_text_llm_amd.runtime.binding as b
-    b.load_library()
-    yield b
+@pytest.fixture(scope="module", autouse=True)
+def _report_worst():
+    yield
     for grp in sorted(RATIOS):
         print(f"\nworst err/bound, group {grp}: {RATIOS[grp]:.4f}")
 
@@ -111,7 +109,7 @@ def _run(B, grp, M, N, K, *, tile, out_dtype, epi, with_bias, res="f32", variant
     if out_dtype == torch.bfloat16:
         e = fb.bf16_out_bound(e, ref, out)
     what = f"tile {tile} {M}x{N}x{K} {epi} {'bias ' if with_bias else ''}{str(out_dtype)[6:]} out, {res} res, {variant}"
-    fb._assert_within(out, ref, e, what)
+    fb.assert_within(out, ref, e, what)
     _assert_guard(buf, out, what)
     _note(grp, out, ref, e)
     return out
@@ -286,7 +284,7 @@ def test_whisper_conv1_form(B, tile):
     ref, e = fb.gemm_ref_bound(dot, mag, 384, bias=bias, gelu=True)
     got = x2[:, 1:T + 1]
     e = fb.bf16_out_bound(e, ref, got)
-    fb._assert_within(got.reshape(n * T, d), ref.reshape(n * T, d), e.reshape(n * T, d), f"conv1 form, tile {tile}")
+    fb.assert_within(got.reshape(n * T, d), ref.reshape(n * T, d), e.reshape(n * T, d), f"conv1 form, tile {tile}")
     assert bool((x2[:, 0] == 0).all()) and bool((x2[:, T + 1] == 0).all()), "conv1 wrote a padding row"
     assert bool((buf[0] == SENT).all()) and bool((buf[-1] == SENT).all())
     _note("e", got, ref, e)
@@ -307,7 +305,7 @@ def test_whisper_conv2_form(B, tile):
     a = torch.cat([x2[:, j:j + 2 * T:2][:, :T] for j in range(3)], -1)  # [n, T, 3d]
     dot, mag = fb.dot64(a, w)
     ref, e = fb.gemm_ref_bound(dot, mag, 3 * d, bias=bias, residual=pos, gelu=True)
-    fb._assert_within(h.reshape(n * T, d), ref.reshape(n * T, d), e.reshape(n * T, d), f"conv2 form, tile {tile}")
+    fb.assert_within(h.reshape(n * T, d), ref.reshape(n * T, d), e.reshape(n * T, d), f"conv2 form, tile {tile}")
     assert bool((buf[0] == SENT).all()) and bool((buf[-1] == SENT).all())
     _note("e", h, ref, e)
 
@@ -344,7 +342,7 @@ def test_beats_posconv_form(B, g, tile):
     dot, mag = fb.dot64(a, w)
     ref, e = fb.gemm_ref_bound(dot, mag, K, bias=bg, residual=x[:, g * cpg:(g + 1) * cpg], gelu=True)
     got = y[:, g * cpg:(g + 1) * cpg]
-    fb._assert_within(got, ref, e, f"pos-conv form, group {g}, tile {tile}")
+    fb.assert_within(got, ref, e, f"pos-conv form, group {g}, tile {tile}")
     for buf in (ybuf, zbuf):
         chk = buf.clone()
         chk[1:1 + n * T, g * cpg:(g + 1) * cpg] = SENT

@@ -18,30 +18,15 @@ import pytest
 import torch
 
 import qknorm_ref as qr
-from test_gpu_gqa import _prompts, _teacher_forced_check, _w_prime_state
+from decoder_support import llama_oracle, row_prompts, teacher_forced_check
+from fp8_ref import w_prime_state
+from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 PARITY_RATIO = 1.25       # the project's margin between two runs that differ only in summation order
 MAX_LEN = 16
 NAN = float("nan")
-
-
-@pytest.fixture(scope="module")
-def B():
-    import icl_speech_text_llm_amd.runtime.binding as b
-    b.load_library()
-    return b
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_a_device_fault():
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:       # nothing more may be launched on a faulted device
-        pytest.exit(f"device fault: {e}", returncode=3)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -179,13 +164,6 @@ def _llama(base, kv, qk_norm=True, **kw):
     return replace(base, hidden=512, n_layers=2, n_heads=4, n_kv_heads=kv, ffn=1024, qk_norm=qk_norm, **kw)
 
 
-def _oracle(sd, c, rnd=True, prefix="llama_model."):
-    from oracle import models as om
-    lsd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
-    cls = qr.QKNormOracle if c.qk_norm else om.LlamaOracle
-    return cls(lsd, c.n_heads, c.rms_eps, c.rope_theta, c.lora_scale, rnd=om.bf16_round if rnd else None, n_kv_heads=c.kv_heads)
-
-
 class _Env:
     def __init__(self, kv, qk_norm=True, **rt_kw):
         from icl_speech_text_llm_amd.runtime import synth
@@ -233,22 +211,22 @@ def _plain_ratio(kv, which):
         if kv not in _plain_envs:
             _plain_envs[kv] = _Env(kv, qk_norm=False)
         p = _plain_envs[kv]
-        prompts = _prompts(p.cfg.llama.vocab, LENS[which], seed=7)
-        _plain_ratios[kv, which] = _step_ratios(p.rt, _oracle(p.sd, p.cfg.llama), _oracle(p.sd, p.cfg.llama, rnd=False), prompts,
+        prompts = row_prompts(p.cfg.llama.vocab, LENS[which], seed=7)
+        _plain_ratios[kv, which] = _step_ratios(p.rt, llama_oracle(p.sd, p.cfg.llama), llama_oracle(p.sd, p.cfg.llama, rnd=False), prompts,
                                                 f"plain decoder kv={kv} {which}")
     return _plain_ratios[kv, which]
 
 
 @pytest.mark.parametrize("which", ["4rows", "12rows"])
 def test_decoder_chain(env, which):
-    """Prefill + 10 decode steps, teacher-forced against QKNormOracle: the token criteria of _teacher_forced_check (2x / 4x the
+    """Prefill + 10 decode steps, teacher-forced against QKNormOracle: the token criteria of teacher_forced_check (2x / 4x the
     step's own error) and the ratio criterion of the module docstring at every step of every row."""
     c = env.cfg.llama
     assert c.qk_norm and env.rt.llama.w.layers[0].q_gamma.shape == (128,)
-    prompts = _prompts(c.vocab, LENS[which], seed=7)
-    ob_b, ob_f = _oracle(env.sd, c), _oracle(env.sd, c, rnd=False)
+    prompts = row_prompts(c.vocab, LENS[which], seed=7)
+    ob_b, ob_f = llama_oracle(env.sd, c), llama_oracle(env.sd, c, rnd=False)
     tag = f"qk-norm decoder kv={c.n_kv_heads} {which}"
-    e = _teacher_forced_check(env.rt, ob_b, prompts, tag)
+    e = teacher_forced_check(env.rt, ob_b, prompts, tag)
     print(f"{tag}: worst step rel-L2 (teacher-forced check) {e:.3e}")
     ratio = _step_ratios(env.rt, ob_b, ob_f, prompts, tag)
     plain = _plain_ratio(c.n_kv_heads, which)
@@ -260,8 +238,8 @@ def test_forward_logits_graph_chunks_and_sampling(env):
     """The same model through the other paths: teacher-forced forward (no cache) under the ratio criterion; captured-graph
     decode and chunked prefill torch.equal to the eager / unchunked run; a seeded sampled run repeats."""
     c, rt = env.cfg.llama, env.rt
-    prompts = _prompts(c.vocab, [37, 150, 64], seed=3)
-    ob_b, ob_f = _oracle(env.sd, c), _oracle(env.sd, c, rnd=False)
+    prompts = row_prompts(c.vocab, [37, 150, 64], seed=3)
+    ob_b, ob_f = llama_oracle(env.sd, c), llama_oracle(env.sd, c, rnd=False)
     fwd = lambda ob: torch.cat([ob.forward(ob.embed(torch.tensor(p[0]))[None])[0][0] for p in prompts])
     want_b, want_f = fwd(ob_b), fwd(ob_f)
     got, n = rt.forward_logits(prompts, None)
@@ -270,7 +248,7 @@ def test_forward_logits_graph_chunks_and_sampling(env):
     if c.n_kv_heads not in _plain_envs:
         _plain_envs[c.n_kv_heads] = _Env(c.n_kv_heads, qk_norm=False)
     p = _plain_envs[c.n_kv_heads]
-    pb, pf = _oracle(p.sd, p.cfg.llama), _oracle(p.sd, p.cfg.llama, rnd=False)
+    pb, pf = llama_oracle(p.sd, p.cfg.llama), llama_oracle(p.sd, p.cfg.llama, rnd=False)
     fwd_p = lambda ob: torch.cat([ob.forward(ob.embed(torch.tensor(q[0]))[None])[0][0] for q in prompts])
     plain_f = fwd_p(pf)
     plain = _rel(p.rt.forward_logits(prompts, None)[0].float().cpu(), plain_f) / _rel(fwd_p(pb), plain_f)
@@ -281,17 +259,17 @@ def test_forward_logits_graph_chunks_and_sampling(env):
     # captured-graph decode == eager
     rt._graphs.clear(); rt._graph_warm.clear()
     lens = [21, 40, 33]
-    outs = [rt.generate(_prompts(c.vocab, lens, seed=s), None, max_new_tokens=8, suppress_eos=True).tokens.clone() for s in (11, 12, 13, 11)]
+    outs = [rt.generate(row_prompts(c.vocab, lens, seed=s), None, max_new_tokens=8, suppress_eos=True).tokens.clone() for s in (11, 12, 13, 11)]
     assert len(rt._graphs) == 1 and torch.equal(outs[0], outs[3])
     rt.use_graphs = False
     try:
-        eager = rt.generate(_prompts(c.vocab, lens, seed=13), None, max_new_tokens=8, suppress_eos=True).tokens
+        eager = rt.generate(row_prompts(c.vocab, lens, seed=13), None, max_new_tokens=8, suppress_eos=True).tokens
     finally:
         del rt.use_graphs
     assert torch.equal(eager, outs[2])
 
     # chunked prefill == unchunked
-    many = _prompts(c.vocab, [37, 64, 5, 50, 21, 44, 9], seed=4100)
+    many = row_prompts(c.vocab, [37, 64, 5, 50, 21, 44, 9], seed=4100)
     try:
         rt.prefill_chunk = 128
         want = rt.generate(many, None, max_new_tokens=6, suppress_eos=True, want_first_logits=True)
@@ -319,9 +297,9 @@ def test_margin_weights_beam(kv):
     cfg = replace(tiny, llama=_llama(tiny.llama, kv))
     sd = synth.salmonn_state(cfg, seed=1, parts=("llama",), margin=True)
     rt = SalmonnRuntime(cfg, dict(sd), device=DEV, parts=("llama",))
-    prompts = _prompts(cfg.llama.vocab, [33, 90, 61], seed=21)
+    prompts = row_prompts(cfg.llama.vocab, [33, 90, 61], seed=21)
     beams = rt.generate(prompts, None, max_new_tokens=5, suppress_eos=True, num_beams=3)
-    ob = _oracle(sd, cfg.llama)
+    ob = llama_oracle(sd, cfg.llama)
     for b, p in enumerate(prompts):
         want = ob.generate_beam(ob.embed(torch.tensor(p[0]))[None], 5, -1, cfg.llama.pad_id, 3, 1.0)
         assert beams.tokens[b, :want.shape[1]].tolist() == want[0].tolist(), b
@@ -333,13 +311,13 @@ def test_fp8_weight_mode(env):
     from icl_speech_text_llm_amd.runtime.salmonn import SalmonnRuntime
     c = env.cfg.llama
     r8 = SalmonnRuntime(env.cfg, dict(env.sd), device=DEV, parts=("llama",), llm_weight_dtype="fp8")
-    wsd = _w_prime_state(env.sd, c)
+    wsd = w_prime_state(env.sd, c)
     assert all(torch.equal(wsd[k], env.sd[k]) for k in wsd if k.endswith("_norm.weight"))
-    ob_b, ob_f = _oracle(wsd, c), _oracle(wsd, c, rnd=False)
+    ob_b, ob_f = llama_oracle(wsd, c), llama_oracle(wsd, c, rnd=False)
     for which in ("4rows", "12rows"):
-        prompts = _prompts(c.vocab, LENS[which], seed=7)
+        prompts = row_prompts(c.vocab, LENS[which], seed=7)
         tag = f"fp8 weight mode, qk-norm kv={c.n_kv_heads} {which}"
-        _teacher_forced_check(r8, ob_b, prompts, tag)
+        teacher_forced_check(r8, ob_b, prompts, tag)
         ratio = _step_ratios(r8, ob_b, ob_f, prompts, tag)
         plain = _plain_ratio(c.n_kv_heads, which)
         print(f"{tag}: ratio {ratio:.3f}, plain decoder {plain:.3f}")
@@ -423,7 +401,7 @@ def test_qwen_runtime_with_a_qk_norm_llm():
     from icl_speech_text_llm_amd.runtime.config import QwenAudioCfg
     from icl_speech_text_llm_amd.runtime.qwen import QwenAudioRuntime
     q = QwenAudioCfg.tiny()
-    prompts = _prompts(q.llm.vocab - 1, [37, 150, 64], seed=9)            # below the audio token id
+    prompts = row_prompts(q.llm.vocab - 1, [37, 150, 64], seed=9)            # below the audio token id
     ratios = {}
     for qk_norm in (True, False):
         cfg = replace(q, llm=_llama(q.llm, 2, qk_norm))
@@ -431,7 +409,7 @@ def test_qwen_runtime_with_a_qk_norm_llm():
         sd = synth.qwen_audio_state(cfg, seed=0)
         assert ("language_model.model.layers.0.self_attn.k_norm.weight" in sd) == qk_norm
         rt = QwenAudioRuntime(cfg, dict(sd), device=DEV)
-        ob_b, ob_f = (_oracle(sd, cfg.llm, rnd, prefix="language_model.") for rnd in (True, False))
+        ob_b, ob_f = (llama_oracle(sd, cfg.llm, "language_model.", rnd) for rnd in (True, False))
         fwd = lambda ob: torch.cat([ob.forward(ob.embed(torch.tensor(p[0]))[None])[0][0] for p in prompts])
         want_b, want_f = fwd(ob_b), fwd(ob_f)
         got = rt.forward_logits(prompts, None)[0].float().cpu()

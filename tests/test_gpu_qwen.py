@@ -4,6 +4,9 @@ import numpy as np
 import pytest
 import torch
 
+from decoder_support import qwen_chat_batch
+from gpu_support import stop_after_a_device_fault  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -22,22 +25,9 @@ def _oracle_sd(model):
     return {k: v.float().cpu() for k, v in model.model.state_dict().items()}
 
 
-def _batch(model, secs=(2.5, 7.0)):
-    p = model.input_processor
-    audios = [np.clip(np.random.default_rng(10 + i).normal(0, 0.1, int(16000 * s)), -1, 1).astype(np.float32) for i, s in enumerate(secs)]
-    conv = [{"role": "system", "content": "Classify the sentiment."},
-            {"role": "user", "content": [{"type": "text", "text": "Here are few examples to learn from:\n"},
-                                         {"type": "audio", "audio_url": "x"}, {"type": "text", "text": "Label: positive\n"},
-                                         {"type": "text", "text": "\nNow analyze this input:\n"}, {"type": "audio", "audio_url": "y"}]}]
-    text = p.apply_chat_template(conv, add_generation_prompt=True, tokenize=False)
-    enc = p(text=text + "negative<|im_end|>", audios=audios, return_tensors="pt", sampling_rate=16000)
-    prompt_len = p(text=text, audios=audios).input_ids.shape[1]
-    return enc, prompt_len, audios
-
-
 def test_audio_tower_matches_oracle(model):
     from oracle import audio_frontend as af, models as om
-    enc, _, audios = _batch(model)
+    enc, _, audios = qwen_chat_batch(model)
     feats, out_lens = model.runtime.encode_audio(input_features=enc.input_features, mel_lens=enc.feature_attention_mask.sum(-1).tolist())
     sd = _oracle_sd(model)
     spec = torch.stack([torch.from_numpy(af.whisper_logmel(a, n_mels=128)) for a in audios])
@@ -52,7 +42,7 @@ def test_audio_tower_matches_oracle(model):
 
 def test_forward_and_generate_match_oracle(model):
     from oracle import audio_frontend as af, models as om
-    enc, prompt_len, audios = _batch(model)
+    enc, prompt_len, audios = qwen_chat_batch(model)
     batch = {"input_ids": enc.input_ids, "attention_mask": enc.attention_mask, "input_features": enc.input_features,
              "feature_attention_mask": enc.feature_attention_mask, "prompt_length": torch.tensor([prompt_len])}
     out = model.forward(batch)
@@ -107,7 +97,7 @@ def test_forward_and_generate_match_oracle(model):
 
 def test_padded_batch_rows_are_packed(model):
     """Two rows of different length (right padded) in one batch: padding is stripped through attention_mask."""
-    enc, prompt_len, _ = _batch(model)
+    enc, prompt_len, _ = qwen_chat_batch(model)
     ids = enc.input_ids[0, :prompt_len]
     short = ids[: prompt_len - 4]
     # second row: text-only suffix of the prompt (no audio tokens) so the audio count still matches
@@ -138,7 +128,7 @@ def test_audio_longer_than_30_seconds_is_truncated_like_the_feature_extractor(mo
     """WhisperFeatureExtractor (inside the reference's Qwen2-Audio processor, models/custom_qwen.py:57) cuts every clip to 30 s =
     3000 mel frames = 750 audio tokens: a 31.5 s clip must expand to 750 placeholders and match the oracle on the first 30 s."""
     from oracle import audio_frontend as af, models as om
-    enc, prompt_len, audios = _batch(model, secs=(31.5, 2.0))
+    enc, prompt_len, audios = qwen_chat_batch(model, secs=(31.5, 2.0))
     mel_lens = enc.feature_attention_mask.sum(-1).tolist()
     assert mel_lens[0] == 3000 and int((enc.input_ids[0] == model.cfg.audio_token_id).sum()) == 750 + ((200 - 1) // 2 + 1 - 2) // 2 + 1
     feats, out_lens = model.runtime.encode_audio(input_features=enc.input_features, mel_lens=mel_lens)

@@ -8,22 +8,16 @@ Miniature Llama dims with head_dim 128 (hidden 256, 2 heads, LoRA present), so t
 attention.  The ragged lengths straddle the 32-row wave block, the 64-key tile and the 128-row q-block."""
 import os
 
-import numpy as np
 import pytest
 import torch
 
+from decoder_support import row_prompts
+from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 LENS = [1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 376]
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 EOS, PAD = 2, 400
-
-
-@pytest.fixture(scope="module")
-def B():
-    import icl_speech_text_llm_amd.runtime.binding as b
-    b.load_library()
-    return b
 
 
 def _cu(lens):
@@ -111,17 +105,13 @@ def env():
     return cfg, rt
 
 
-def _prompts(cfg, lens, seed=99):
-    return [[np.random.default_rng(seed + i).integers(3, cfg.llama.vocab - 1, n).tolist()] for i, n in enumerate(lens)]
-
-
 def test_trimmed_prefill_matches_the_full_prefill_bitwise(B, env):
     """prefill(last_rows_only=True) == the last rows of the full prefill, and every layer's K and V cache planes are the same
     bits after either (LoRA present: the augmented columns of the gathered rows are covered)."""
     cfg, rt = env
     c, ll, ws = cfg.llama, rt.llama, rt.ws
     assert ll.prefill_last_rows and B.rope_epilogue_ok(c.n_heads, c.head_dim, ll.w.k_aug)
-    prompts = _prompts(cfg, LENS, seed=4300)
+    prompts = row_prompts(cfg.llama.vocab, LENS, seed=4300)
     last_idx = torch.tensor([e - 1 for e in _cu(LENS)[1:]], device=DEV)
 
     def run(trim):
@@ -166,7 +156,7 @@ def test_generation_is_unchanged_by_the_switch(env, auto, mode, batch):
     greedy, label-constrained and 4-beam decoding; one prompt, and 11 prompts prefilled in chunks of 4 (a ragged last chunk)."""
     cfg, rt = env
     lens = LENS[-1:] if batch == "one" else LENS
-    prompts = _prompts(cfg, lens, seed=4400)
+    prompts = row_prompts(cfg.llama.vocab, lens, seed=4400)
     kw = dict(max_new_tokens=4, want_first_logits=True)
     if mode == "greedy":
         kw.update(suppress_eos=True)
