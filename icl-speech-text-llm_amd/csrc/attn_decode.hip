@@ -1,5 +1,5 @@
 // attn_decode.hip — single-token decode attention over the KV cache (HBM-bound KV stream): ONE kernel,
-// attn_decode_kernel<D, UNR, FUSE, F8, EPL, NG>, behind every icl_attn_decode_* entry point.
+// attn_decode_kernel<D, UNR, FUSE, F8, EPL, NG, MASK>, behind every icl_attn_decode_* entry point.
 // Cache layout [n_seqs][n_heads][max_len][D] bf16: the keys of one (sequence, head) are one
 // contiguous stream, read with 16-B loads straight to VGPRs (no LDS round trip: guide §5 table row
 // "GEMV / M <= 16 decode").  D/8 lanes cover one key row, so a wave-instruction fetches 64/(D/8)
@@ -38,6 +38,18 @@ constexpr float LOG2E = 1.4426950408889634f;
 // FMA contraction.  The state (q chunk, m, l, o[8]) is 18 VGPRs per head, so UNR shrinks as NG grows.  The K / V
 // conversions (kv_words) stay inside the per-head loop, next to their uses: the identity for bf16, and hoisted out of it they cost
 // the fp8 instantiations 43-85 VGPRs (196 -> 261 at <128, 8, false, true, 16>: a whole key group's converted rows live at once).
+// MASK (icl_attn_decode_masked_bf16, attention knockout): a row LIST instead of all sequences and a per-key, per-head segment
+// mask; bf16, no RoPE-fused and no fp8 form.  ONE UNR per (head_dim, group size), whatever the grid: the few / many switch of
+// the unmasked multi-head launches changes bits (measured: a row alone at UNR 16 against the same row among 1056 workgroups at
+// UNR 4), and a knockout result must not depend on the batch a row travels in.  Multi-head takes 8 — between the two: 116 VGPRs
+// and 4 waves per SIMD, against 201 / 2 at UNR 16 and 102 / 4 at UNR 4 — grouped the unmasked kernel's UNR (the mask costs UNR
+// bytes in flight and NG wave-uniform words).  -Rpass-analysis=kernel-resource-usage for gfx950, VGPRs / SGPRs / waves per
+// SIMD, masked (the unmasked instantiation of the same <D, UNR, NG>); no instantiation uses scratch or spills a VGPR:
+//   <64, 8, .., 1>    115 / 43 / 4                      <128, 8, .., 1>   116 / 43 / 4
+//   <128, 8, .., 2>   160 / 43 / 3  (151 / 32 / 3)      <128, 4, .., 3>   125 / 54 / 4  (121 / 36 / 4)
+//   <128, 4, .., 4>   152 / 59 / 3  (160 / 32 / 3)      <128, 4, .., 5>   169 / 76 / 2  (165 / 42 / 3)
+//   <128, 4, .., 6>   212 / 91 / 2  (206 / 42 / 2)      <128, 4, .., 7>   241 / 104 / 2 (239 / 46 / 2)
+//   <128, 4, .., 8>   256 + 3 AGPRs / 101 / 1  (254 / 32 / 2): UNR 4 is the smallest there is, so G = 8 runs one wave per SIMD
 struct DecodeRope {
   const float* cosT;
   const float* sinT;
@@ -49,6 +61,17 @@ struct DecodeRope {
   float* vs;
   int64_t k_off, v_off;   // column offsets of k / v in the qkv row
 };
+
+// MASK: the list and the per-key mask of icl_attn_decode_masked_bf16, behind the (unused, zero) DecodeRope of a MASK = false launch
+struct DecodeMask : DecodeRope {
+  const unsigned char* seg;   // seg[row_seq[r] * ld_seg + key]: the segment of a key
+  int64_t ld_seg;
+  const unsigned* blocked;    // blocked[r * (query heads) + head]: bit g = segment g is not read
+  const int* row_seq;         // list entry r: the cache sequence ...
+  const int* row_q;           // ... and the row of Q / O
+};
+template <bool MASK> struct DecodeTail { typedef DecodeRope T; };
+template <> struct DecodeTail<true> { typedef DecodeMask T; };
 
 template <int EPL> struct KvWords;                       // EPL bf16 of a lane: EPL / 2 dwords
 template <> struct KvWords<8> { typedef u32x4 T; };
@@ -73,15 +96,21 @@ __device__ __forceinline__ typename KvWords<EPL>::T kv_words(typename KvRaw<F8, 
 }
 
 // blockIdx.x = h, a head of the CACHE (n_heads of them); its query heads are h * NG + g.
-template <int D, int UNR, bool FUSE, bool F8, int EPL, int NG>
+// MASK (icl_attn_decode_masked_bf16): blockIdx.y = r, an entry of a row LIST — cache sequence row_seq[r], row row_q[r] of Q / O —
+// and key j of query head hq counts iff j < len and not (seg_j < 32 and bit seg_j of blocked[r][hq]): the predicate joins ok[i].
+// One segment byte per key a lane group loads (UNR bytes in flight next to the UNR K / V rows); the NG masks of a K/V group are
+// wave-uniform (SGPRs) and each head's own mask meets the shared K / V chunk inside the per-head loop.  A stream folds the keys
+// the unmasked kernel gives it, in its groups of four: a masked key is a key past the end, s = NEG_BIG and p = 0.
+template <int D, int UNR, bool FUSE, bool F8, int EPL, int NG, bool MASK = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* Q, int64_t ldq, const void* Kc, const void* Vc,
                                                            const float* Ks, const float* Vs, unsigned short* O, int64_t ldo,
                                                            const int* lens, int n_heads, int max_len, float scale_log2e,
-                                                           DecodeRope rp) {
+                                                           typename DecodeTail<MASK>::T rp) {
   typedef typename KvRaw<F8, EPL>::T Raw;
   typedef typename KvWords<EPL>::T Wd;
   static_assert(!F8 || EPL == 16, "the fp8 cache is read 16 elements per lane");
   static_assert(NG == 1 || (!FUSE && !F8 && D == 128 && EPL == 8), "grouped-query: the plain bf16 form at head_dim 128 only");
+  static_assert(!MASK || (!FUSE && !F8 && EPL == 8), "masked: the plain bf16 forms only");
   constexpr int NW = EPL / 2;      // bf16 words per lane
   constexpr int EB = F8 ? 1 : 2;   // bytes per cache element
   constexpr int LPR = D / EPL;     // lanes per key row
@@ -91,8 +120,18 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
   const int h = blockIdx.x, b = blockIdx.y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int dc = lane % LPR, sub = lane / LPR;
-  const int len = min(lens[b], max_len);
-  const int crow = FUSE && rp.seq_ids ? rp.seq_ids[b] : b;
+  int bs = b, bq = b;              // the cache sequence, and the row of Q / O
+  unsigned blk[NG] = {};
+  const unsigned char* segp = nullptr;
+  if constexpr (MASK) {
+    bs = rp.row_seq[b];
+    bq = rp.row_q[b];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) blk[g] = rp.blocked[((int64_t)b * n_heads + h) * NG + g];
+    segp = rp.seg + (int64_t)bs * rp.ld_seg;
+  }
+  const int len = min(lens[bs], max_len);
+  const int crow = FUSE && rp.seq_ids ? rp.seq_ids[b] : bs;
   const int64_t base = ((int64_t)crow * n_heads + h) * (int64_t)max_len * D;
   const int64_t sbase = base / D;     // F8: the scale of row (crow, h, key) is Ks[sbase + key]
   const char* kp = (const char*)Kc + (base + dc * EPL) * EB;
@@ -157,7 +196,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
     }
   } else {
 #pragma unroll
-    for (int g = 0; g < NG; ++g) q_raw[g] = *(const Wd*)(Q + (int64_t)b * ldq + (h * NG + g) * D + dc * EPL);
+    for (int g = 0; g < NG; ++g) q_raw[g] = *(const Wd*)(Q + (int64_t)bq * ldq + (h * NG + g) * D + dc * EPL);
   }
   float q[NG][EPL], m[NG], l[NG], o[NG][EPL];
 #pragma unroll
@@ -182,6 +221,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
   for (int j0 = wave * KPW; j0 < len; j0 += 4 * KPW * UNR) {
     Raw kr[UNR], vr[UNR];
     float ksr[UNR], vsr[UNR];
+    unsigned sgr[UNR];                   // MASK: the keys' segment bytes
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const int key = min(j0 + u * 4 * KPW + sub, len - 1);
@@ -193,12 +233,17 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
       } else {
         ksr[u] = vsr[u] = 1.f;
       }
+      if constexpr (MASK) sgr[u] = segp[key];     // (turned into the key's mask bit below, once for the NG heads)
       if (FUSE && key == pos_new) {      // the row this launch appends: from registers (the store above may not have landed)
         kr[u] = k_new;
         vr[u] = v_new;
         ksr[u] = ks_new;
         vsr[u] = vs_new;
       }
+    }
+    if constexpr (MASK) {
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) sgr[u] = sgr[u] < 32u ? 1u << sgr[u] : 0u;     // ids >= 32 are never blocked
     }
 #pragma unroll
     for (int gk = 0; gk < UNR / G; ++gk) {
@@ -219,6 +264,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
 #pragma unroll
           for (int x = 1; x < LPR; x <<= 1) d += __shfl_xor(d, x, 64);
           ok[i] = j0 + u * 4 * KPW + sub < len;
+          if constexpr (MASK) ok[i] = ok[i] && !(blk[g] & sgr[u]);
           s[i] = ok[i] ? d : NEG_BIG;
         }
         const float m_new = fmaxf(fmaxf(m[g], fmaxf(s[0], s[1])), fmaxf(s[2], s[3]));
@@ -271,7 +317,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
       // F8: a NaN cache row (a non-finite appended k / v) makes L NaN, and the output of this (sequence, head) NaN; the bf16
       // kernel's L > 0 test would turn it into zeros.  Identical for every finite input.
       const bool live = F8 ? !(L <= 0.f) : L > 0.f;
-      O[(int64_t)b * ldo + (h * NG + g) * D + d] = f32_to_bf16_bits(live ? acc / L : 0.f);
+      O[(int64_t)bq * ldo + (h * NG + g) * D + d] = f32_to_bf16_bits(live ? acc / L : 0.f);
     }
   }
 }
@@ -384,6 +430,73 @@ extern "C" int icl_attn_decode_gqa_bf16(const void* Q, int64_t ldq, const void* 
   }
   return launch_attn_decode(Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_kv_heads, group, head_dim, max_len, scale,
                             nullptr, 8, stream, "icl_attn_decode_gqa_bf16");
+}
+
+// The masked form (attention knockout): the bf16 kernel over a row list, every key under its head's segment mask.  n_heads = heads
+// of the cache.  One UNR per form, no few / many switch: a row's bits do not depend on the list (the resource notes in the header).
+static int launch_attn_decode_masked(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O, int64_t ldo,
+                                     const int32_t* lens, const DecodeMask& mk, int32_t n_rows, int32_t n_heads, int group,
+                                     int32_t head_dim, int32_t max_len, float scale, void* stream, const char* who) {
+  dim3 grid(n_heads, n_rows);
+#define ICL_MASKED_CASE(DD, UU, GG)                                                                                            \
+  hipLaunchKernelGGL((attn_decode_kernel<DD, UU, false, false, 8, GG, true>), grid, dim3(256), 0, (hipStream_t)stream,         \
+                     (const unsigned short*)Q, ldq, Kc, Vc, (const float*)nullptr, (const float*)nullptr, (unsigned short*)O,  \
+                     ldo, lens, n_heads, max_len, scale * LOG2E, mk)
+#define ICL_MASKED_GQA_CASE(GG, UU) case GG: ICL_MASKED_CASE(128, UU, GG); break
+  if (group > 1) {
+    switch (group) {
+      ICL_MASKED_GQA_CASE(2, 8);
+      ICL_MASKED_GQA_CASE(3, 4);
+      ICL_MASKED_GQA_CASE(4, 4);
+      ICL_MASKED_GQA_CASE(5, 4);
+      ICL_MASKED_GQA_CASE(6, 4);
+      ICL_MASKED_GQA_CASE(7, 4);
+      ICL_MASKED_GQA_CASE(8, 4);
+    }
+  } else if (head_dim == 64) {
+    ICL_MASKED_CASE(64, 8, 1);
+  } else {
+    ICL_MASKED_CASE(128, 8, 1);
+  }
+#undef ICL_MASKED_GQA_CASE
+#undef ICL_MASKED_CASE
+  ICL_CHECK_LAUNCH(who);
+  return ICL_OK;
+}
+
+extern "C" int icl_attn_decode_masked_bf16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O, int64_t ldo,
+                                           const int32_t* lens, const uint8_t* seg, int64_t ld_seg, const uint32_t* blocked,
+                                           const int32_t* row_seq, const int32_t* row_q, int32_t n_rows, int32_t n_heads,
+                                           int32_t n_kv_heads, int32_t head_dim, int32_t max_len, float scale, void* stream) {
+#define WHO "icl_attn_decode_masked_bf16"
+  ICL_CHECK_ARG(n_rows > 0 && n_rows <= 65535, WHO ": n_rows=%d (1..65535 list entries)", n_rows);
+  ICL_CHECK_ARG(Q && Kc && Vc && O && lens && seg && blocked && row_seq && row_q,
+                WHO ": NULL pointer (Q / Kc / Vc / O / lens / seg / blocked / row_seq / row_q)");
+  ICL_CHECK_ARG(head_dim == 64 || head_dim == 128, WHO ": head_dim=%d (only 64 and 128)", head_dim);
+  ICL_CHECK_ARG(n_heads > 0 && max_len > 0, WHO ": n_heads=%d, max_len=%d must be positive", n_heads, max_len);
+  if (n_kv_heads == 0) n_kv_heads = n_heads;
+  ICL_CHECK_ARG(n_kv_heads > 0 && n_kv_heads <= 65535 && n_heads % n_kv_heads == 0,
+                WHO ": n_heads=%d is not a multiple of n_kv_heads=%d", n_heads, n_kv_heads);
+  const int group = n_heads / n_kv_heads;
+  ICL_CHECK_ARG(group <= 8, WHO ": %d query heads per K/V head (G at most 8)", group);
+  ICL_CHECK_ARG(group == 1 || head_dim == 128, WHO ": head_dim=%d with G=%d (grouped-query attention: only 128)", head_dim, group);
+  ICL_CHECK_ARG(ld_seg >= max_len, WHO ": ld_seg=%lld < max_len=%d", (long long)ld_seg, max_len);
+  ICL_CHECK_ARG(ldq % 8 == 0 && ((uintptr_t)Q & 15) == 0 && ((uintptr_t)Kc & 15) == 0 && ((uintptr_t)Vc & 15) == 0,
+                WHO ": misaligned Q / Kc / Vc (16 bytes, ldq %% 8 == 0)");
+  ICL_CHECK_ARG(((uintptr_t)blocked & 3) == 0, WHO ": misaligned blocked");
+  ICL_CHECK_ARG(ldq >= (int64_t)n_heads * head_dim && ldo >= (int64_t)n_heads * head_dim,
+                WHO ": ldq=%lld / ldo=%lld must hold n_heads * head_dim = %lld columns", (long long)ldq, (long long)ldo,
+                (long long)n_heads * head_dim);
+  ICL_CHECK_ARG(__builtin_isfinite(scale), WHO ": scale is not finite");
+  DecodeMask mk = {};
+  mk.seg = seg;
+  mk.ld_seg = ld_seg;
+  mk.blocked = blocked;
+  mk.row_seq = row_seq;
+  mk.row_q = row_q;
+  return launch_attn_decode_masked(Q, ldq, Kc, Vc, O, ldo, lens, mk, n_rows, n_kv_heads, group, head_dim, max_len, scale, stream,
+                                   WHO);
+#undef WHO
 }
 
 // the RoPE-fused forms: kscale / vscale NULL = the bf16 cache

@@ -642,6 +642,47 @@ class CustomSALMONN(BaseModel):
         res = self.runtime.prompt_attention(segs, speech, [self.piece_ids(s) for s in segs], n_seg=max(len(pc) for pc in pieces))
         return {"mass": res.mass, "pieces": pieces, "first_logits": res.first_logits}
 
+    def generate_knockout(self, samples: Dict[str, Any], block, layers=None, heads=None) -> Dict[str, Any]:
+        """Attention knockout, the causal companion of ``prompt_attention``: generate while the deciding positions — the last
+        prompt position and every generated one — cannot read the pieces in ``block``, in decoder layers ``layers`` (a half-open
+        range, None: all) and query heads ``heads`` (None: all).  ``block``: pieces in the vocabulary of ``prompt_attention``'s
+        ``pieces``, such as ``("example", 2)`` or ``("speech", 0)`` — one list for all rows, or one list per row (an empty list
+        leaves that row untouched).  A piece a row does not have, and more than 32 pieces in a row, are ``ValueError``s naming
+        the row, raised before anything is launched on the decoder.  Returns ``{"texts", "tokens": int64 [B, width] (CPU),
+        "first_logits": f32 [B, V] (device), "pieces"}``; generation knobs are read from the batch as ``generate_ids`` reads them
+        (greedy, sampled or label-constrained; no beams)."""
+        samples = self._host_counts(samples)
+        constraint = self._label_constraint(samples)
+        speech_embeds, _, example_embeds, _ = self.get_speech_embeddings(samples)
+        num_examples = samples.get("num_examples", torch.zeros(len(samples["prompt"]), dtype=torch.long))
+        segs, speech, pieces = self._segments_and_pieces(speech_embeds, samples["prompt"], num_examples, example_embeds)
+        block = list(block)
+        is_piece = lambda x: isinstance(x, (tuple, list)) and len(x) == 2 and isinstance(x[0], str)
+        per_row = len(block) > 0 and not any(is_piece(x) for x in block)      # one list per row (of pieces, possibly empty)
+        if per_row and len(block) != len(pieces):
+            raise ValueError(f"{len(block)} block lists for {len(pieces)} rows")
+        blocked = []
+        for b, pc in enumerate(pieces):
+            if len(pc) > self.MAX_PIECES:
+                raise ValueError(f"row {b}: {len(pc)} pieces in the wrapped prompt, a knockout blocks among at most {self.MAX_PIECES}")
+            ids = []
+            for piece in (block[b] if per_row else block):
+                piece = (str(piece[0]), int(piece[1]))
+                if piece not in pc:
+                    raise ValueError(f"row {b}: the wrapped prompt has no piece {piece} (its pieces: {pc})")
+                ids.append(pc.index(piece))
+            blocked.append(ids)
+        res = self.runtime.generate(segs, speech, max_new_tokens=int(samples.get("max_new_tokens", 10)),
+                                    eos_id=self.llama_tokenizer.eos_token_id, pad_id=self.llama_tokenizer.pad_token_id,
+                                    do_sample=bool(samples.get("do_sample", False)),
+                                    temperature=float(samples.get("temperature", 0.8)), top_p=float(samples.get("top_p", 0.9)),
+                                    top_k=int(self.hf_generation_defaults.get("top_k", 50)),
+                                    repetition_penalty=float(samples.get("repetition_penalty", 1.0)),
+                                    generator=samples.get("generator"), want_first_logits=True, overlong="drop",
+                                    num_beams=int(samples.get("num_beams", 1)), constraint=constraint,
+                                    knockout=([self.piece_ids(s) for s in segs], blocked, layers, heads))
+        return {"texts": self.decode_ids(res.tokens), "tokens": res.tokens, "first_logits": res.first_logits, "pieces": pieces}
+
     def _label_constraint(self, samples: Dict[str, Any]):
         """``(automaton, start states)`` for a batch that sets ``constrain_labels`` (one grammar per row, by its ``dataset_type``),
         else ``None``.  Automata are built once per set of dataset types from this model's tokenizer and kept."""

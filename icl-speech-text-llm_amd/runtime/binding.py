@@ -69,6 +69,9 @@ _SIGNATURES = {
                                          c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
     "icl_attn_segmass_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
                                       c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "icl_attn_decode_masked_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                            c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float,
+                                            c_void_p]),
     "icl_attn_decode_rope_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float,
                                           c_void_p]),
@@ -428,6 +431,30 @@ def attn_segmass(q, kcache, lens, seg, mass, n_heads: int, head_dim: int, max_le
                                                 probs.stride(1) if probs is not None else 0, n_seqs, n_heads, n_kv_heads,
                                                 head_dim, max_len, scale, _stream()), "icl_attn_segmass_bf16")
     return mass
+
+
+def attn_decode_masked(q, kcache, vcache, out, lens, seg, blocked, row_seq, row_q, n_heads: int, head_dim: int, max_len: int,
+                       scale: float, *, n_kv_heads: int = 0):
+    """Attention knockout (icl_attn_decode_masked_bf16): ``attn_decode`` / ``attn_decode_gqa`` for the listed rows only, every key
+    under a segment mask.  List entry r attends over cache sequence ``row_seq[r]`` (int32) with the query at row ``row_q[r]``
+    (int32) of ``q`` (bf16, already rotated) and writes that row of ``out``; other rows of ``out`` are not written.  seg: uint8
+    [n_seqs, >= max_len], the segment of every key; blocked: int32 (read as u32 bit sets) [n_listed, n_heads], bit g = that query
+    head does not read segment g (ids >= 32 are never blocked); lens: int32 [n_seqs], the keys of every cache sequence."""
+    _require_gpu(q, kcache, vcache, out, lens, seg, blocked, row_seq, row_q)
+    assert q.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and kcache.dtype == torch.bfloat16 and vcache.dtype == torch.bfloat16
+    assert lens.dtype == torch.int32 and seg.dtype == torch.uint8 and blocked.dtype == torch.int32
+    assert row_seq.dtype == torch.int32 and row_q.dtype == torch.int32
+    n_seqs, n_rows = lens.numel(), row_seq.numel()
+    assert row_q.numel() == n_rows and row_seq.is_contiguous() and row_q.is_contiguous()
+    assert seg.dim() == 2 and seg.shape[0] == n_seqs and seg.stride(1) == 1
+    assert blocked.is_contiguous() and blocked.dim() == 2 and tuple(blocked.shape) == (n_rows, n_heads)
+    assert kcache.shape[0] == n_seqs and vcache.shape[0] == n_seqs and q.stride(1) == 1 and out.stride(1) == 1
+    _check(load_library().icl_attn_decode_masked_bf16(q.data_ptr(), q.stride(0), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(),
+                                                      out.stride(0), lens.data_ptr(), seg.data_ptr(), seg.stride(0),
+                                                      blocked.data_ptr(), row_seq.data_ptr(), row_q.data_ptr(), n_rows, n_heads,
+                                                      n_kv_heads, head_dim, max_len, scale, _stream()),
+           "icl_attn_decode_masked_bf16")
+    return out
 
 
 def attn_decode_rope(qkv, k_off: int, v_off: int, cos, sin, pos, seq_ids, kcache, vcache, out, lens, n_heads: int,

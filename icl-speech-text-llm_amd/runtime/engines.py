@@ -10,7 +10,7 @@ Reference call sites: models/custom_salmon.py:546-554 (encode_speech), :115-299 
 from __future__ import annotations
 
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -609,8 +609,13 @@ class LlamaHIP:
     # ---- K10: prefill over ragged packed sequences ------------------------------------------------
     def prefill(self, ws: Workspace, h: torch.Tensor, seq_lens: List[int], cache: Optional["KVCache"] = None,
                 last_rows_only: bool = False, last_out: Optional[torch.Tensor] = None,
-                readout: Optional["AttnReadout"] = None) -> torch.Tensor:
+                readout: Optional["AttnReadout"] = None, knockout: Optional["Knockout"] = None) -> torch.Tensor:
         """h f32 [sum S_b, hidden] (modified in place) -> same buffer holding the final hidden states.
+
+        ``knockout`` (needs ``last_rows_only`` and a bf16 cache): attention knockout.  In a layer of its window, after the
+        layer's ordinary attention launch, one more launch (icl_attn_decode_masked_bf16) rewrites the attention output of the
+        listed sequences' LAST rows from their rotated q and the cache, which holds every prompt position by then in every
+        prefill form; every other row keeps its bits, and without it the layers launch what they launch.
 
         ``readout`` (needs ``last_rows_only`` and a bf16 cache): the prompt-attention readout.  In every layer, once q / k are
         rotated and k is in the cache, one more launch (icl_attn_segmass_bf16) writes the last row's attention mass per key
@@ -630,6 +635,7 @@ class LlamaHIP:
         assert max(seq_lens) <= c.max_pos
         assert cache is not None or not last_rows_only, "prefill(last_rows_only=True) needs a KV cache"
         assert readout is None or (last_rows_only and cache.dtype == "bf16"), "the attention readout reads the last rows' q and a bf16 K cache"
+        assert knockout is None or (last_rows_only and cache.dtype == "bf16"), "attention knockout rewrites the last rows from a bf16 KV cache"
         pos = _i32([p for s in seq_lens for p in range(s)], dev)
         sid = _i32([b for b, s in enumerate(seq_lens) for _ in range(s)], dev)
         cu = _i32(cu_h, dev)
@@ -652,11 +658,17 @@ class LlamaHIP:
             last_idx = _i32([e - 1 for e in cu_h[1:]], dev)
             out = last_out if last_out is not None else ws.get("pfl_h", (len(seq_lens), hd), F32)
         sites = prefill_sites(c, w.k_aug)
+        ko_lens = ko_rows = None
+        if knockout is not None:        # the prompt lengths as the masked launch's key counts; the listed sequences' last rows
+            ko_lens = _i32(seq_lens, dev)
+            ko_rows = _i32([cu_h[b + 1] - 1 for b in knockout.listed], dev)
         for i, L in enumerate(w.layers):
             kc, vc, ks, vs = cache.layer(i) if cache is not None else (None, None, None, None)
+            ko = knockout if knockout is not None and knockout.covers(i) else None
             if trim and i == len(w.layers) - 1:
                 return self._last_layer_rows(ws, L, h, seq_lens, pos, sid, cu, kc, vc, max_len, last_idx, out,
-                                             readout=None if readout is None else (readout, i))
+                                             readout=None if readout is None else (readout, i),
+                                             knockout=None if ko is None else (ko, ko_lens))
             xn = self._xn(ws, L, h, M, "pf_", decode=False)
             qkv = ws.get("pf_qkv", (M, qkv_width(c)), BF16)
             att = ws.get("pf_att", (M, hd), BF16)
@@ -693,11 +705,13 @@ class LlamaHIP:
             else:
                 B.attn_fwd(qkv[:, :k_off], qkv[:, k_off:v_off], qkv[:, v_off:], att, cu, maxS, H, D, D ** -0.5, causal=True,
                            n_kv_heads=c.kv_heads if gqa else 0)
+            if ko is not None:          # the listed last rows again, under their masks
+                ko.launch(qkv[:, :k_off], att, ko_rows, kc, vc, ko_lens, c, max_len)
             self._attn_out_mlp(ws, L, h, xn, att, "pf_", sites, None)
         return B.gather_rows(h, last_idx, out) if last_rows_only else h
 
     def _last_layer_rows(self, ws: Workspace, L, h, seq_lens: List[int], pos, sid, cu, kc, vc, max_len: int,
-                         last_idx, hg, readout=None) -> torch.Tensor:
+                         last_idx, hg, readout=None, knockout=None) -> torch.Tensor:
         """The last decoder layer of a prefill whose caller reads the last row of every sequence only: the layer's k / v are
         projected (and appended to the cache) for all M rows; q, the attention, o_proj, the post-attention norm and the MLP run
         on the len(seq_lens) gathered rows.  Exact, not approximate: every kernel here computes a row independently of its
@@ -727,6 +741,8 @@ class LlamaHIP:
         att = ws.get("pfl_att", (Bn, hd), BF16)
         B.attn_fwd(q, kc, vc, att, cu, max(seq_lens), H, D, D ** -0.5, causal=True, kv_cache_max_len=max_len,
                    cu_q=_i32(list(range(Bn + 1)), dev))
+        if knockout is not None:        # (Knockout, prompt lengths): gathered row b is sequence b's last row
+            knockout[0].launch(q, att, knockout[0].row_seq, kc, vc, knockout[1], c, max_len)
         self._attn_out_mlp(ws, L, hg, xg, att, "pfl_", prefill_sites(c, w.k_aug, tile=3), None)
         return hg
 
@@ -744,8 +760,12 @@ class LlamaHIP:
 
     # ---- K11: one decode step for Bn sequences -----------------------------------------------------
     def decode_step(self, ws: Workspace, cache: "KVCache", next_ids: torch.Tensor, pos: torch.Tensor,
-                    lens: torch.Tensor, sid: torch.Tensor) -> torch.Tensor:
+                    lens: torch.Tensor, sid: torch.Tensor, knockout: Optional["Knockout"] = None) -> torch.Tensor:
+        """``knockout`` (a bf16 cache): in a layer of its window one more launch (icl_attn_decode_masked_bf16) rewrites the listed
+        rows of the attention output under their masks.  The step then takes the two-launch RoPE + attention form at every batch
+        size — the fused launch leaves q unrotated in ``qkv``; the two forms are bit-identical — so unlisted rows keep their bits."""
         c, w = self.w.cfg, self.w
+        assert knockout is None or cache.dtype == "bf16", "attention knockout reads a bf16 KV cache"
         Bn = next_ids.numel()
         h = self.embed(ws, next_ids, None, name="dc_h")
         H, D = c.n_heads, c.head_dim
@@ -767,7 +787,7 @@ class LlamaHIP:
         # Same-box A/B (tools/ab_decode_rope.sh, profiles/r04_decode_rope_ab.txt): at 256 rows decode 143.2 -> 142.5 ms; at ONE
         # sequence 58.4 -> 59.6 ms per utterance — the rotation's dependent loads (pos -> cos / sin, q, k) sit in front of a
         # latency-bound attention and cost more than the 5-us launch they replace — so small batches keep the two launches.
-        fuse_rope = self.fuse_decode_rope and Bn > 8 and not c.qk_norm
+        fuse_rope = self.fuse_decode_rope and Bn > 8 and not c.qk_norm and knockout is None
         ready = False
         for i, L in enumerate(layers):
             kc, vc, ks, vs = cache.layer(i)
@@ -794,6 +814,8 @@ class LlamaHIP:
             else:
                 B.rope_kv(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, kc, vc, H, D, max_len, M=Bn)
                 B.attn_decode(qkv[:, :k_off], kc, vc, att, lens, H, D, max_len, scale)
+            if knockout is not None and knockout.covers(i):
+                knockout.launch(qkv[:, :k_off], att, knockout.row_seq, kc, vc, lens, c, max_len)
             nxt = (layers[i + 1].rms1, xn_next) if i + 1 < len(layers) else (w.norm, xn_final)
             ready = self._attn_out_mlp(ws, L, h, xn, att, "dc_", sites, wsk, next_norm=nxt)
         return self.logits(ws, h, name="dc_logits", xn_ready=ready)
@@ -821,6 +843,50 @@ class AttnReadout:
     def launch(self, layer: int, q: torch.Tensor, q_rows: Optional[torch.Tensor], kc: torch.Tensor, cfg, max_len: int) -> None:
         B.attn_segmass(q, kc, self.lens, self.seg, self.mass[layer], cfg.n_heads, cfg.head_dim, max_len, cfg.head_dim ** -0.5,
                        n_kv_heads=cfg.kv_heads, q_rows=q_rows, probs=None if self.probs is None else self.probs[layer])
+
+
+MAX_KNOCKOUT_SEGMENTS = 32     # icl_attn_decode_masked_bf16: one bit of a u32 per segment; ids >= 32 are never blocked
+
+
+@dataclass
+class Knockout:
+    """Attention knockout, all on the device: in decoder layers ``layers[0] .. layers[1] - 1`` the LAST prompt row and every
+    generated row of the listed sequences attend as if the keys of their blocked segments were not there
+    (icl_attn_decode_masked_bf16 rewrites those rows of the attention output after the layer's ordinary attention launch).
+    ``seg`` uint8 [n_seqs, >= cache max_len]: the segment of every cache position, 255 past the prompt (generated positions are
+    always visible); ``blocked`` int32 [n_listed, n_heads]: bit g of a (listed row, query head) = segment g is not read;
+    ``row_seq`` int32 [n_listed]: the listed sequences, ascending (``listed``: the same on the host).  The runtime keeps all
+    three in graph-visible workspace buffers and refills them on every call, so ``uid`` — what a captured decode graph bakes in
+    besides those pointers: the number of listed rows (a grid size) and the layer window — keys the decode graphs."""
+    seg: torch.Tensor
+    blocked: torch.Tensor
+    row_seq: torch.Tensor
+    listed: Tuple[int, ...]
+    layers: Tuple[int, int]
+
+    @property
+    def uid(self):
+        return ("knockout", len(self.listed), self.layers[0], self.layers[1])
+
+    def rows(self, b0: int, b1: int) -> Optional["Knockout"]:
+        """The knockout of sequences b0 .. b1-1 (views; sequence ids relative to b0), for a prefill over that chunk of the
+        batch (``KVCache.rows``); None when the chunk lists no row."""
+        lo = sum(1 for s in self.listed if s < b0)
+        hi = sum(1 for s in self.listed if s < b1)
+        if lo == hi:
+            return None
+        if b0 == 0 and hi == len(self.listed):
+            return replace(self, seg=self.seg[b0:b1])
+        sub = tuple(s - b0 for s in self.listed[lo:hi])
+        return Knockout(self.seg[b0:b1], self.blocked[lo:hi], _i32(sub, self.seg.device), sub, self.layers)
+
+    def covers(self, layer: int) -> bool:
+        return self.layers[0] <= layer < self.layers[1]
+
+    def launch(self, q: torch.Tensor, att: torch.Tensor, row_q: torch.Tensor, kc, vc, lens: torch.Tensor, cfg, max_len: int) -> None:
+        """Rewrite rows ``row_q`` (int32 [n_listed]) of ``att`` from the same rows of ``q`` (rotated) over the bf16 cache."""
+        B.attn_decode_masked(q, kc, vc, att, lens, self.seg, self.blocked, self.row_seq, row_q, cfg.n_heads, cfg.head_dim, max_len,
+                             cfg.head_dim ** -0.5, n_kv_heads=cfg.kv_heads)
 
 
 KV_DTYPES = ("bf16", "fp8")

@@ -18,7 +18,7 @@ import torch
 
 from . import binding as B
 from .config import SalmonnCfg
-from .engines import (BF16, F32, I32, MAX_READOUT_SEGMENTS, AttnReadout, BeatsHIP, KVCache, LlamaHIP, LogMel, SpeechQFormerHIP, WhisperEncoderHIP, Workspace, _i32,
+from .engines import (BF16, F32, I32, MAX_KNOCKOUT_SEGMENTS, MAX_READOUT_SEGMENTS, AttnReadout, BeatsHIP, Knockout, KVCache, LlamaHIP, LogMel, SpeechQFormerHIP, WhisperEncoderHIP, Workspace, _i32,
                       check_kv_dtype)
 from .packing import normalize_keys, pack_beats, pack_llama, pack_qformer, pack_whisper
 
@@ -148,7 +148,8 @@ class CausalLMRuntimeMixin:
         assert max_len <= self.lm_cfg.max_pos, f"prompt + new tokens ({need}) exceeds max_pos {self.lm_cfg.max_pos}"  # validated
         return max_len
 
-    def _prefill_logits(self, h, lens: List[int], cache: KVCache, last, readout: Optional[AttnReadout] = None) -> torch.Tensor:
+    def _prefill_logits(self, h, lens: List[int], cache: KVCache, last, readout: Optional[AttnReadout] = None,
+                        knockout: Optional[Knockout] = None) -> torch.Tensor:
         """Prefill in chunks of at most ``prefill_chunk`` sequences (the caller decodes ALL of them together: the decode GEMMs
         stream the weights once per step whatever the row count — 256 rows cost 0.84 us each against 1.06 at 128 — while the
         prefill GEMMs measured 1.3 % faster per utterance at 128 sequences than at 256; a sequence's arithmetic does not depend
@@ -159,8 +160,9 @@ class CausalLMRuntimeMixin:
         for b0 in range(0, len(lens), self.prefill_chunk):
             b1 = min(len(lens), b0 + self.prefill_chunk)
             r1 = r0 + sum(lens[b0:b1])
+            ko = None if knockout is None else knockout.rows(b0, b1)       # None: a chunk that lists no row launches as ever
             self.llama.prefill(self.ws, h[r0:r1], lens[b0:b1], cache.rows(b0, b1), last_rows_only=True, last_out=last[b0:b1],
-                               readout=None if readout is None else readout.rows(b0, b1))
+                               readout=None if readout is None else readout.rows(b0, b1), **({} if ko is None else {"knockout": ko}))
             r0 = r1
         return self.llama.logits(self.ws, last, name="gen_logits")
 
@@ -245,7 +247,8 @@ class CausalLMRuntimeMixin:
                  cache_len_multiple: int = 64, do_sample: bool = False, temperature: float = 1.0, top_p: float = 1.0,
                  top_k: int = 50, repetition_penalty: float = 1.0, generator: Optional[torch.Generator] = None,
                  sample_debug=None, want_step_logits: bool = False, overlong: str = "raise", num_beams: int = 1,
-                 length_penalty: float = 1.0, beam_debug: Optional[dict] = None, constraint=None) -> GenerateResult:
+                 length_penalty: float = 1.0, beam_debug: Optional[dict] = None, constraint=None,
+                 knockout=None) -> GenerateResult:
         """Greedy search with HF ``generate(inputs_embeds=…)`` semantics (models/custom_salmon.py:704-720): returns only
         the new tokens; a row that has emitted EOS is filled with pad; the width is that of the longest row
         (``min_length`` is a no-op with inputs_embeds).  All steps are enqueued without a host sync; the
@@ -270,7 +273,20 @@ class CausalLMRuntimeMixin:
         that runs out of ``max_new_tokens`` stops on a complete answer; the result carries ``token_logprobs``.  Prefill, KV cache
         and decode step are the unconstrained ones.  Greedy only: sampling, a repetition penalty, beams and ``suppress_eos``
         together with a constraint, a ``max_new_tokens`` below a row's shortest answer, and a start-state list of the wrong
-        length are ``ValueError``s raised before anything is launched."""
+        length are ``ValueError``s raised before anything is launched.
+
+        ``knockout`` = ``(segments, blocked, layers, heads)`` (the last two optional; or a dict with those keys): opt-in
+        attention knockout, the causal companion of ``prompt_attention``.  ``segments[b]``: one id (0..255) per position of
+        prompt b, as for the readout; ``blocked[b]``: the segment ids (0..31) row b may not read, empty = the row is not
+        touched; ``layers``: a half-open range ``(l0, l1)`` of decoder layers (None: all); ``heads``: query-head indices (None:
+        all).  In those layers and heads the query of the LAST prompt position of row b and of every generated position gives
+        weight 0 to every key of a blocked segment, and the softmax runs over the rest (generated positions are always
+        visible); every other query of the prompt sees what it always saw.  One more launch (icl_attn_decode_masked_bf16) per
+        windowed layer, prefill chunk and decode step rewrites those rows of the attention output; rows with an empty set keep
+        their bits, and a knockout whose every set is empty is no knockout.  Works with every tail above; ``ValueError`` before
+        any launch: the FP8 KV cache, beams, a segment list of the wrong length, ids outside 0..255, a blocked id outside 0..31, a
+        layer window outside ``[0, n_layers]`` or empty, a head index out of range, a row whose blocked set covers its whole
+        prompt."""
         args = {k: v for k, v in locals().items() if k not in ("self", "prompts", "speech")}   # the keyword arguments, as given
         c, ws = self.lm_cfg, self.ws
         # ---- 1. validate: every caller error is raised here, before anything is launched
@@ -281,6 +297,8 @@ class CausalLMRuntimeMixin:
                                                 num_beams, suppress_eos)
         limit = c.max_pos // cache_len_multiple * cache_len_multiple      # cache lengths are multiples of cache_len_multiple
         plens = self._prompt_lengths(prompts)
+        if knockout is not None:
+            knockout = args["knockout"] = self._check_knockout(knockout, plens, num_beams)      # None: every blocked set is empty
         bad = [b for b, n in enumerate(plens) if n + max_new_tokens > limit]
         if bad and (overlong == "raise" or len(bad) == len(plens)):
             raise ValueError(f"prompt + new tokens of row(s) {bad} ({[plens[b] + max_new_tokens for b in bad]} positions) "
@@ -316,6 +334,8 @@ class CausalLMRuntimeMixin:
             keep = [b for b in range(len(plens)) if b not in set(bad)]
             if constraint is not None:
                 args["constraint"] = (constraint[0], [constraint[1][b] for b in keep])
+            if knockout is not None:          # the surviving rows' entries
+                args["knockout"] = ([knockout[0][b] for b in keep], [knockout[1][b] for b in keep]) + tuple(knockout[2:])
             return _undrop(self.generate([prompts[b] for b in keep], speech, **args), keep, bad, len(plens), pad)
         # ---- 3. beams
         if num_beams != 1:
@@ -330,7 +350,9 @@ class CausalLMRuntimeMixin:
         marks = getattr(self, "phase_marks", None)     # optional {name: torch.cuda.Event}: bench.py times prefill / decode with it
         if marks is not None:
             marks["prefill_start"].record()
-        logits = self._prefill_logits(h, lens, cache, ws.get("gen_last", (Bn, c.hidden), F32))
+        ko = None if knockout is None else self._knockout_state(knockout, Bn, max_len)
+        ko_kw = {} if ko is None else {"knockout": ko}
+        logits = self._prefill_logits(h, lens, cache, ws.get("gen_last", (Bn, c.hidden), F32), **ko_kw)
         first = logits.clone() if want_first_logits else None
         trace = ws.get("gen_logits_trace", (max_new_tokens, Bn, c.vocab), F32) if want_step_logits else None
         if trace is not None:
@@ -351,11 +373,12 @@ class CausalLMRuntimeMixin:
 
             def decode_loop():
                 for t in range(steps):
-                    lg = self.llama.decode_step(ws, cache, nxt, pos_all[t], len_all[t], sid)
+                    lg = self.llama.decode_step(ws, cache, nxt, pos_all[t], len_all[t], sid, **ko_kw)
                     if trace is not None:
                         trace[t + 1].copy_(lg)
                     tail(lg, t + 1)
-            self._run_decode((Bn, max_len, steps, eos, pad, tail_key, trace is not None, self.kv_dtype), decode_loop)
+            self._run_decode((Bn, max_len, steps, eos, pad, tail_key, trace is not None, self.kv_dtype)
+                             + (() if ko is None else (ko.uid,)), decode_loop)
         if marks is not None:
             marks["decode_end"].record()
         # ---- 8. collect: the first host sync of the call, and its only D2H (two with a constraint)
@@ -429,6 +452,82 @@ class CausalLMRuntimeMixin:
         return PromptAttention(mass=mass.cpu().transpose(0, 1).contiguous(),
                                probs=None if probs is None else probs.transpose(0, 1).clone(),
                                first_logits=logits.clone(), lens=list(lens))
+
+    def _check_knockout(self, knockout, plens: List[int], num_beams: int):
+        """Host validation of ``generate(knockout=...)``: everything is a ``ValueError`` raised before any launch.  Returns
+        ``(segments as int lists, blocked as sorted tuples, (l0, l1), heads tuple | None)``, or None when every set is empty."""
+        c = self.lm_cfg
+        if isinstance(knockout, dict):
+            unknown = set(knockout) - {"segments", "blocked", "layers", "heads"}
+            if unknown or "segments" not in knockout or "blocked" not in knockout:
+                raise ValueError("knockout as a dict holds 'segments' and 'blocked', and optionally 'layers' and 'heads'")
+            knockout = (knockout["segments"], knockout["blocked"], knockout.get("layers"), knockout.get("heads"))
+        try:
+            segments, blocked, layers, heads = (tuple(knockout) + (None, None))[:4] if 2 <= len(knockout) <= 4 else (None,) * 4
+        except TypeError:
+            segments = None
+        if segments is None:
+            raise ValueError("knockout must be (segments, blocked[, layers[, heads]]) or a dict with those keys")
+        if len(segments) != len(plens) or len(blocked) != len(plens):
+            raise ValueError(f"knockout: {len(segments)} segment lists and {len(blocked)} blocked sets for {len(plens)} prompts")
+        segs, sets = [], []
+        for b, (sg, n) in enumerate(zip(segments, plens)):
+            sg = [int(x) for x in (sg.tolist() if isinstance(sg, torch.Tensor) else sg)]
+            if len(sg) != n:
+                raise ValueError(f"knockout: segments[{b}] has {len(sg)} entries, the prompt of row {b} has {n} positions")
+            if sg and (min(sg) < 0 or max(sg) > 255):
+                raise ValueError(f"knockout: segments[{b}]: segment ids are 0..255 (ids >= {MAX_KNOCKOUT_SEGMENTS} are never blocked)")
+            bl = tuple(sorted({int(x) for x in blocked[b]}))
+            if bl and not (0 <= bl[0] and bl[-1] < MAX_KNOCKOUT_SEGMENTS):
+                raise ValueError(f"knockout: blocked[{b}] = {list(bl)}: only segment ids 0..{MAX_KNOCKOUT_SEGMENTS - 1} can be blocked")
+            segs.append(sg)
+            sets.append(bl)
+        if layers is None:
+            layers = (0, c.n_layers)
+        try:
+            l0, l1 = (int(x) for x in layers)
+        except (TypeError, ValueError):
+            raise ValueError(f"knockout: layers must be a half-open range (l0, l1), not {layers!r}") from None
+        if not 0 <= l0 < l1 <= c.n_layers:
+            raise ValueError(f"knockout: layer window ({l0}, {l1}) must be a non-empty range inside [0, {c.n_layers}]")
+        if heads is not None:
+            heads = tuple(sorted({int(x) for x in heads}))
+            if not heads or heads[0] < 0 or heads[-1] >= c.n_heads:
+                raise ValueError(f"knockout: head indices {list(heads)} must be a non-empty subset of 0..{c.n_heads - 1}")
+        for b, (sg, bl) in enumerate(zip(segs, sets)):
+            if bl and all(x in bl for x in sg):
+                raise ValueError(f"knockout: row {b}: the blocked segments {list(bl)} cover every position of its prompt")
+        if not any(sets):
+            return None
+        if self.kv_dtype != "bf16":
+            raise ValueError(f"knockout needs the bf16 KV cache (llm_kv_dtype={self.kv_dtype!r}: the FP8 prefill attends to unrounded "
+                             "k / v, so the cache does not hold the keys the attention saw)")
+        if num_beams != 1:
+            raise ValueError("knockout runs with greedy, sampled and label-constrained decoding, not with beams (num_beams > 1)")
+        return segs, sets, (l0, l1), heads
+
+    def _knockout_state(self, knockout, Bn: int, max_len: int) -> Knockout:
+        """The validated knockout on the device, in graph-visible workspace buffers refilled on every call: the segment table
+        padded with ``IGNORE_SEGMENT`` to the cache length, the listed rows (non-empty sets) and their per-head bit sets."""
+        segs, sets, layers, heads = knockout
+        c, ws = self.lm_cfg, self.ws
+        seg = torch.full((Bn, max_len), self.IGNORE_SEGMENT, dtype=torch.uint8)
+        for b, sg in enumerate(segs):
+            seg[b, :len(sg)] = torch.tensor(sg, dtype=torch.uint8)
+        listed = tuple(b for b, bl in enumerate(sets) if bl)
+        on = set(range(c.n_heads) if heads is None else heads)
+        bits = []
+        for b in listed:
+            m = sum(1 << g for g in sets[b])
+            m -= (1 << 32) if m >= (1 << 31) else 0           # the u32 bit set in an int32 tensor
+            bits.append([m if h in on else 0 for h in range(c.n_heads)])
+        seg_d = ws.get("gen_ko_seg", (Bn, max_len), torch.uint8)
+        blk_d = ws.get("gen_ko_blocked", (len(listed), c.n_heads), I32)
+        rows_d = ws.get("gen_ko_rows", (len(listed),), I32)
+        seg_d.copy_(seg, non_blocking=True)
+        blk_d.copy_(torch.tensor(bits, dtype=I32), non_blocking=True)
+        rows_d.copy_(torch.tensor(listed, dtype=I32), non_blocking=True)
+        return Knockout(seg_d, blk_d, rows_d, listed, layers)
 
     def _check_constraint(self, constraint, n_rows: int, max_new_tokens: int, eos_id, do_sample: bool, repetition_penalty: float,
                           num_beams: int, suppress_eos: bool):

@@ -246,6 +246,29 @@ int icl_attn_segmass_bf16(const void* Q, int64_t ldq, const int32_t* q_rows, con
                           int32_t n_seqs, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int32_t max_len, float scale,
                           void* stream);
 
+/* ---- attention knockout: icl_attn_decode_bf16 / icl_attn_decode_gqa_bf16 over a row LIST, under a per-key segment mask ----
+ * The causal companion of the readout above: the deciding query attends as if chosen pieces of the prompt were not there.
+ * List entry r (0 <= r < n_rows) works on cache sequence row_seq[r]: it reads the query (bf16, already rotated) at row row_q[r]
+ * of Q and writes row row_q[r] of O; rows of O that no entry lists are not written.  row_seq values must be sequences of the
+ * cache and of lens / seg, row_q values rows of Q / O (the caller's duty: the call cannot see those extents).
+ *   Kc/Vc  the bf16 cache of the decode kernels, [n_seqs][n_kv_heads][max_len][head_dim]; n_kv_heads 0 = n_heads.
+ *   seg    seg[row_seq[r] * ld_seg + j] = the segment of key j (u8); entries at or past lens[row_seq[r]] are never read.
+ *   blocked  u32 [n_rows][n_heads]: bit g of blocked[r * n_heads + h] = query head h of entry r does not read segment g.
+ *   Key j counts for head h iff j < lens[row_seq[r]] and not (seg_j < 32 and bit seg_j of the mask): ids >= 32 are never blocked.
+ * The softmax runs over the keys that count, in the stream order of the unmasked kernel (a key that does not count is a key past
+ * the end): a mask of 0 gives icl_attn_decode_bf16's sums in its stream order (within rounding of that call, not bit-equal to it
+ * by contract), a (row, head) without a key that counts writes zeros (the L > 0 rule).  One instantiation per (head_dim, G)
+ * whatever n_rows is: a row's output is bit-identical alone and in any list.  One byte per key is read on top of a decode launch.
+ * head_dim 64 or 128 multi-head; grouped (2 <= G <= 8) at head_dim 128, each head's own mask on the K / V chunk its group shares.
+ * ICL_EINVAL (before any launch, naming the argument): a NULL pointer, n_rows <= 0 (or > 65535), head_dim not 64 / 128,
+ * n_kv_heads not dividing n_heads, G > 8, G > 1 at head_dim 64, ld_seg < max_len, misaligned Q / Kc / Vc (16 B; ldq % 8),
+ * ldq / ldo < n_heads * head_dim, a scale that is not finite.
+ */
+int icl_attn_decode_masked_bf16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O, int64_t ldo,
+                                const int32_t* lens, const uint8_t* seg, int64_t ld_seg, const uint32_t* blocked,
+                                const int32_t* row_seq, const int32_t* row_q, int32_t n_rows, int32_t n_heads, int32_t n_kv_heads,
+                                int32_t head_dim, int32_t max_len, float scale, void* stream);
+
 /* ---- K11: the decode step's RoPE + KV-cache append + attention as ONE launch --------------------
  * icl_rope_kv_bf16 (M = n_seqs rows, one new position each) followed by icl_attn_decode_bf16, fused: qkv bf16 [n_seqs][ld] holds
  * the QKV projection's raw q | k | v row of every sequence (column blocks at 0 | k_off | v_off, n_heads*head_dim wide);
