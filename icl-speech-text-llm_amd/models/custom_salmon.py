@@ -683,6 +683,44 @@ class CustomSALMONN(BaseModel):
                                     knockout=([self.piece_ids(s) for s in segs], blocked, layers, heads))
         return {"texts": self.decode_ids(res.tokens), "tokens": res.tokens, "first_logits": res.first_logits, "pieces": pieces}
 
+    def _generate_resid(self, samples: Dict[str, Any], **resid) -> Any:
+        """``runtime.generate`` on the batch as ``generate_ids`` reads it (greedy, sampled or label-constrained; no beams), with
+        the residual-stream arguments ``resid`` (``want_hidden`` / ``patch``) and the first-step logits."""
+        samples = self._host_counts(samples)
+        constraint = self._label_constraint(samples)
+        speech_embeds, _, example_embeds, _ = self.get_speech_embeddings(samples)
+        num_examples = samples.get("num_examples", torch.zeros(len(samples["prompt"]), dtype=torch.long))
+        segs, speech = self._segments(speech_embeds, samples["prompt"], num_examples, example_embeds)
+        return self.runtime.generate(segs, speech, max_new_tokens=int(samples.get("max_new_tokens", 10)),
+                                     eos_id=self.llama_tokenizer.eos_token_id, pad_id=self.llama_tokenizer.pad_token_id,
+                                     do_sample=bool(samples.get("do_sample", False)),
+                                     temperature=float(samples.get("temperature", 0.8)), top_p=float(samples.get("top_p", 0.9)),
+                                     top_k=int(self.hf_generation_defaults.get("top_k", 50)),
+                                     repetition_penalty=float(samples.get("repetition_penalty", 1.0)),
+                                     generator=samples.get("generator"), want_first_logits=True, overlong="drop",
+                                     num_beams=int(samples.get("num_beams", 1)), constraint=constraint, **resid)
+
+    def task_vectors(self, samples: Dict[str, Any]) -> Dict[str, Any]:
+        """The residual stream of the last prompt position — the "task vector" of a few-shot prompt — at every site: ``{"hidden":
+        f32 [B, n_layers + 1, hidden] (device; site l < n_layers = the input of decoder layer l, HF ``hidden_states[l]``; site
+        n_layers = the last layer's output before the final norm; a dropped row is NaN), "first_logits": f32 [B, V] (device),
+        "tokens": int64 [B, width] (CPU), "texts"}``.  The generation is ``generate_ids``'s, bit for bit;
+        ``runtime.layer_logits(hidden)`` is the logit lens."""
+        res = self._generate_resid(samples, want_hidden=True)
+        return {"hidden": res.hidden, "first_logits": res.first_logits, "tokens": res.tokens, "texts": self.decode_ids(res.tokens)}
+
+    def generate_patched(self, samples: Dict[str, Any], vectors, site: int, mode: str = "replace", alpha: float = 1.0,
+                         steps: str = "prompt", rows=None) -> Dict[str, Any]:
+        """Activation patching and steering: generate with the residual stream of the last prompt position (``steps="all"``: and
+        of every generated one) at ``site`` replaced by ``vectors`` (``mode="replace"``: a task-vector transplant) or moved by
+        ``alpha * vectors`` (``mode="add"``).  ``vectors``: f32 [B, hidden] (``task_vectors(...)["hidden"][:, site]`` of a batch
+        of the same size), or [1, hidden] / [hidden] for all rows; ``rows``: None (all) or the rows of the batch to patch.
+        Returns ``{"texts", "tokens": int64 [B, width] (CPU), "first_logits": f32 [B, V] (device)}``.  A wrong ``vectors`` shape
+        or dtype, a site outside 0..n_layers, a bad mode / steps / alpha / rows and beams are ``ValueError``s raised before
+        anything is launched on the decoder."""
+        res = self._generate_resid(samples, patch=dict(site=site, vectors=vectors, mode=mode, alpha=alpha, steps=steps, rows=rows))
+        return {"texts": self.decode_ids(res.tokens), "tokens": res.tokens, "first_logits": res.first_logits}
+
     def _label_constraint(self, samples: Dict[str, Any]):
         """``(automaton, start states)`` for a batch that sets ``constrain_labels`` (one grammar per row, by its ``dataset_type``),
         else ``None``.  Automata are built once per set of dataset types from this model's tokenizer and kept."""

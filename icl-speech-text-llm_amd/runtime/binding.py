@@ -139,6 +139,8 @@ _SIGNATURES = {
     "icl_gather_rows_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
     "icl_gather_rows_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
     "icl_cross_entropy": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "icl_resid_rows_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32,
+                                   c_float, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -797,6 +799,32 @@ def gather_rows(src, idx, out, N=None):
     _check(fn(src.data_ptr(), src.stride(0), idx.data_ptr(), out.data_ptr(), out.stride(0), idx.numel(),
               src.shape[1] if N is None else N, _stream()), what)
     return out
+
+
+RESID_MODES = {"replace": 0, "add": 1}
+
+
+def resid_rows(h, rows, *, capture=None, vec=None, mode="replace", alpha: float = 1.0, hidden=None):
+    """Residual-stream capture and patch at the listed rows (icl_resid_rows_f32).  h: f32 [R, >= hidden] (row stride = its
+    leading dimension), patched in place; rows: int32 [n], distinct rows of h; capture: None or f32 [n, >= hidden], receives the
+    rows' PRE-patch bits; vec: None or f32 [n, >= hidden] (one vector per entry) or [1, hidden] / [hidden] (one for all entries);
+    mode "replace" (bits) or "add" (h = fma(alpha, vec, h), one rounding).  ``hidden``: the columns worked on (default: h's width)."""
+    _require_gpu(h, rows, capture, vec)
+    assert h.dtype == torch.float32 and h.dim() == 2 and h.stride(1) == 1 and rows.dtype == torch.int32 and rows.is_contiguous()
+    n = rows.numel()
+    hidden = h.shape[1] if hidden is None else hidden
+    ld_cap = ld_vec = 0
+    if capture is not None:
+        assert capture.dtype == torch.float32 and capture.dim() == 2 and capture.shape[0] == n and capture.stride(1) == 1
+        ld_cap = capture.stride(0)
+    if vec is not None:
+        assert vec.dtype == torch.float32 and vec.dim() in (1, 2) and vec.stride(-1) == 1
+        assert vec.dim() == 1 or vec.shape[0] in (1, n), f"{vec.shape[0]} vectors for {n} rows"
+        ld_vec = vec.stride(0) if vec.dim() == 2 and vec.shape[0] > 1 else 0      # 0: the one vector serves every entry
+    mode_i = RESID_MODES[mode] if mode in RESID_MODES else int(mode)   # an integer goes through: the entry point refuses a bad one
+    _check(load_library().icl_resid_rows_f32(h.data_ptr(), h.stride(0), rows.data_ptr(), n, hidden, _ptr(capture), ld_cap,
+                                             _ptr(vec), ld_vec, mode_i, float(alpha), _stream()), "icl_resid_rows_f32")
+    return h
 
 
 def cross_entropy(logits, labels, row_loss, mean_loss, V=None):

@@ -609,8 +609,17 @@ class LlamaHIP:
     # ---- K10: prefill over ragged packed sequences ------------------------------------------------
     def prefill(self, ws: Workspace, h: torch.Tensor, seq_lens: List[int], cache: Optional["KVCache"] = None,
                 last_rows_only: bool = False, last_out: Optional[torch.Tensor] = None,
-                readout: Optional["AttnReadout"] = None, knockout: Optional["Knockout"] = None) -> torch.Tensor:
+                readout: Optional["AttnReadout"] = None, knockout: Optional["Knockout"] = None,
+                capture: Optional[torch.Tensor] = None, patch: Optional["ResidPatch"] = None) -> torch.Tensor:
         """h f32 [sum S_b, hidden] (modified in place) -> same buffer holding the final hidden states.
+
+        ``capture`` f32 [n_seqs, n_layers + 1, hidden] and ``patch`` (both need ``last_rows_only``): the residual stream of the
+        sequences' LAST rows, read and written (icl_resid_rows_f32).  Site l < n_layers is ``h`` at the top of layer l, before
+        its input norm and before the branch into the trimmed last layer, so that layer's k / v of the row see the patch; site
+        n_layers is the gathered rows before they are returned.  ``capture[:, l]`` receives every sequence's row at every site,
+        pre-patch; at ``patch.site`` the listed sequences' rows are replaced or added to.  One launch per site with a capture
+        (two at the patched site when the patch lists only some sequences), one in all with a patch alone; without either the
+        layers launch what they launch.
 
         ``knockout`` (needs ``last_rows_only`` and a bf16 cache): attention knockout.  In a layer of its window, after the
         layer's ordinary attention launch, one more launch (icl_attn_decode_masked_bf16) rewrites the attention output of the
@@ -636,6 +645,7 @@ class LlamaHIP:
         assert cache is not None or not last_rows_only, "prefill(last_rows_only=True) needs a KV cache"
         assert readout is None or (last_rows_only and cache.dtype == "bf16"), "the attention readout reads the last rows' q and a bf16 K cache"
         assert knockout is None or (last_rows_only and cache.dtype == "bf16"), "attention knockout rewrites the last rows from a bf16 KV cache"
+        assert (capture is None and patch is None) or last_rows_only, "residual capture / patching works on the last rows (last_rows_only)"
         pos = _i32([p for s in seq_lens for p in range(s)], dev)
         sid = _i32([b for b, s in enumerate(seq_lens) for _ in range(s)], dev)
         cu = _i32(cu_h, dev)
@@ -662,13 +672,17 @@ class LlamaHIP:
         if knockout is not None:        # the prompt lengths as the masked launch's key counts; the listed sequences' last rows
             ko_lens = _i32(seq_lens, dev)
             ko_rows = _i32([cu_h[b + 1] - 1 for b in knockout.listed], dev)
+        rp_rows = None if patch is None else _i32([cu_h[b + 1] - 1 for b in patch.listed], dev)   # the listed last packed rows
         for i, L in enumerate(w.layers):
+            if capture is not None or (patch is not None and patch.site == i):
+                resid_site(i, h, last_idx, rp_rows, capture, patch)
             kc, vc, ks, vs = cache.layer(i) if cache is not None else (None, None, None, None)
             ko = knockout if knockout is not None and knockout.covers(i) else None
             if trim and i == len(w.layers) - 1:
-                return self._last_layer_rows(ws, L, h, seq_lens, pos, sid, cu, kc, vc, max_len, last_idx, out,
-                                             readout=None if readout is None else (readout, i),
-                                             knockout=None if ko is None else (ko, ko_lens))
+                hg = self._last_layer_rows(ws, L, h, seq_lens, pos, sid, cu, kc, vc, max_len, last_idx, out,
+                                           readout=None if readout is None else (readout, i),
+                                           knockout=None if ko is None else (ko, ko_lens))
+                break
             xn = self._xn(ws, L, h, M, "pf_", decode=False)
             qkv = ws.get("pf_qkv", (M, qkv_width(c)), BF16)
             att = ws.get("pf_att", (M, hd), BF16)
@@ -708,7 +722,12 @@ class LlamaHIP:
             if ko is not None:          # the listed last rows again, under their masks
                 ko.launch(qkv[:, :k_off], att, ko_rows, kc, vc, ko_lens, c, max_len)
             self._attn_out_mlp(ws, L, h, xn, att, "pf_", sites, None)
-        return B.gather_rows(h, last_idx, out) if last_rows_only else h
+        else:
+            hg = B.gather_rows(h, last_idx, out) if last_rows_only else h
+        if capture is not None or (patch is not None and patch.site == len(w.layers)):     # gathered row b is sequence b's
+            resid_site(len(w.layers), hg, _i32(list(range(len(seq_lens))), dev), None if patch is None else patch.row_seq,
+                       capture, patch)
+        return hg
 
     def _last_layer_rows(self, ws: Workspace, L, h, seq_lens: List[int], pos, sid, cu, kc, vc, max_len: int,
                          last_idx, hg, readout=None, knockout=None) -> torch.Tensor:
@@ -760,8 +779,13 @@ class LlamaHIP:
 
     # ---- K11: one decode step for Bn sequences -----------------------------------------------------
     def decode_step(self, ws: Workspace, cache: "KVCache", next_ids: torch.Tensor, pos: torch.Tensor,
-                    lens: torch.Tensor, sid: torch.Tensor, knockout: Optional["Knockout"] = None) -> torch.Tensor:
-        """``knockout`` (a bf16 cache): in a layer of its window one more launch (icl_attn_decode_masked_bf16) rewrites the listed
+                    lens: torch.Tensor, sid: torch.Tensor, knockout: Optional["Knockout"] = None,
+                    patch: Optional["ResidPatch"] = None) -> torch.Tensor:
+        """``patch`` (one whose ``steps`` is "all"): at the top of layer ``patch.site`` one launch (icl_resid_rows_f32) replaces or
+        adds to the listed rows of ``h``.  The previous layer's ``down`` launch may have written this layer's normed input from the
+        unpatched ``h``, so the patched layer runs its input norm as a launch of its own (site n_layers: the final norm).
+
+        ``knockout`` (a bf16 cache): in a layer of its window one more launch (icl_attn_decode_masked_bf16) rewrites the listed
         rows of the attention output under their masks.  The step then takes the two-launch RoPE + attention form at every batch
         size — the fused launch leaves q unrotated in ``qkv``; the two forms are bit-identical — so unlisted rows keep their bits."""
         c, w = self.w.cfg, self.w
@@ -791,6 +815,9 @@ class LlamaHIP:
         ready = False
         for i, L in enumerate(layers):
             kc, vc, ks, vs = cache.layer(i)
+            if patch is not None and patch.site == i:
+                patch.launch(h, patch.row_seq)
+                ready = False       # what the previous down wrote is the norm of the unpatched rows
             xn = self._xn(ws, L, h, Bn, "dc_", decode=True, ready=ready)
             self._site_gemm(L, sites, "qkv", xn, qkv, wsk, bias=L.bqkv)
             if c.qk_norm:         # QK-norm (Qwen3): two launches at every batch size, norm + RoPE + append and the decode attention
@@ -818,6 +845,9 @@ class LlamaHIP:
                 knockout.launch(qkv[:, :k_off], att, knockout.row_seq, kc, vc, lens, c, max_len)
             nxt = (layers[i + 1].rms1, xn_next) if i + 1 < len(layers) else (w.norm, xn_final)
             ready = self._attn_out_mlp(ws, L, h, xn, att, "dc_", sites, wsk, next_norm=nxt)
+        if patch is not None and patch.site == len(layers):
+            patch.launch(h, patch.row_seq)
+            ready = False
         return self.logits(ws, h, name="dc_logits", xn_ready=ready)
 
 
@@ -887,6 +917,61 @@ class Knockout:
         """Rewrite rows ``row_q`` (int32 [n_listed]) of ``att`` from the same rows of ``q`` (rotated) over the bf16 cache."""
         B.attn_decode_masked(q, kc, vc, att, lens, self.seg, self.blocked, self.row_seq, row_q, cfg.n_heads, cfg.head_dim, max_len,
                              cfg.head_dim ** -0.5, n_kv_heads=cfg.kv_heads)
+
+
+@dataclass
+class ResidPatch:
+    """Residual-stream patching at the deciding rows, all on the device: at site ``site`` (0 .. n_layers - 1: the input of that
+    decoder layer, before its norm; n_layers: the output of the last layer, before the final norm) the LAST prompt row of the
+    listed sequences — and with ``steps == "all"`` every generated row — is replaced by its vector, or gets ``alpha`` times its
+    vector added (icl_resid_rows_f32).  ``vectors`` f32 [n_listed, hidden], or [1, hidden]: one vector for all listed rows;
+    ``row_seq`` int32 [n_listed]: the listed sequences, ascending and distinct (``listed``: the same on the host).  The runtime
+    keeps both tensors in graph-visible workspace buffers and refills them on every call, so ``uid`` — what a captured decode
+    graph bakes in besides those pointers: the number of listed rows (a grid size), whether the vector is shared (a leading
+    dimension), site, mode, steps and alpha, a by-value kernel argument — keys the decode graphs."""
+    vectors: torch.Tensor
+    row_seq: torch.Tensor
+    listed: Tuple[int, ...]
+    site: int
+    mode: str = "replace"
+    alpha: float = 1.0
+    steps: str = "prompt"
+
+    @property
+    def uid(self):
+        return ("resid_patch", len(self.listed), int(self.vectors.shape[0]), self.site, self.mode, self.steps, float(self.alpha))
+
+    def rows(self, b0: int, b1: int) -> Optional["ResidPatch"]:
+        """The patch of sequences b0 .. b1-1 (views; sequence ids relative to b0), for a prefill over that chunk of the batch
+        (``KVCache.rows``); None when the chunk lists no row."""
+        lo = sum(1 for s in self.listed if s < b0)
+        hi = sum(1 for s in self.listed if s < b1)
+        if lo == hi:
+            return None
+        if b0 == 0 and hi == len(self.listed):
+            return self
+        sub = tuple(s - b0 for s in self.listed[lo:hi])
+        vec = self.vectors if self.vectors.shape[0] == 1 else self.vectors[lo:hi]
+        return replace(self, vectors=vec, row_seq=_i32(sub, self.vectors.device), listed=sub)
+
+    def launch(self, h: torch.Tensor, rows: torch.Tensor, capture: Optional[torch.Tensor] = None) -> None:
+        """Patch rows ``rows`` (int32 [n_listed]) of ``h``; ``capture`` f32 [n_listed, hidden] receives their pre-patch bits."""
+        B.resid_rows(h, rows, capture=capture, vec=self.vectors, mode=self.mode, alpha=self.alpha)
+
+
+def resid_site(site: int, h: torch.Tensor, all_rows: torch.Tensor, listed_rows: Optional[torch.Tensor],
+               capture: Optional[torch.Tensor], patch: Optional[ResidPatch]) -> None:
+    """One site of a prefill: ``capture[:, site]`` (f32 [n_seqs, n_layers + 1, hidden] or None) receives rows ``all_rows`` of
+    ``h``, one per sequence, and a ``patch`` at this site rewrites rows ``listed_rows``.  One launch does both when the patch
+    lists every sequence; a patch of some sequences next to a capture of all is a capture launch and then a patch launch."""
+    cap = None if capture is None else capture[:, site]
+    pt = patch if patch is not None and patch.site == site else None
+    if cap is not None and pt is not None and pt.listed == tuple(range(all_rows.numel())):
+        return pt.launch(h, all_rows, capture=cap)
+    if cap is not None:
+        B.resid_rows(h, all_rows, capture=cap)
+    if pt is not None:
+        pt.launch(h, listed_rows)
 
 
 KV_DTYPES = ("bf16", "fp8")

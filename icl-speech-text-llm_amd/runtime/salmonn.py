@@ -9,6 +9,7 @@ gather kernel (K9).  Everything arithmetic goes through libicl_hip; there is no 
 """
 from __future__ import annotations
 
+import math
 import os
 
 from dataclasses import dataclass
@@ -18,7 +19,7 @@ import torch
 
 from . import binding as B
 from .config import SalmonnCfg
-from .engines import (BF16, F32, I32, MAX_KNOCKOUT_SEGMENTS, MAX_READOUT_SEGMENTS, AttnReadout, BeatsHIP, Knockout, KVCache, LlamaHIP, LogMel, SpeechQFormerHIP, WhisperEncoderHIP, Workspace, _i32,
+from .engines import (BF16, F32, I32, MAX_KNOCKOUT_SEGMENTS, MAX_READOUT_SEGMENTS, AttnReadout, BeatsHIP, Knockout, KVCache, LlamaHIP, LogMel, ResidPatch, SpeechQFormerHIP, WhisperEncoderHIP, Workspace, _i32,
                       check_kv_dtype)
 from .packing import normalize_keys, pack_beats, pack_llama, pack_qformer, pack_whisper
 
@@ -37,6 +38,9 @@ class GenerateResult:
     dropped: Tuple[int, ...] = ()                # rows NOT generated (``overlong="drop"``): pad-filled tokens, NaN logits
     token_logprobs: Optional[torch.Tensor] = None   # f32 [B, width] on CPU, with a ``constraint`` only: log-probability of every
     #                                                 token among the candidates it was chosen from (0 after a row's EOS)
+    hidden = None    # or f32 [B, n_layers + 1, hidden] (device), with ``want_hidden``: the residual stream of the last prompt row at
+    #                  every site, pre-patch at a patched site.  An attribute set after construction, not a dataclass field: the
+    #                  fields are what a result of a plain call consists of (the pinned generate trace lists them)
 
 
 @dataclass
@@ -60,9 +64,12 @@ def _undrop(sub: GenerateResult, keep: List[int], bad: List[int], n: int, pad: i
         out[(slice(None),) * dim + (torch.tensor(keep).to(x.device),)] = x
         return out
     nan = float("nan")
-    return GenerateResult(tokens=spread(sub.tokens, 0, pad), first_logits=spread(sub.first_logits, 0, nan),
-                          step_logits=spread(sub.step_logits, 1, nan), dropped=tuple(bad),
-                          token_logprobs=spread(sub.token_logprobs, 0, nan))
+    res = GenerateResult(tokens=spread(sub.tokens, 0, pad), first_logits=spread(sub.first_logits, 0, nan),
+                         step_logits=spread(sub.step_logits, 1, nan), dropped=tuple(bad),
+                         token_logprobs=spread(sub.token_logprobs, 0, nan))
+    if sub.hidden is not None:
+        res.hidden = spread(sub.hidden, 0, nan)
+    return res
 
 
 def _is_speech(seg) -> bool:
@@ -149,7 +156,8 @@ class CausalLMRuntimeMixin:
         return max_len
 
     def _prefill_logits(self, h, lens: List[int], cache: KVCache, last, readout: Optional[AttnReadout] = None,
-                        knockout: Optional[Knockout] = None) -> torch.Tensor:
+                        knockout: Optional[Knockout] = None, capture: Optional[torch.Tensor] = None,
+                        patch: Optional[ResidPatch] = None) -> torch.Tensor:
         """Prefill in chunks of at most ``prefill_chunk`` sequences (the caller decodes ALL of them together: the decode GEMMs
         stream the weights once per step whatever the row count — 256 rows cost 0.84 us each against 1.06 at 128 — while the
         prefill GEMMs measured 1.3 % faster per utterance at 128 sequences than at 256; a sequence's arithmetic does not depend
@@ -161,8 +169,13 @@ class CausalLMRuntimeMixin:
             b1 = min(len(lens), b0 + self.prefill_chunk)
             r1 = r0 + sum(lens[b0:b1])
             ko = None if knockout is None else knockout.rows(b0, b1)       # None: a chunk that lists no row launches as ever
+            kw = {} if ko is None else {"knockout": ko}
+            if capture is not None:
+                kw["capture"] = capture[b0:b1]
+            if patch is not None and patch.rows(b0, b1) is not None:
+                kw["patch"] = patch.rows(b0, b1)
             self.llama.prefill(self.ws, h[r0:r1], lens[b0:b1], cache.rows(b0, b1), last_rows_only=True, last_out=last[b0:b1],
-                               readout=None if readout is None else readout.rows(b0, b1), **({} if ko is None else {"knockout": ko}))
+                               readout=None if readout is None else readout.rows(b0, b1), **kw)
             r0 = r1
         return self.llama.logits(self.ws, last, name="gen_logits")
 
@@ -248,7 +261,7 @@ class CausalLMRuntimeMixin:
                  top_k: int = 50, repetition_penalty: float = 1.0, generator: Optional[torch.Generator] = None,
                  sample_debug=None, want_step_logits: bool = False, overlong: str = "raise", num_beams: int = 1,
                  length_penalty: float = 1.0, beam_debug: Optional[dict] = None, constraint=None,
-                 knockout=None) -> GenerateResult:
+                 knockout=None, want_hidden: bool = False, patch=None) -> GenerateResult:
         """Greedy search with HF ``generate(inputs_embeds=…)`` semantics (models/custom_salmon.py:704-720): returns only
         the new tokens; a row that has emitted EOS is filled with pad; the width is that of the longest row
         (``min_length`` is a no-op with inputs_embeds).  All steps are enqueued without a host sync; the
@@ -286,7 +299,21 @@ class CausalLMRuntimeMixin:
         their bits, and a knockout whose every set is empty is no knockout.  Works with every tail above; ``ValueError`` before
         any launch: the FP8 KV cache, beams, a segment list of the wrong length, ids outside 0..255, a blocked id outside 0..31, a
         layer window outside ``[0, n_layers]`` or empty, a head index out of range, a row whose blocked set covers its whole
-        prompt."""
+        prompt.
+
+        ``want_hidden`` and ``patch``: the residual stream at the deciding rows, read and written.  A decoder of n_layers layers
+        has n_layers + 1 sites: site l < n_layers is the f32 stream at the input of layer l, before its input norm (HF
+        ``hidden_states[l]``), site n_layers the output of the last layer before the final norm.  ``want_hidden``: the result's
+        ``hidden`` f32 [B, n_layers + 1, hidden] (device) holds the LAST prompt row at every site, pre-patch at a patched site
+        (dropped rows: NaN); ``layer_logits`` turns it into the logit lens.  ``patch`` = a dict ``site``, ``vectors`` (f32, CPU or
+        device: [B, hidden] one per prompt, or [1, hidden] / [hidden] shared), ``mode`` "replace" (default) | "add", ``alpha`` (1.0;
+        add only: row += alpha * vector, one rounding), ``rows`` (None: all, or distinct prompt indices; an empty list is no
+        patch), ``steps`` "prompt" (default: the last prompt row only) | "all" (every generated row as well).  One launch
+        (icl_resid_rows_f32) per site and prefill chunk with ``want_hidden``, one per chunk with a patch alone, and with
+        ``steps="all"`` one per decode step plus the patched layer's input norm as a launch of its own; rows not listed keep
+        their bits.  Works with every tail above, both KV dtypes and both weight dtypes.  ``ValueError`` before any launch:
+        unknown keys, a site outside 0..n_layers, vectors of the wrong shape or dtype, a bad mode or steps, a non-finite alpha,
+        a duplicate or out-of-range row, beams, ``patch`` together with ``knockout``."""
         args = {k: v for k, v in locals().items() if k not in ("self", "prompts", "speech")}   # the keyword arguments, as given
         c, ws = self.lm_cfg, self.ws
         # ---- 1. validate: every caller error is raised here, before anything is launched
@@ -299,6 +326,10 @@ class CausalLMRuntimeMixin:
         plens = self._prompt_lengths(prompts)
         if knockout is not None:
             knockout = args["knockout"] = self._check_knockout(knockout, plens, num_beams)      # None: every blocked set is empty
+        if patch is not None:
+            patch = args["patch"] = self._check_patch(patch, len(plens), num_beams, knockout)    # None: an empty row list
+        if want_hidden and num_beams != 1:
+            raise ValueError("want_hidden runs with greedy, sampled and label-constrained decoding, not with beams (num_beams > 1)")
         bad = [b for b, n in enumerate(plens) if n + max_new_tokens > limit]
         if bad and (overlong == "raise" or len(bad) == len(plens)):
             raise ValueError(f"prompt + new tokens of row(s) {bad} ({[plens[b] + max_new_tokens for b in bad]} positions) "
@@ -336,6 +367,10 @@ class CausalLMRuntimeMixin:
                 args["constraint"] = (constraint[0], [constraint[1][b] for b in keep])
             if knockout is not None:          # the surviving rows' entries
                 args["knockout"] = ([knockout[0][b] for b in keep], [knockout[1][b] for b in keep]) + tuple(knockout[2:])
+            if patch is not None:             # the surviving rows' vectors, under the indices they have among the survivors
+                vec = patch["vectors"]
+                args["patch"] = dict(patch, vectors=vec if vec.shape[0] == 1 else vec[torch.tensor(keep, device=vec.device)],
+                                     rows=[keep.index(b) for b in patch["rows"] if b in keep])
             return _undrop(self.generate([prompts[b] for b in keep], speech, **args), keep, bad, len(plens), pad)
         # ---- 3. beams
         if num_beams != 1:
@@ -352,7 +387,13 @@ class CausalLMRuntimeMixin:
             marks["prefill_start"].record()
         ko = None if knockout is None else self._knockout_state(knockout, Bn, max_len)
         ko_kw = {} if ko is None else {"knockout": ko}
-        logits = self._prefill_logits(h, lens, cache, ws.get("gen_last", (Bn, c.hidden), F32), **ko_kw)
+        rp = None if patch is None else self._patch_state(patch)
+        if rp is not None:
+            ko_kw = {"patch": rp}           # (never both: a patch together with a knockout is refused)
+        hidden = ws.get("gen_hidden", (Bn, c.n_layers + 1, c.hidden), F32) if want_hidden else None
+        logits = self._prefill_logits(h, lens, cache, ws.get("gen_last", (Bn, c.hidden), F32), capture=hidden, **ko_kw)
+        if rp is not None and rp.steps != "all":
+            ko_kw = {}                      # a prompt-only patch: the decode steps are the plain ones
         first = logits.clone() if want_first_logits else None
         trace = ws.get("gen_logits_trace", (max_new_tokens, Bn, c.vocab), F32) if want_step_logits else None
         if trace is not None:
@@ -378,7 +419,7 @@ class CausalLMRuntimeMixin:
                         trace[t + 1].copy_(lg)
                     tail(lg, t + 1)
             self._run_decode((Bn, max_len, steps, eos, pad, tail_key, trace is not None, self.kv_dtype)
-                             + (() if ko is None else (ko.uid,)), decode_loop)
+                             + (() if ko is None else (ko.uid,)) + (() if "patch" not in ko_kw else (rp.uid,)), decode_loop)
         if marks is not None:
             marks["decode_end"].record()
         # ---- 8. collect: the first host sync of the call, and its only D2H (two with a constraint)
@@ -388,9 +429,95 @@ class CausalLMRuntimeMixin:
             is_eos = torch.isin(out, torch.tensor([e for e in B._eos_pair(eos) if e >= 0]))
             first_eos = torch.where(is_eos.any(1), is_eos.float().argmax(1) + 1, torch.full((Bn,), max_new_tokens))
             width = int(first_eos.max())
-        return GenerateResult(tokens=out[:, :width].contiguous(), first_logits=first,
-                              step_logits=trace.clone() if trace is not None else None,
-                              token_logprobs=lps.cpu()[:, :width].contiguous() if lps is not None else None)
+        res = GenerateResult(tokens=out[:, :width].contiguous(), first_logits=first,
+                             step_logits=trace.clone() if trace is not None else None,
+                             token_logprobs=lps.cpu()[:, :width].contiguous() if lps is not None else None)
+        if hidden is not None:
+            res.hidden = hidden.clone()
+        return res
+
+    # ---- the residual stream at the deciding rows: the logit lens and generate(patch=...) ----
+    def layer_logits(self, hidden: torch.Tensor) -> torch.Tensor:
+        """The logit lens: what every site would answer.  ``hidden`` f32 [B, n_layers + 1, hidden] (``generate(want_hidden=True)``)
+        -> f32 [B, n_layers + 1, V] on the device: the final norm and the LM head on every site's row, through
+        ``LlamaHIP.logits`` over the B rows of a site — the launches generation makes for its first logits, so site n_layers is
+        ``first_logits`` bit for bit."""
+        c = self.lm_cfg
+        if not (isinstance(hidden, torch.Tensor) and hidden.dtype == F32 and hidden.dim() == 3
+                and tuple(hidden.shape[1:]) == (c.n_layers + 1, c.hidden)):
+            raise ValueError(f"hidden must be f32 [B, {c.n_layers + 1}, {c.hidden}]")
+        hidden = hidden.to(self.device)
+        out = torch.empty((hidden.shape[0], c.n_layers + 1, c.vocab), dtype=F32, device=self.device)
+        for site in range(c.n_layers + 1):
+            out[:, site].copy_(self.llama.logits(self.ws, hidden[:, site].contiguous(), name="lens_logits"))
+        return out
+
+    PATCH_KEYS = ("site", "vectors", "mode", "alpha", "rows", "steps")
+
+    def _check_patch(self, patch, n_prompts: int, num_beams: int, knockout):
+        """Host validation of ``generate(patch=...)``: everything is a ``ValueError`` raised before any launch.  Returns the
+        patch as a dict of all ``PATCH_KEYS`` — ``vectors`` f32 [n_prompts or 1, hidden], ``rows`` an ascending list — or None
+        when ``rows`` is empty."""
+        c = self.lm_cfg
+        if not isinstance(patch, dict):
+            raise ValueError(f"patch must be a dict with the keys {self.PATCH_KEYS}")
+        unknown = set(patch) - set(self.PATCH_KEYS)
+        if unknown or "site" not in patch or "vectors" not in patch:
+            raise ValueError(f"patch holds 'site' and 'vectors', and optionally 'mode', 'alpha', 'rows' and 'steps' (unknown: {sorted(unknown)})")
+        site, vec = patch["site"], patch["vectors"]
+        if isinstance(site, bool) or not isinstance(site, int) or not 0 <= site <= c.n_layers:
+            raise ValueError(f"patch: site {site!r} must be an integer in 0..{c.n_layers} (n_layers = the last layer's output)")
+        if not isinstance(vec, torch.Tensor) or vec.dtype != F32:
+            raise ValueError("patch: vectors must be a float32 tensor")
+        if vec.dim() == 1:
+            vec = vec[None]
+        if vec.dim() != 2 or vec.shape[1] != c.hidden or vec.shape[0] not in (1, n_prompts):
+            raise ValueError(f"patch: vectors of shape {tuple(patch['vectors'].shape)}: [{n_prompts}, {c.hidden}] (one per prompt), "
+                             f"[1, {c.hidden}] or [{c.hidden}] (shared)")
+        mode, steps = patch.get("mode", "replace"), patch.get("steps", "prompt")
+        if mode not in ("replace", "add"):
+            raise ValueError(f"patch: mode must be 'replace' or 'add', not {mode!r}")
+        if steps not in ("prompt", "all"):
+            raise ValueError(f"patch: steps must be 'prompt' or 'all', not {steps!r}")
+        try:
+            alpha = float(patch.get("alpha", 1.0))
+        except (TypeError, ValueError):
+            raise ValueError(f"patch: alpha must be a finite number, not {patch.get('alpha')!r}") from None
+        if not math.isfinite(alpha):
+            raise ValueError(f"patch: alpha must be finite, not {alpha}")
+        rows = patch.get("rows")
+        if rows is None:
+            rows = list(range(n_prompts))
+        else:
+            try:
+                rows = [int(b) for b in rows]
+            except (TypeError, ValueError):
+                raise ValueError(f"patch: rows must be None or a list of prompt indices, not {patch.get('rows')!r}") from None
+            if len(set(rows)) != len(rows):
+                raise ValueError(f"patch: rows {rows} lists a prompt twice")
+            if rows and not (0 <= min(rows) and max(rows) < n_prompts):
+                raise ValueError(f"patch: rows {rows} outside 0..{n_prompts - 1}")
+            rows = sorted(rows)
+        if num_beams != 1:
+            raise ValueError("patch runs with greedy, sampled and label-constrained decoding, not with beams (num_beams > 1)")
+        if knockout is not None:
+            raise ValueError("patch together with knockout is not supported")
+        if not rows:
+            return None
+        return dict(site=site, vectors=vec, mode=mode, alpha=alpha, rows=rows, steps=steps)
+
+    def _patch_state(self, patch) -> ResidPatch:
+        """The validated patch on the device, in graph-visible workspace buffers refilled on every call: the listed rows'
+        vectors (one row of the buffer when the vector is shared) and the listed sequences."""
+        c, ws = self.lm_cfg, self.ws
+        vec, rows = patch["vectors"], patch["rows"]
+        if vec.shape[0] != 1:
+            vec = vec[torch.tensor(rows, device=vec.device)]
+        vec_d = ws.get("gen_rp_vec", (vec.shape[0], c.hidden), F32)
+        rows_d = ws.get("gen_rp_rows", (len(rows),), I32)
+        vec_d.copy_(vec, non_blocking=True)
+        rows_d.copy_(torch.tensor(rows, dtype=I32), non_blocking=True)
+        return ResidPatch(vec_d, rows_d, tuple(rows), patch["site"], patch["mode"], patch["alpha"], patch["steps"])
 
     # ---- the prompt-attention readout: generate()'s prefill plus one launch per layer ----
     IGNORE_SEGMENT = 255       # a segment id that is counted nowhere, whatever n_seg is

@@ -518,6 +518,26 @@ int icl_gather_rows_f32(const float* src, int64_t ld_src, const int32_t* idx, fl
 int icl_gather_rows_bf16(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out,
                          int32_t rows, int32_t N, void* stream);
 
+/* ---- residual-stream capture and patching at listed rows ------------------------------------------------------------
+ * The read and the write of an in-context-learning study on the f32 residual stream h [.][ldh] (transformers:
+ * output_hidden_states=True plus a forward pre-hook on a decoder layer).  List entry r (0 <= r < n_rows) works on row
+ * row = rows[r] of h, for 0 <= i < hidden, in this order:
+ *   capture (unless NULL):  capture[r*ld_cap + i] = h[row*ldh + i], copied as bits: always the value BEFORE the patch;
+ *   vec (unless NULL), entry r's vector at vec + r*ld_vec (ld_vec == 0: one vector for all entries):
+ *     mode 0, replace:  h[row*ldh + i] = vec[r*ld_vec + i], copied as bits (NaN payloads, -0.0 and subnormals survive);
+ *     mode 1, add:      h[row*ldh + i] = __fmaf_rn(alpha, vec[r*ld_vec + i], h[row*ldh + i]): ONE rounding, of the exact
+ *                       alpha*v + h (not a rounded product and a rounded sum).  Mode 0 does not use alpha (still checked).
+ * Rows that no entry lists, and the columns of a listed row at or beyond hidden, are not written.  rows values must be rows of
+ * h (the caller's duty: the call cannot see that extent); a row listed TWICE is the caller's error — two blocks would race on
+ * it — and the host layers above refuse such lists.  capture and vec must not overlap h.  One block per entry, 16-byte moves,
+ * all address arithmetic in int64_t (ldh may exceed 2^32).
+ * ICL_EINVAL (before any launch, naming the argument): h or rows NULL; capture and vec both NULL; n_rows outside 1..65535;
+ * hidden <= 0 or not a multiple of 4; ldh, ld_cap (with capture) or a non-zero ld_vec (with vec) below hidden or not a multiple
+ * of 4; h, capture or vec not 16-byte aligned; mode outside {0, 1}; alpha not finite.
+ */
+int icl_resid_rows_f32(float* h, int64_t ldh, const int32_t* rows, int32_t n_rows, int32_t hidden, float* capture,
+                       int64_t ld_cap, const float* vec, int64_t ld_vec, int32_t mode, float alpha, void* stream);
+
 /* ---- K11 (beam search): one step of HF's static-shaped beam search + the cache reorder ------------------------------
  * icl_beam_step, per batch row b (num_beams K <= 8, max_new_tokens T <= 64, V >= 2K): log-softmax of the K beams' logits
  *   (row b*rows_per_batch + k; rows_per_batch == 1 at step 0, where the K beams still share the prompt's one distribution) plus
