@@ -622,7 +622,7 @@ class CustomSALMONN(BaseModel):
         self.batch_counter += 1
         return res
 
-    MAX_PIECES = 32        # segments the readout kernel sums (runtime.engines.MAX_READOUT_SEGMENTS): 14 non-SQA exemplars
+    MAX_PIECES = 32        # segments the readout kernel sums (runtime.probes.MAX_READOUT_SEGMENTS): 14 non-SQA exemplars
 
     def prompt_attention(self, samples: Dict[str, Any]) -> Dict[str, Any]:
         """Where the last prompt position (the query that decides the first generated token) looks, per piece of the wrapped

@@ -10,7 +10,7 @@ Reference call sites: models/custom_salmon.py:546-554 (encode_speech), :115-299 
 from __future__ import annotations
 
 import os
-from dataclasses import dataclass, replace
+from dataclasses import dataclass
 
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -608,27 +608,16 @@ class LlamaHIP:
 
     # ---- K10: prefill over ragged packed sequences ------------------------------------------------
     def prefill(self, ws: Workspace, h: torch.Tensor, seq_lens: List[int], cache: Optional["KVCache"] = None,
-                last_rows_only: bool = False, last_out: Optional[torch.Tensor] = None,
-                readout: Optional["AttnReadout"] = None, knockout: Optional["Knockout"] = None,
-                capture: Optional[torch.Tensor] = None, patch: Optional["ResidPatch"] = None) -> torch.Tensor:
+                last_rows_only: bool = False, last_out: Optional[torch.Tensor] = None, probes=None) -> torch.Tensor:
         """h f32 [sum S_b, hidden] (modified in place) -> same buffer holding the final hidden states.
 
-        ``capture`` f32 [n_seqs, n_layers + 1, hidden] and ``patch`` (both need ``last_rows_only``): the residual stream of the
-        sequences' LAST rows, read and written (icl_resid_rows_f32).  Site l < n_layers is ``h`` at the top of layer l, before
-        its input norm and before the branch into the trimmed last layer, so that layer's k / v of the row see the patch; site
-        n_layers is the gathered rows before they are returned.  ``capture[:, l]`` receives every sequence's row at every site,
-        pre-patch; at ``patch.site`` the listed sequences' rows are replaced or added to.  One launch per site with a capture
-        (two at the patched site when the patch lists only some sequences), one in all with a patch alone; without either the
-        layers launch what they launch.
-
-        ``knockout`` (needs ``last_rows_only`` and a bf16 cache): attention knockout.  In a layer of its window, after the
-        layer's ordinary attention launch, one more launch (icl_attn_decode_masked_bf16) rewrites the attention output of the
-        listed sequences' LAST rows from their rotated q and the cache, which holds every prompt position by then in every
-        prefill form; every other row keeps its bits, and without it the layers launch what they launch.
-
-        ``readout`` (needs ``last_rows_only`` and a bf16 cache): the prompt-attention readout.  In every layer, once q / k are
-        rotated and k is in the cache, one more launch (icl_attn_segmass_bf16) writes the last row's attention mass per key
-        segment into the layer's slice of ``readout``; nothing else changes, and without it the layers launch what they launch.
+        ``probes`` (a ``probes.Probes``; needs ``last_rows_only``, and a bf16 cache where it reads one): what is read and
+        written at the sequences' LAST rows.  The layers call it at three points and launch what they launch otherwise:
+        ``residual_site(l, h)`` at the top of layer l, before its input norm and before the branch into the trimmed last layer —
+        so that layer's k / v of the row see a rewritten stream — and, as site n_layers, on the gathered rows before they are
+        returned; ``keys_appended`` once q / k are rotated and k is in the cache, in front of the attention launch;
+        ``attention_written`` after the layer's attention launch, when the cache holds every prompt position in every prefill
+        form — it may rewrite the last rows of ``att``, every other row keeps its bits.
 
         ``last_rows_only`` (needs a cache): return only the final hidden state of the LAST row of every sequence, f32
         [len(seq_lens), hidden] (written into ``last_out`` when given) — what generation feeds to the final norm and the LM
@@ -643,9 +632,6 @@ class LlamaHIP:
             cu_h.append(cu_h[-1] + s)
         assert max(seq_lens) <= c.max_pos
         assert cache is not None or not last_rows_only, "prefill(last_rows_only=True) needs a KV cache"
-        assert readout is None or (last_rows_only and cache.dtype == "bf16"), "the attention readout reads the last rows' q and a bf16 K cache"
-        assert knockout is None or (last_rows_only and cache.dtype == "bf16"), "attention knockout rewrites the last rows from a bf16 KV cache"
-        assert (capture is None and patch is None) or last_rows_only, "residual capture / patching works on the last rows (last_rows_only)"
         pos = _i32([p for s in seq_lens for p in range(s)], dev)
         sid = _i32([b for b, s in enumerate(seq_lens) for _ in range(s)], dev)
         cu = _i32(cu_h, dev)
@@ -668,20 +654,14 @@ class LlamaHIP:
             last_idx = _i32([e - 1 for e in cu_h[1:]], dev)
             out = last_out if last_out is not None else ws.get("pfl_h", (len(seq_lens), hd), F32)
         sites = prefill_sites(c, w.k_aug)
-        ko_lens = ko_rows = None
-        if knockout is not None:        # the prompt lengths as the masked launch's key counts; the listed sequences' last rows
-            ko_lens = _i32(seq_lens, dev)
-            ko_rows = _i32([cu_h[b + 1] - 1 for b in knockout.listed], dev)
-        rp_rows = None if patch is None else _i32([cu_h[b + 1] - 1 for b in patch.listed], dev)   # the listed last packed rows
+        if probes is not None:
+            probes.start_prefill(seq_lens, cu_h, last_idx, cache)      # its preconditions and its host tables of this call
         for i, L in enumerate(w.layers):
-            if capture is not None or (patch is not None and patch.site == i):
-                resid_site(i, h, last_idx, rp_rows, capture, patch)
+            if probes is not None:
+                probes.residual_site(i, h, packed=True)
             kc, vc, ks, vs = cache.layer(i) if cache is not None else (None, None, None, None)
-            ko = knockout if knockout is not None and knockout.covers(i) else None
             if trim and i == len(w.layers) - 1:
-                hg = self._last_layer_rows(ws, L, h, seq_lens, pos, sid, cu, kc, vc, max_len, last_idx, out,
-                                           readout=None if readout is None else (readout, i),
-                                           knockout=None if ko is None else (ko, ko_lens))
+                hg = self._last_layer_rows(ws, L, h, seq_lens, pos, sid, cu, kc, vc, max_len, last_idx, out, probes=probes)
                 break
             xn = self._xn(ws, L, h, M, "pf_", decode=False)
             qkv = ws.get("pf_qkv", (M, qkv_width(c)), BF16)
@@ -712,25 +692,24 @@ class LlamaHIP:
                 B.rope_kv(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, kc, vc, H, D, max_len, M=M)
             if fp8:
                 B.kv_append_fp8(qkv, k_off, v_off, pos, sid, kc, vc, ks, vs, H, D, max_len, M=M)
-            if readout is not None:     # the last rows of the QKV buffer are the queries; their keys are in the cache by now
-                readout.launch(i, qkv[:, :k_off], last_idx, kc, c, max_len)
+            if probes is not None:      # the last rows of the QKV buffer are the deciding queries; their keys are in the cache by now
+                probes.keys_appended(i, qkv[:, :k_off], kc, c, max_len, packed=True)
             if in_cache:
                 B.attn_fwd(qkv[:, :hd], kc, vc, att, cu, maxS, H, D, D ** -0.5, causal=True, kv_cache_max_len=max_len)
             else:
                 B.attn_fwd(qkv[:, :k_off], qkv[:, k_off:v_off], qkv[:, v_off:], att, cu, maxS, H, D, D ** -0.5, causal=True,
                            n_kv_heads=c.kv_heads if gqa else 0)
-            if ko is not None:          # the listed last rows again, under their masks
-                ko.launch(qkv[:, :k_off], att, ko_rows, kc, vc, ko_lens, c, max_len)
+            if probes is not None:
+                probes.attention_written(i, qkv[:, :k_off], att, kc, vc, c, max_len, packed=True)
             self._attn_out_mlp(ws, L, h, xn, att, "pf_", sites, None)
         else:
             hg = B.gather_rows(h, last_idx, out) if last_rows_only else h
-        if capture is not None or (patch is not None and patch.site == len(w.layers)):     # gathered row b is sequence b's
-            resid_site(len(w.layers), hg, _i32(list(range(len(seq_lens))), dev), None if patch is None else patch.row_seq,
-                       capture, patch)
+        if probes is not None:          # gathered row b is sequence b's
+            probes.residual_site(len(w.layers), hg)
         return hg
 
     def _last_layer_rows(self, ws: Workspace, L, h, seq_lens: List[int], pos, sid, cu, kc, vc, max_len: int,
-                         last_idx, hg, readout=None, knockout=None) -> torch.Tensor:
+                         last_idx, hg, probes=None) -> torch.Tensor:
         """The last decoder layer of a prefill whose caller reads the last row of every sequence only: the layer's k / v are
         projected (and appended to the cache) for all M rows; q, the attention, o_proj, the post-attention norm and the MLP run
         on the len(seq_lens) gathered rows.  Exact, not approximate: every kernel here computes a row independently of its
@@ -738,7 +717,8 @@ class LlamaHIP:
         order (tiles 1 - 3 agree, so the small launches are pinned to tile 3 instead of the library's small-M choice), the same
         fused RoPE epilogue at the row's position, and the full attention launch's wave, lane and 64-key tile sequence
         (icl_attn_fwd_suffix_bf16, q_len = 1).  The gathered buffers have names of their own (pfl_*): the full-height ones
-        keep their size.  Returns ``hg``, f32 [len(seq_lens), hidden]: the rows' final hidden states."""
+        keep their size.  ``probes``: ``prefill``'s, called on the gathered rows — row b is sequence b's — at the same two points
+        around the attention launch.  Returns ``hg``, f32 [len(seq_lens), hidden]: the rows' final hidden states."""
         c, w = self.w.cfg, self.w
         hd, D, H = c.hidden, c.head_dim, c.n_heads
         M, Bn, dev = sum(seq_lens), len(seq_lens), h.device
@@ -755,13 +735,13 @@ class LlamaHIP:
         q = ws.get("pfl_q", (Bn, hd), BF16)
         B.gemm(xg, L.wqkv[:hd], q, bias=L.bqkv[:hd] if L.bqkv is not None else None, tile=3,
                rope=(hd, hd, *rope, _i32([s - 1 for s in seq_lens], dev), None, None, None, H, D, max_len))
-        if readout is not None:         # (AttnReadout, layer): the gathered rows' rotated q, one per sequence
-            readout[0].launch(readout[1], q, None, kc, c, max_len)
+        if probes is not None:
+            probes.keys_appended(len(w.layers) - 1, q, kc, c, max_len)
         att = ws.get("pfl_att", (Bn, hd), BF16)
         B.attn_fwd(q, kc, vc, att, cu, max(seq_lens), H, D, D ** -0.5, causal=True, kv_cache_max_len=max_len,
                    cu_q=_i32(list(range(Bn + 1)), dev))
-        if knockout is not None:        # (Knockout, prompt lengths): gathered row b is sequence b's last row
-            knockout[0].launch(q, att, knockout[0].row_seq, kc, vc, knockout[1], c, max_len)
+        if probes is not None:
+            probes.attention_written(len(w.layers) - 1, q, att, kc, vc, c, max_len)
         self._attn_out_mlp(ws, L, hg, xg, att, "pfl_", prefill_sites(c, w.k_aug, tile=3), None)
         return hg
 
@@ -779,17 +759,15 @@ class LlamaHIP:
 
     # ---- K11: one decode step for Bn sequences -----------------------------------------------------
     def decode_step(self, ws: Workspace, cache: "KVCache", next_ids: torch.Tensor, pos: torch.Tensor,
-                    lens: torch.Tensor, sid: torch.Tensor, knockout: Optional["Knockout"] = None,
-                    patch: Optional["ResidPatch"] = None) -> torch.Tensor:
-        """``patch`` (one whose ``steps`` is "all"): at the top of layer ``patch.site`` one launch (icl_resid_rows_f32) replaces or
-        adds to the listed rows of ``h``.  The previous layer's ``down`` launch may have written this layer's normed input from the
-        unpatched ``h``, so the patched layer runs its input norm as a launch of its own (site n_layers: the final norm).
-
-        ``knockout`` (a bf16 cache): in a layer of its window one more launch (icl_attn_decode_masked_bf16) rewrites the listed
-        rows of the attention output under their masks.  The step then takes the two-launch RoPE + attention form at every batch
-        size — the fused launch leaves q unrotated in ``qkv``; the two forms are bit-identical — so unlisted rows keep their bits."""
+                    lens: torch.Tensor, sid: torch.Tensor, probes=None) -> torch.Tensor:
+        """``probes`` (a ``probes.Probes``, the decode steps' bundle): ``residual_site(l, h)`` at the top of layer l (n_layers: in
+        front of the final norm) says whether it rewrote rows of ``h``.  The previous layer's ``down`` launch may have written
+        this layer's normed input from the unwritten ``h``, so the layer then runs its input norm as a launch of its own (site
+        n_layers: the final norm).  ``attention_written`` after a layer's attention launch may rewrite rows of the attention
+        output from the rotated q.  When ``masks_attention`` says it will, the step takes the two-launch RoPE + attention form
+        at every batch size — the fused launch leaves q unrotated in ``qkv``; the two forms are bit-identical — so the other rows
+        keep their bits."""
         c, w = self.w.cfg, self.w
-        assert knockout is None or cache.dtype == "bf16", "attention knockout reads a bf16 KV cache"
         Bn = next_ids.numel()
         h = self.embed(ws, next_ids, None, name="dc_h")
         H, D = c.n_heads, c.head_dim
@@ -811,13 +789,13 @@ class LlamaHIP:
         # Same-box A/B (tools/ab_decode_rope.sh, profiles/r04_decode_rope_ab.txt): at 256 rows decode 143.2 -> 142.5 ms; at ONE
         # sequence 58.4 -> 59.6 ms per utterance — the rotation's dependent loads (pos -> cos / sin, q, k) sit in front of a
         # latency-bound attention and cost more than the 5-us launch they replace — so small batches keep the two launches.
-        fuse_rope = self.fuse_decode_rope and Bn > 8 and not c.qk_norm and knockout is None
+        masked = probes is not None and probes.masks_attention(cache)
+        fuse_rope = self.fuse_decode_rope and Bn > 8 and not c.qk_norm and not masked
         ready = False
         for i, L in enumerate(layers):
             kc, vc, ks, vs = cache.layer(i)
-            if patch is not None and patch.site == i:
-                patch.launch(h, patch.row_seq)
-                ready = False       # what the previous down wrote is the norm of the unpatched rows
+            if probes is not None and probes.residual_site(i, h):
+                ready = False       # what the previous down wrote is the norm of the rows as they were
             xn = self._xn(ws, L, h, Bn, "dc_", decode=True, ready=ready)
             self._site_gemm(L, sites, "qkv", xn, qkv, wsk, bias=L.bqkv)
             if c.qk_norm:         # QK-norm (Qwen3): two launches at every batch size, norm + RoPE + append and the decode attention
@@ -841,137 +819,13 @@ class LlamaHIP:
             else:
                 B.rope_kv(qkv, k_off, v_off, w.rope_cos, w.rope_sin, pos, sid, kc, vc, H, D, max_len, M=Bn)
                 B.attn_decode(qkv[:, :k_off], kc, vc, att, lens, H, D, max_len, scale)
-            if knockout is not None and knockout.covers(i):
-                knockout.launch(qkv[:, :k_off], att, knockout.row_seq, kc, vc, lens, c, max_len)
+            if probes is not None:
+                probes.attention_written(i, qkv[:, :k_off], att, kc, vc, c, max_len, lens=lens)
             nxt = (layers[i + 1].rms1, xn_next) if i + 1 < len(layers) else (w.norm, xn_final)
             ready = self._attn_out_mlp(ws, L, h, xn, att, "dc_", sites, wsk, next_norm=nxt)
-        if patch is not None and patch.site == len(layers):
-            patch.launch(h, patch.row_seq)
+        if probes is not None and probes.residual_site(len(layers), h):
             ready = False
         return self.logits(ws, h, name="dc_logits", xn_ready=ready)
-
-
-MAX_READOUT_SEGMENTS = 32      # icl_attn_segmass_bf16: one thread per (head of a K/V group, segment)
-
-
-@dataclass
-class AttnReadout:
-    """Where ``LlamaHIP.prefill(readout=...)`` leaves the prompt-attention readout of its sequences, all on the device:
-    ``seg`` uint8 [n_seqs, >= cache max_len] the segment of every prompt position (>= n_seg: counted nowhere), ``lens`` int32
-    [n_seqs] the prompt lengths, ``mass`` f32 [n_layers, n_seqs, n_heads, n_seg] and ``probs`` None or f32 [n_layers, n_seqs,
-    n_heads, >= max_len] (written)."""
-    seg: torch.Tensor
-    lens: torch.Tensor
-    mass: torch.Tensor
-    probs: Optional[torch.Tensor] = None
-
-    def rows(self, b0: int, b1: int) -> "AttnReadout":
-        """The readout of sequences b0 .. b1-1 (views), for a prefill over that chunk of the batch (``KVCache.rows``)."""
-        return AttnReadout(self.seg[b0:b1], self.lens[b0:b1], self.mass[:, b0:b1],
-                           None if self.probs is None else self.probs[:, b0:b1])
-
-    def launch(self, layer: int, q: torch.Tensor, q_rows: Optional[torch.Tensor], kc: torch.Tensor, cfg, max_len: int) -> None:
-        B.attn_segmass(q, kc, self.lens, self.seg, self.mass[layer], cfg.n_heads, cfg.head_dim, max_len, cfg.head_dim ** -0.5,
-                       n_kv_heads=cfg.kv_heads, q_rows=q_rows, probs=None if self.probs is None else self.probs[layer])
-
-
-MAX_KNOCKOUT_SEGMENTS = 32     # icl_attn_decode_masked_bf16: one bit of a u32 per segment; ids >= 32 are never blocked
-
-
-@dataclass
-class Knockout:
-    """Attention knockout, all on the device: in decoder layers ``layers[0] .. layers[1] - 1`` the LAST prompt row and every
-    generated row of the listed sequences attend as if the keys of their blocked segments were not there
-    (icl_attn_decode_masked_bf16 rewrites those rows of the attention output after the layer's ordinary attention launch).
-    ``seg`` uint8 [n_seqs, >= cache max_len]: the segment of every cache position, 255 past the prompt (generated positions are
-    always visible); ``blocked`` int32 [n_listed, n_heads]: bit g of a (listed row, query head) = segment g is not read;
-    ``row_seq`` int32 [n_listed]: the listed sequences, ascending (``listed``: the same on the host).  The runtime keeps all
-    three in graph-visible workspace buffers and refills them on every call, so ``uid`` — what a captured decode graph bakes in
-    besides those pointers: the number of listed rows (a grid size) and the layer window — keys the decode graphs."""
-    seg: torch.Tensor
-    blocked: torch.Tensor
-    row_seq: torch.Tensor
-    listed: Tuple[int, ...]
-    layers: Tuple[int, int]
-
-    @property
-    def uid(self):
-        return ("knockout", len(self.listed), self.layers[0], self.layers[1])
-
-    def rows(self, b0: int, b1: int) -> Optional["Knockout"]:
-        """The knockout of sequences b0 .. b1-1 (views; sequence ids relative to b0), for a prefill over that chunk of the
-        batch (``KVCache.rows``); None when the chunk lists no row."""
-        lo = sum(1 for s in self.listed if s < b0)
-        hi = sum(1 for s in self.listed if s < b1)
-        if lo == hi:
-            return None
-        if b0 == 0 and hi == len(self.listed):
-            return replace(self, seg=self.seg[b0:b1])
-        sub = tuple(s - b0 for s in self.listed[lo:hi])
-        return Knockout(self.seg[b0:b1], self.blocked[lo:hi], _i32(sub, self.seg.device), sub, self.layers)
-
-    def covers(self, layer: int) -> bool:
-        return self.layers[0] <= layer < self.layers[1]
-
-    def launch(self, q: torch.Tensor, att: torch.Tensor, row_q: torch.Tensor, kc, vc, lens: torch.Tensor, cfg, max_len: int) -> None:
-        """Rewrite rows ``row_q`` (int32 [n_listed]) of ``att`` from the same rows of ``q`` (rotated) over the bf16 cache."""
-        B.attn_decode_masked(q, kc, vc, att, lens, self.seg, self.blocked, self.row_seq, row_q, cfg.n_heads, cfg.head_dim, max_len,
-                             cfg.head_dim ** -0.5, n_kv_heads=cfg.kv_heads)
-
-
-@dataclass
-class ResidPatch:
-    """Residual-stream patching at the deciding rows, all on the device: at site ``site`` (0 .. n_layers - 1: the input of that
-    decoder layer, before its norm; n_layers: the output of the last layer, before the final norm) the LAST prompt row of the
-    listed sequences — and with ``steps == "all"`` every generated row — is replaced by its vector, or gets ``alpha`` times its
-    vector added (icl_resid_rows_f32).  ``vectors`` f32 [n_listed, hidden], or [1, hidden]: one vector for all listed rows;
-    ``row_seq`` int32 [n_listed]: the listed sequences, ascending and distinct (``listed``: the same on the host).  The runtime
-    keeps both tensors in graph-visible workspace buffers and refills them on every call, so ``uid`` — what a captured decode
-    graph bakes in besides those pointers: the number of listed rows (a grid size), whether the vector is shared (a leading
-    dimension), site, mode, steps and alpha, a by-value kernel argument — keys the decode graphs."""
-    vectors: torch.Tensor
-    row_seq: torch.Tensor
-    listed: Tuple[int, ...]
-    site: int
-    mode: str = "replace"
-    alpha: float = 1.0
-    steps: str = "prompt"
-
-    @property
-    def uid(self):
-        return ("resid_patch", len(self.listed), int(self.vectors.shape[0]), self.site, self.mode, self.steps, float(self.alpha))
-
-    def rows(self, b0: int, b1: int) -> Optional["ResidPatch"]:
-        """The patch of sequences b0 .. b1-1 (views; sequence ids relative to b0), for a prefill over that chunk of the batch
-        (``KVCache.rows``); None when the chunk lists no row."""
-        lo = sum(1 for s in self.listed if s < b0)
-        hi = sum(1 for s in self.listed if s < b1)
-        if lo == hi:
-            return None
-        if b0 == 0 and hi == len(self.listed):
-            return self
-        sub = tuple(s - b0 for s in self.listed[lo:hi])
-        vec = self.vectors if self.vectors.shape[0] == 1 else self.vectors[lo:hi]
-        return replace(self, vectors=vec, row_seq=_i32(sub, self.vectors.device), listed=sub)
-
-    def launch(self, h: torch.Tensor, rows: torch.Tensor, capture: Optional[torch.Tensor] = None) -> None:
-        """Patch rows ``rows`` (int32 [n_listed]) of ``h``; ``capture`` f32 [n_listed, hidden] receives their pre-patch bits."""
-        B.resid_rows(h, rows, capture=capture, vec=self.vectors, mode=self.mode, alpha=self.alpha)
-
-
-def resid_site(site: int, h: torch.Tensor, all_rows: torch.Tensor, listed_rows: Optional[torch.Tensor],
-               capture: Optional[torch.Tensor], patch: Optional[ResidPatch]) -> None:
-    """One site of a prefill: ``capture[:, site]`` (f32 [n_seqs, n_layers + 1, hidden] or None) receives rows ``all_rows`` of
-    ``h``, one per sequence, and a ``patch`` at this site rewrites rows ``listed_rows``.  One launch does both when the patch
-    lists every sequence; a patch of some sequences next to a capture of all is a capture launch and then a patch launch."""
-    cap = None if capture is None else capture[:, site]
-    pt = patch if patch is not None and patch.site == site else None
-    if cap is not None and pt is not None and pt.listed == tuple(range(all_rows.numel())):
-        return pt.launch(h, all_rows, capture=cap)
-    if cap is not None:
-        B.resid_rows(h, all_rows, capture=cap)
-    if pt is not None:
-        pt.launch(h, listed_rows)
 
 
 KV_DTYPES = ("bf16", "fp8")

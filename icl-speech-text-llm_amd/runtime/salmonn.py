@@ -9,7 +9,7 @@ gather kernel (K9).  Everything arithmetic goes through libicl_hip; there is no 
 """
 from __future__ import annotations
 
-import math
+import gc
 import os
 
 from dataclasses import dataclass
@@ -18,9 +18,9 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import binding as B
+from . import probes as P
 from .config import SalmonnCfg
-from .engines import (BF16, F32, I32, MAX_KNOCKOUT_SEGMENTS, MAX_READOUT_SEGMENTS, AttnReadout, BeatsHIP, Knockout, KVCache, LlamaHIP, LogMel, ResidPatch, SpeechQFormerHIP, WhisperEncoderHIP, Workspace, _i32,
-                      check_kv_dtype)
+from .engines import BF16, F32, I32, BeatsHIP, KVCache, LlamaHIP, LogMel, SpeechQFormerHIP, WhisperEncoderHIP, Workspace, _i32, check_kv_dtype
 from .packing import normalize_keys, pack_beats, pack_llama, pack_qformer, pack_whisper
 
 Segment = Union[Sequence[int], Tuple[str, int, int]]  # token ids | ("speech", first_row, n_rows)
@@ -155,27 +155,20 @@ class CausalLMRuntimeMixin:
         assert max_len <= self.lm_cfg.max_pos, f"prompt + new tokens ({need}) exceeds max_pos {self.lm_cfg.max_pos}"  # validated
         return max_len
 
-    def _prefill_logits(self, h, lens: List[int], cache: KVCache, last, readout: Optional[AttnReadout] = None,
-                        knockout: Optional[Knockout] = None, capture: Optional[torch.Tensor] = None,
-                        patch: Optional[ResidPatch] = None) -> torch.Tensor:
+    def _prefill_logits(self, h, lens: List[int], cache: KVCache, last, probes: Optional[P.Probes] = None) -> torch.Tensor:
         """Prefill in chunks of at most ``prefill_chunk`` sequences (the caller decodes ALL of them together: the decode GEMMs
         stream the weights once per step whatever the row count — 256 rows cost 0.84 us each against 1.06 at 128 — while the
         prefill GEMMs measured 1.3 % faster per utterance at 128 sequences than at 256; a sequence's arithmetic does not depend
         on its neighbours in either phase, so the split changes no result).  Only the last position of every prompt is read
         afterwards: the prefill writes those rows into ``last`` f32 [n, hidden] and trims its last layer to them
-        (LlamaHIP.prefill, last_rows_only).  Returns their logits, f32 [n, vocab]."""
+        (LlamaHIP.prefill, last_rows_only).  ``probes``: each chunk gets its rows of them (None: a chunk that lists no row
+        launches as ever).  Returns their logits, f32 [n, vocab]."""
         r0 = 0
         for b0 in range(0, len(lens), self.prefill_chunk):
             b1 = min(len(lens), b0 + self.prefill_chunk)
             r1 = r0 + sum(lens[b0:b1])
-            ko = None if knockout is None else knockout.rows(b0, b1)       # None: a chunk that lists no row launches as ever
-            kw = {} if ko is None else {"knockout": ko}
-            if capture is not None:
-                kw["capture"] = capture[b0:b1]
-            if patch is not None and patch.rows(b0, b1) is not None:
-                kw["patch"] = patch.rows(b0, b1)
             self.llama.prefill(self.ws, h[r0:r1], lens[b0:b1], cache.rows(b0, b1), last_rows_only=True, last_out=last[b0:b1],
-                               readout=None if readout is None else readout.rows(b0, b1), **kw)
+                               probes=None if probes is None else probes.rows(b0, b1))
             r0 = r1
         return self.llama.logits(self.ws, last, name="gen_logits")
 
@@ -197,7 +190,9 @@ class CausalLMRuntimeMixin:
         """Enqueue ``decode_loop()``.  It is launch-bound at small batch (~17 kernels x layers x steps), so with ``use_graphs``
         a key's first call runs it eagerly (which sizes every workspace buffer), the second captures it into a HIP graph and
         replays that, later ones replay — all pointers are workspace-stable and nothing inside synchronises or allocates.  A
-        graph bakes raw pointers into workspace buffers: a move (``ws.generation``) retires every graph and warm key."""
+        graph bakes raw pointers into workspace buffers: a move (``ws.generation``) retires every graph and warm key.  The
+        garbage collector is off inside the capture: a dead reference cycle may hold GPU objects (another runtime's graphs,
+        events, buffers) whose finalisers make HIP calls that a capturing stream does not allow — the process aborts."""
         if not self.use_graphs:
             return decode_loop()
         if self._graph_gen != self.ws.generation:
@@ -213,11 +208,15 @@ class CausalLMRuntimeMixin:
             graph = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
             prof, B.GEMM_PROFILE = B.GEMM_PROFILE, None              # no timing events inside a stream capture
+            gc_was_on = gc.isenabled()
+            gc.disable()
             try:
                 with torch.cuda.graph(graph):
                     decode_loop()
             finally:
                 B.GEMM_PROFILE = prof
+                if gc_was_on:
+                    gc.enable()
             while len(self._graphs) >= self.MAX_GRAPHS:
                 self._graphs.pop(next(iter(self._graphs)))
             self._graphs[gkey] = graph
@@ -325,9 +324,9 @@ class CausalLMRuntimeMixin:
         limit = c.max_pos // cache_len_multiple * cache_len_multiple      # cache lengths are multiples of cache_len_multiple
         plens = self._prompt_lengths(prompts)
         if knockout is not None:
-            knockout = args["knockout"] = self._check_knockout(knockout, plens, num_beams)      # None: every blocked set is empty
+            knockout = args["knockout"] = P.check_knockout(knockout, c, self.kv_dtype, plens, num_beams)   # None: every blocked set is empty
         if patch is not None:
-            patch = args["patch"] = self._check_patch(patch, len(plens), num_beams, knockout)    # None: an empty row list
+            patch = args["patch"] = P.check_patch(patch, c, len(plens), num_beams, knockout)     # None: an empty row list
         if want_hidden and num_beams != 1:
             raise ValueError("want_hidden runs with greedy, sampled and label-constrained decoding, not with beams (num_beams > 1)")
         bad = [b for b, n in enumerate(plens) if n + max_new_tokens > limit]
@@ -365,12 +364,7 @@ class CausalLMRuntimeMixin:
             keep = [b for b in range(len(plens)) if b not in set(bad)]
             if constraint is not None:
                 args["constraint"] = (constraint[0], [constraint[1][b] for b in keep])
-            if knockout is not None:          # the surviving rows' entries
-                args["knockout"] = ([knockout[0][b] for b in keep], [knockout[1][b] for b in keep]) + tuple(knockout[2:])
-            if patch is not None:             # the surviving rows' vectors, under the indices they have among the survivors
-                vec = patch["vectors"]
-                args["patch"] = dict(patch, vectors=vec if vec.shape[0] == 1 else vec[torch.tensor(keep, device=vec.device)],
-                                     rows=[keep.index(b) for b in patch["rows"] if b in keep])
+            args["knockout"], args["patch"] = P.keep_rows(knockout, patch, keep)
             return _undrop(self.generate([prompts[b] for b in keep], speech, **args), keep, bad, len(plens), pad)
         # ---- 3. beams
         if num_beams != 1:
@@ -385,15 +379,10 @@ class CausalLMRuntimeMixin:
         marks = getattr(self, "phase_marks", None)     # optional {name: torch.cuda.Event}: bench.py times prefill / decode with it
         if marks is not None:
             marks["prefill_start"].record()
-        ko = None if knockout is None else self._knockout_state(knockout, Bn, max_len)
-        ko_kw = {} if ko is None else {"knockout": ko}
-        rp = None if patch is None else self._patch_state(patch)
-        if rp is not None:
-            ko_kw = {"patch": rp}           # (never both: a patch together with a knockout is refused)
         hidden = ws.get("gen_hidden", (Bn, c.n_layers + 1, c.hidden), F32) if want_hidden else None
-        logits = self._prefill_logits(h, lens, cache, ws.get("gen_last", (Bn, c.hidden), F32), capture=hidden, **ko_kw)
-        if rp is not None and rp.steps != "all":
-            ko_kw = {}                      # a prompt-only patch: the decode steps are the plain ones
+        probes = P.Probes(knockout=None if knockout is None else P.knockout_state(ws, c, knockout, max_len), capture=hidden,
+                          patch=None if patch is None else P.patch_state(ws, c, patch))      # (never both a knockout and a patch)
+        logits = self._prefill_logits(h, lens, cache, ws.get("gen_last", (Bn, c.hidden), F32), probes=probes)
         first = logits.clone() if want_first_logits else None
         trace = ws.get("gen_logits_trace", (max_new_tokens, Bn, c.vocab), F32) if want_step_logits else None
         if trace is not None:
@@ -411,15 +400,15 @@ class CausalLMRuntimeMixin:
         steps = max_new_tokens - 1
         if steps:
             pos_all, len_all, sid = self._step_tables(lens, steps)
+            step_probes = probes.decode_steps()     # None: the decode steps are the plain ones
 
             def decode_loop():
                 for t in range(steps):
-                    lg = self.llama.decode_step(ws, cache, nxt, pos_all[t], len_all[t], sid, **ko_kw)
+                    lg = self.llama.decode_step(ws, cache, nxt, pos_all[t], len_all[t], sid, probes=step_probes)
                     if trace is not None:
                         trace[t + 1].copy_(lg)
                     tail(lg, t + 1)
-            self._run_decode((Bn, max_len, steps, eos, pad, tail_key, trace is not None, self.kv_dtype)
-                             + (() if ko is None else (ko.uid,)) + (() if "patch" not in ko_kw else (rp.uid,)), decode_loop)
+            self._run_decode((Bn, max_len, steps, eos, pad, tail_key, trace is not None, self.kv_dtype) + probes.graph_key(), decode_loop)
         if marks is not None:
             marks["decode_end"].record()
         # ---- 8. collect: the first host sync of the call, and its only D2H (two with a constraint)
@@ -452,76 +441,7 @@ class CausalLMRuntimeMixin:
             out[:, site].copy_(self.llama.logits(self.ws, hidden[:, site].contiguous(), name="lens_logits"))
         return out
 
-    PATCH_KEYS = ("site", "vectors", "mode", "alpha", "rows", "steps")
-
-    def _check_patch(self, patch, n_prompts: int, num_beams: int, knockout):
-        """Host validation of ``generate(patch=...)``: everything is a ``ValueError`` raised before any launch.  Returns the
-        patch as a dict of all ``PATCH_KEYS`` — ``vectors`` f32 [n_prompts or 1, hidden], ``rows`` an ascending list — or None
-        when ``rows`` is empty."""
-        c = self.lm_cfg
-        if not isinstance(patch, dict):
-            raise ValueError(f"patch must be a dict with the keys {self.PATCH_KEYS}")
-        unknown = set(patch) - set(self.PATCH_KEYS)
-        if unknown or "site" not in patch or "vectors" not in patch:
-            raise ValueError(f"patch holds 'site' and 'vectors', and optionally 'mode', 'alpha', 'rows' and 'steps' (unknown: {sorted(unknown)})")
-        site, vec = patch["site"], patch["vectors"]
-        if isinstance(site, bool) or not isinstance(site, int) or not 0 <= site <= c.n_layers:
-            raise ValueError(f"patch: site {site!r} must be an integer in 0..{c.n_layers} (n_layers = the last layer's output)")
-        if not isinstance(vec, torch.Tensor) or vec.dtype != F32:
-            raise ValueError("patch: vectors must be a float32 tensor")
-        if vec.dim() == 1:
-            vec = vec[None]
-        if vec.dim() != 2 or vec.shape[1] != c.hidden or vec.shape[0] not in (1, n_prompts):
-            raise ValueError(f"patch: vectors of shape {tuple(patch['vectors'].shape)}: [{n_prompts}, {c.hidden}] (one per prompt), "
-                             f"[1, {c.hidden}] or [{c.hidden}] (shared)")
-        mode, steps = patch.get("mode", "replace"), patch.get("steps", "prompt")
-        if mode not in ("replace", "add"):
-            raise ValueError(f"patch: mode must be 'replace' or 'add', not {mode!r}")
-        if steps not in ("prompt", "all"):
-            raise ValueError(f"patch: steps must be 'prompt' or 'all', not {steps!r}")
-        try:
-            alpha = float(patch.get("alpha", 1.0))
-        except (TypeError, ValueError):
-            raise ValueError(f"patch: alpha must be a finite number, not {patch.get('alpha')!r}") from None
-        if not math.isfinite(alpha):
-            raise ValueError(f"patch: alpha must be finite, not {alpha}")
-        rows = patch.get("rows")
-        if rows is None:
-            rows = list(range(n_prompts))
-        else:
-            try:
-                rows = [int(b) for b in rows]
-            except (TypeError, ValueError):
-                raise ValueError(f"patch: rows must be None or a list of prompt indices, not {patch.get('rows')!r}") from None
-            if len(set(rows)) != len(rows):
-                raise ValueError(f"patch: rows {rows} lists a prompt twice")
-            if rows and not (0 <= min(rows) and max(rows) < n_prompts):
-                raise ValueError(f"patch: rows {rows} outside 0..{n_prompts - 1}")
-            rows = sorted(rows)
-        if num_beams != 1:
-            raise ValueError("patch runs with greedy, sampled and label-constrained decoding, not with beams (num_beams > 1)")
-        if knockout is not None:
-            raise ValueError("patch together with knockout is not supported")
-        if not rows:
-            return None
-        return dict(site=site, vectors=vec, mode=mode, alpha=alpha, rows=rows, steps=steps)
-
-    def _patch_state(self, patch) -> ResidPatch:
-        """The validated patch on the device, in graph-visible workspace buffers refilled on every call: the listed rows'
-        vectors (one row of the buffer when the vector is shared) and the listed sequences."""
-        c, ws = self.lm_cfg, self.ws
-        vec, rows = patch["vectors"], patch["rows"]
-        if vec.shape[0] != 1:
-            vec = vec[torch.tensor(rows, device=vec.device)]
-        vec_d = ws.get("gen_rp_vec", (vec.shape[0], c.hidden), F32)
-        rows_d = ws.get("gen_rp_rows", (len(rows),), I32)
-        vec_d.copy_(vec, non_blocking=True)
-        rows_d.copy_(torch.tensor(rows, dtype=I32), non_blocking=True)
-        return ResidPatch(vec_d, rows_d, tuple(rows), patch["site"], patch["mode"], patch["alpha"], patch["steps"])
-
     # ---- the prompt-attention readout: generate()'s prefill plus one launch per layer ----
-    IGNORE_SEGMENT = 255       # a segment id that is counted nowhere, whatever n_seg is
-
     def prompt_attention(self, prompts, speech: Optional[torch.Tensor], segments: Sequence[Sequence[int]],
                          want_probs: bool = False, n_seg: Optional[int] = None, cache_len_multiple: int = 64) -> PromptAttention:
         """Where the last prompt row (the query that decides the first generated token) looks: its attention mass in every
@@ -538,123 +458,20 @@ class CausalLMRuntimeMixin:
         ``ValueError`` before any launch: the FP8 KV cache (its prefill attends to unrounded k, the cache does not hold what the
         attention saw), a segment list of the wrong length, ids outside 0..255, more than 32 segments, a prompt over max_pos."""
         c, ws = self.lm_cfg, self.ws
-        if self.kv_dtype != "bf16":
-            raise ValueError(f"prompt_attention needs the bf16 KV cache (llm_kv_dtype={self.kv_dtype!r}: the FP8 prefill attends to "
-                             "unrounded k / v, so the cache does not hold the keys the attention saw)")
         plens = self._prompt_lengths(prompts)
-        if len(segments) != len(plens):
-            raise ValueError(f"{len(segments)} segment lists for {len(plens)} prompts")
-        rows = []
-        for b, (sg, n) in enumerate(zip(segments, plens)):
-            if len(sg) != n:
-                raise ValueError(f"segments[{b}] has {len(sg)} entries, the prompt of row {b} has {n} positions")
-            sg = torch.as_tensor(sg, dtype=torch.int64).reshape(-1)
-            if n and (int(sg.min()) < 0 or int(sg.max()) > 255):
-                raise ValueError(f"segments[{b}]: segment ids are 0..255 ({self.IGNORE_SEGMENT} = counted nowhere)")
-            rows.append(sg)
-        if n_seg is None:
-            n_seg = 1 + max(int(sg[sg < self.IGNORE_SEGMENT].max()) if bool((sg < self.IGNORE_SEGMENT).any()) else 0 for sg in rows)
-        if not 1 <= int(n_seg) <= MAX_READOUT_SEGMENTS:
-            raise ValueError(f"{n_seg} segments: the readout kernel sums at most {MAX_READOUT_SEGMENTS}")
-        n_seg = int(n_seg)
+        segs, n_seg = P.check_readout(segments, n_seg, self.kv_dtype, plens)
         limit = c.max_pos // cache_len_multiple * cache_len_multiple
         bad = [b for b, n in enumerate(plens) if n + 1 > limit]
         if bad:
             raise ValueError(f"prompt of row(s) {bad} ({[plens[b] for b in bad]} positions, + 1 for the cache) exceeds max_pos {c.max_pos}")
         h, lens = self.embed_prompts(prompts, speech)
-        Bn = len(lens)
         max_len = self._cache_len(lens, 1, cache_len_multiple)
-        cache = self._cache(Bn, max_len)
-        seg = torch.full((Bn, max_len), self.IGNORE_SEGMENT, dtype=torch.uint8)
-        for b, sg in enumerate(rows):
-            seg[b, :sg.numel()] = sg.to(torch.uint8)
-        seg_d = ws.get("pa_seg", (Bn, max_len), torch.uint8)
-        seg_d.copy_(seg, non_blocking=True)
-        mass = ws.get("pa_mass", (c.n_layers, Bn, c.n_heads, n_seg), F32)
-        probs = ws.get("pa_probs", (c.n_layers, Bn, c.n_heads, max_len), F32) if want_probs else None
-        if probs is not None:
-            probs.zero_()           # the kernel leaves a row's tail untouched
-        readout = AttnReadout(seg_d, _i32(lens, self.device), mass, probs)
-        logits = self._prefill_logits(h, lens, cache, ws.get("gen_last", (Bn, c.hidden), F32), readout=readout)
-        return PromptAttention(mass=mass.cpu().transpose(0, 1).contiguous(),
-                               probs=None if probs is None else probs.transpose(0, 1).clone(),
+        cache = self._cache(len(lens), max_len)
+        readout = P.readout_state(ws, c, segs, n_seg, lens, max_len, want_probs, self.device)
+        logits = self._prefill_logits(h, lens, cache, ws.get("gen_last", (len(lens), c.hidden), F32), probes=P.Probes(readout=readout))
+        return PromptAttention(mass=readout.mass.cpu().transpose(0, 1).contiguous(),
+                               probs=None if readout.probs is None else readout.probs.transpose(0, 1).clone(),
                                first_logits=logits.clone(), lens=list(lens))
-
-    def _check_knockout(self, knockout, plens: List[int], num_beams: int):
-        """Host validation of ``generate(knockout=...)``: everything is a ``ValueError`` raised before any launch.  Returns
-        ``(segments as int lists, blocked as sorted tuples, (l0, l1), heads tuple | None)``, or None when every set is empty."""
-        c = self.lm_cfg
-        if isinstance(knockout, dict):
-            unknown = set(knockout) - {"segments", "blocked", "layers", "heads"}
-            if unknown or "segments" not in knockout or "blocked" not in knockout:
-                raise ValueError("knockout as a dict holds 'segments' and 'blocked', and optionally 'layers' and 'heads'")
-            knockout = (knockout["segments"], knockout["blocked"], knockout.get("layers"), knockout.get("heads"))
-        try:
-            segments, blocked, layers, heads = (tuple(knockout) + (None, None))[:4] if 2 <= len(knockout) <= 4 else (None,) * 4
-        except TypeError:
-            segments = None
-        if segments is None:
-            raise ValueError("knockout must be (segments, blocked[, layers[, heads]]) or a dict with those keys")
-        if len(segments) != len(plens) or len(blocked) != len(plens):
-            raise ValueError(f"knockout: {len(segments)} segment lists and {len(blocked)} blocked sets for {len(plens)} prompts")
-        segs, sets = [], []
-        for b, (sg, n) in enumerate(zip(segments, plens)):
-            sg = [int(x) for x in (sg.tolist() if isinstance(sg, torch.Tensor) else sg)]
-            if len(sg) != n:
-                raise ValueError(f"knockout: segments[{b}] has {len(sg)} entries, the prompt of row {b} has {n} positions")
-            if sg and (min(sg) < 0 or max(sg) > 255):
-                raise ValueError(f"knockout: segments[{b}]: segment ids are 0..255 (ids >= {MAX_KNOCKOUT_SEGMENTS} are never blocked)")
-            bl = tuple(sorted({int(x) for x in blocked[b]}))
-            if bl and not (0 <= bl[0] and bl[-1] < MAX_KNOCKOUT_SEGMENTS):
-                raise ValueError(f"knockout: blocked[{b}] = {list(bl)}: only segment ids 0..{MAX_KNOCKOUT_SEGMENTS - 1} can be blocked")
-            segs.append(sg)
-            sets.append(bl)
-        if layers is None:
-            layers = (0, c.n_layers)
-        try:
-            l0, l1 = (int(x) for x in layers)
-        except (TypeError, ValueError):
-            raise ValueError(f"knockout: layers must be a half-open range (l0, l1), not {layers!r}") from None
-        if not 0 <= l0 < l1 <= c.n_layers:
-            raise ValueError(f"knockout: layer window ({l0}, {l1}) must be a non-empty range inside [0, {c.n_layers}]")
-        if heads is not None:
-            heads = tuple(sorted({int(x) for x in heads}))
-            if not heads or heads[0] < 0 or heads[-1] >= c.n_heads:
-                raise ValueError(f"knockout: head indices {list(heads)} must be a non-empty subset of 0..{c.n_heads - 1}")
-        for b, (sg, bl) in enumerate(zip(segs, sets)):
-            if bl and all(x in bl for x in sg):
-                raise ValueError(f"knockout: row {b}: the blocked segments {list(bl)} cover every position of its prompt")
-        if not any(sets):
-            return None
-        if self.kv_dtype != "bf16":
-            raise ValueError(f"knockout needs the bf16 KV cache (llm_kv_dtype={self.kv_dtype!r}: the FP8 prefill attends to unrounded "
-                             "k / v, so the cache does not hold the keys the attention saw)")
-        if num_beams != 1:
-            raise ValueError("knockout runs with greedy, sampled and label-constrained decoding, not with beams (num_beams > 1)")
-        return segs, sets, (l0, l1), heads
-
-    def _knockout_state(self, knockout, Bn: int, max_len: int) -> Knockout:
-        """The validated knockout on the device, in graph-visible workspace buffers refilled on every call: the segment table
-        padded with ``IGNORE_SEGMENT`` to the cache length, the listed rows (non-empty sets) and their per-head bit sets."""
-        segs, sets, layers, heads = knockout
-        c, ws = self.lm_cfg, self.ws
-        seg = torch.full((Bn, max_len), self.IGNORE_SEGMENT, dtype=torch.uint8)
-        for b, sg in enumerate(segs):
-            seg[b, :len(sg)] = torch.tensor(sg, dtype=torch.uint8)
-        listed = tuple(b for b, bl in enumerate(sets) if bl)
-        on = set(range(c.n_heads) if heads is None else heads)
-        bits = []
-        for b in listed:
-            m = sum(1 << g for g in sets[b])
-            m -= (1 << 32) if m >= (1 << 31) else 0           # the u32 bit set in an int32 tensor
-            bits.append([m if h in on else 0 for h in range(c.n_heads)])
-        seg_d = ws.get("gen_ko_seg", (Bn, max_len), torch.uint8)
-        blk_d = ws.get("gen_ko_blocked", (len(listed), c.n_heads), I32)
-        rows_d = ws.get("gen_ko_rows", (len(listed),), I32)
-        seg_d.copy_(seg, non_blocking=True)
-        blk_d.copy_(torch.tensor(bits, dtype=I32), non_blocking=True)
-        rows_d.copy_(torch.tensor(listed, dtype=I32), non_blocking=True)
-        return Knockout(seg_d, blk_d, rows_d, listed, layers)
 
     def _check_constraint(self, constraint, n_rows: int, max_new_tokens: int, eos_id, do_sample: bool, repetition_penalty: float,
                           num_beams: int, suppress_eos: bool):

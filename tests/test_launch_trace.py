@@ -9,6 +9,7 @@ The generation driver above them (runtime/salmonn.py: generate / _generate_beam)
 tests/golden/generate_launch_trace.json: launches, the torch plumbing between them, the phase marks and the result's shape.  Its
 HIP-graph protocol cannot run on ``meta`` tensors and is covered with fakes at the end of this file."""
 import contextlib
+import gc
 import os
 import sys
 
@@ -62,7 +63,7 @@ def gen_got():
 
 def test_generate_matrix_shape():
     cases = ["/".join(c) for c in lt.GEN_MATRIX]
-    assert len(cases) == len(set(cases)) == 21
+    assert len(cases) == len(set(cases)) == 71
     assert set(lt.load_fixture(lt.GEN_FIXTURE)) == set(cases)
 
 
@@ -78,6 +79,11 @@ def test_generate_trace_sees_the_modes(gen_got):
     names = ("greedy4", "chunk2", "sample_seeded", "repetition_penalty", "constrained", "beam3")
     assert len({gen_got[f"tiny_h4/bf16/{n}"] for n in names}) == len(names)
     assert gen_got["tiny_h4/bf16/chunk5"] == gen_got["tiny_h4/bf16/greedy4"]
+    # ... and so do the probes of the deciding rows: plain, readout, knockout, capture and patch, on every config that runs them
+    probes = ("greedy4", "prompt_attention", "knockout", "hidden", "patch_all_steps")
+    for cname in ("tiny_h4", "7b_gqa8_bias"):
+        assert len({gen_got[f"{cname}/bf16/{n}"] for n in probes}) == len(probes), cname
+    assert len({gen_got[f"7b_lora/bf16/{n}"] for n in probes[1:]}) == len(probes) - 1
 
 
 @pytest.fixture
@@ -102,10 +108,10 @@ def test_sampling_knobs_are_refused_before_any_launch(traced, kw):
 # ---- the HIP-graph protocol of generate(), with stand-ins for the graph API --------------------------------------------------------
 class FakeGraphs:
     """torch.cuda.CUDAGraph / torch.cuda.graph / torch.cuda.synchronize: ``graph`` runs its body once and notes what
-    binding.GEMM_PROFILE was inside; a graph object counts its replays."""
+    binding.GEMM_PROFILE was inside and whether the garbage collector was on; a graph object counts its replays."""
 
     def __init__(self, monkeypatch, B):
-        self.replays, self.profile_inside = 0, []
+        self.replays, self.profile_inside, self.gc_inside = 0, [], []
         outer = self
 
         class Graph:
@@ -116,6 +122,7 @@ class FakeGraphs:
         def graph(g):
             assert isinstance(g, Graph)
             outer.profile_inside.append(B.GEMM_PROFILE)
+            outer.gc_inside.append(gc.isenabled())
             yield
         monkeypatch.setattr(torch.cuda, "CUDAGraph", Graph)
         monkeypatch.setattr(torch.cuda, "graph", graph)
@@ -151,6 +158,7 @@ def test_graph_protocol_eager_capture_replay(monkeypatch):
 
         assert [run() for _ in range(2)] == [(2, 0), (2, 1)]                 # eager; capture + replay
         assert len(rt._graphs) == 1 and fake.profile_inside == [None] and B.GEMM_PROFILE is profile
+        assert fake.gc_inside == [False] and gc.isenabled()                  # no finaliser of a dead cycle runs inside a capture
         assert [run() for _ in range(2)] == [(0, 1), (0, 1)]                 # replay; replay
         (key,) = rt._graphs
         assert key[5] is None                                                # greedy
@@ -167,9 +175,53 @@ def test_graph_protocol_eager_capture_replay(monkeypatch):
             run(max_new_tokens=2)
         failing.clear()
         assert fake.profile_inside[-1] is None and B.GEMM_PROFILE is profile and len(rt._graphs) == 2
+        assert fake.gc_inside[-1] is False and gc.isenabled()
         # MAX_GRAPHS + 1 keys (the largest first, so that no buffer grows and retires them): the oldest goes
         rt._graph_reset()
         lengths = list(range(rt.MAX_GRAPHS + 2, 1, -1))
         for T in lengths:
             assert [run(max_new_tokens=T) for _ in range(2)] == [(T - 1, 0), (T - 1, 1)]
         assert [k[2] for k in rt._graphs] == [T - 1 for T in lengths[1:]]
+
+
+def test_graph_keys_of_the_probes(monkeypatch):
+    """What keys a decode graph with a probe: a knockout's shape (listed rows, layer window) and a ``steps="all"`` patch's uid,
+    appended to the key of the plain call — not the blocked sets or the vectors, which live in buffers refilled on every call."""
+    if not lt.device_ok():
+        pytest.skip(f"the trace is taken at {lt.N_CU} CUs (MI355X); this device has another count")
+    rec = lt.Recorder()
+    fake = FakeGraphs(monkeypatch, lt._modules()[0])
+    with lt.generate_recording(rec):
+        rt = lt.generate_runtime("tiny_h4", "bf16", rec)
+        rt.phase_marks, rt.use_graphs = None, True
+        rt._graph_reset()
+        c, segs = rt.lm_cfg, lt.segments_of(lt.GEN_LENS)
+
+        def run(**kw):
+            """(replays, graphs kept) after one call"""
+            r = fake.replays
+            rt.generate(lt.prompts_of(), None, max_new_tokens=3, **kw)
+            return fake.replays - r, len(rt._graphs)
+
+        def patch(site, steps="all", fill=0.0):
+            return dict(site=site, vectors=torch.full((5, c.hidden), fill), mode="add", alpha=0.5, steps=steps, rows=[0, 3])
+
+        assert [run() for _ in range(2)] == [(0, 0), (1, 1)]
+        (plain,) = rt._graphs
+        assert plain == (5, 64, 2, c.eos_id, c.pad_id, None, False, "bf16")        # without probes: today's key, element for element
+        blocked = [[1], [], [], [0, 2], []]
+        assert [run(knockout=(segs, blocked, (1, 2), [1, 3])) for _ in range(2)] == [(0, 1), (1, 2)]
+        # the same shape with other blocked sets and heads: the same uid over refilled buffers replays
+        assert run(knockout=(segs, [[2], [], [], [1], []], (1, 2), None)) == (1, 2)
+        assert list(rt._graphs)[1] == plain + (("knockout", 2, 1, 2),)
+        # another layer window, another number of listed rows: graphs of their own
+        assert [run(knockout=(segs, blocked, (0, 2), [1, 3])) for _ in range(2)] == [(0, 2), (1, 3)]
+        assert [run(knockout=(segs, [[1], [], [], [], []], (1, 2))) for _ in range(2)] == [(0, 3), (1, 4)]
+        # a patch of every step keys by its uid: other vectors replay, another site captures
+        assert [run(patch=patch(1)) for _ in range(2)] == [(0, 4), (1, 5)]
+        assert run(patch=patch(1, fill=1.0)) == (1, 5)
+        assert list(rt._graphs)[4] == plain + (("resid_patch", 2, 2, 1, "add", "all", 0.5),)
+        assert [run(patch=patch(0)) for _ in range(2)] == [(0, 5), (1, 6)]
+        # a prompt-only patch and a capture leave the decode steps the plain ones
+        assert run(patch=patch(1, steps="prompt")) == (1, 6) and run(want_hidden=True) == (1, 6)
+        assert [k[:8] for k in rt._graphs] == [plain] * 6

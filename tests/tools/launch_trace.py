@@ -8,7 +8,8 @@ engines.py with the same digests make the same calls with the same operands in t
 the same device time by construction.  tests/test_launch_trace.py compares against tests/golden/llama_launch_trace.json.
 
 A second matrix pins the generation driver one level up (runtime/salmonn.py: ``generate`` with every decode tail, chunked
-prefill, ``overlong="drop"`` and beam search): one sha256 per case in tests/golden/generate_launch_trace.json.  Besides the
+prefill, ``overlong="drop"`` and beam search, and the probes of the deciding rows — ``prompt_attention``, ``knockout``,
+``want_hidden`` and ``patch`` — chunked and not): one sha256 per case in tests/golden/generate_launch_trace.json.  Besides the
 launches, a generate trace holds the torch plumbing between them (every in-place op or ``clone`` on a device tensor, host
 tables by value), where the three ``phase_marks`` are recorded, and the shape of the result.
 
@@ -343,7 +344,17 @@ def _automaton():
     return LabelAutomaton([0, 2, 3, 4], [10, 12, 11, 2], [1, 2, 2, 2], {}, 260, 2)
 
 
-# name -> (attributes set on the runtime, prompt lengths, keyword arguments of generate(); a callable is built per run)
+def segments_of(lens):
+    """Four segments per prompt, in position order."""
+    return [[j * 4 // n for j in range(n)] for n in lens]
+
+
+def _overlong_third(cfg):
+    return (5, 9, cfg.max_pos + 119, 4, 6)
+
+
+# name -> (attributes set on the runtime, prompt lengths, keyword arguments of generate()); a callable is built per run from
+# (the decoder's cfg, the prompt lengths) — the lengths themselves from the cfg
 GEN_CASES = {
     "greedy4": ({}, GEN_LENS, dict(max_new_tokens=4)),
     "greedy1": ({}, GEN_LENS, dict(max_new_tokens=1)),
@@ -353,11 +364,11 @@ GEN_CASES = {
     "suppress_eos": ({}, GEN_LENS, dict(max_new_tokens=4, suppress_eos=True)),
     "first_and_step_logits": ({}, GEN_LENS, dict(max_new_tokens=4, want_first_logits=True, want_step_logits=True)),
     "sample_seeded": ({}, GEN_LENS, dict(max_new_tokens=4, do_sample=True, top_k=5, top_p=0.9, temperature=0.7,
-                                         generator=lambda: torch.Generator().manual_seed(1234))),
+                                         generator=lambda cfg, lens: torch.Generator().manual_seed(1234))),
     "sample_global": ({}, GEN_LENS, dict(max_new_tokens=4, do_sample=True, top_k=5, top_p=0.9, temperature=0.7)),
     "sample_top_k0": ({}, GEN_LENS, dict(max_new_tokens=4, do_sample=True, top_k=0, top_p=0.9, temperature=0.7)),
     "repetition_penalty": ({}, GEN_LENS, dict(max_new_tokens=4, repetition_penalty=1.2)),
-    "constrained": ({}, GEN_LENS, dict(max_new_tokens=4, constraint=lambda: (_automaton(), [0, -1, 1, 0, -1]))),
+    "constrained": ({}, GEN_LENS, dict(max_new_tokens=4, constraint=lambda cfg, lens: (_automaton(), [0, -1, 1, 0, -1]))),
     "drop_overlong": ({}, (5, 9, 2167, 4, 6), dict(max_new_tokens=4, overlong="drop", want_first_logits=True)),
     "speech_segment": ({}, GEN_LENS, dict(max_new_tokens=4)),
     "beam3": ({}, GEN_LENS[:2], dict(max_new_tokens=3, num_beams=3)),
@@ -366,6 +377,40 @@ GEN_CASES = {
 }
 GEN_MATRIX = ([("tiny_h4", "bf16", name) for name in GEN_CASES]
               + [(cname, kv, name) for cname, kv in (("tiny_h4", "fp8"), ("7b_gqa8_bias", "bf16")) for name in ("greedy4", "beam3")])
+
+# The probes of the deciding rows.  tiny_h4: head_dim 64, an untrimmed last layer; 7b_lora: the trimmed last layer with the
+# suffix-query attention; 7b_gqa8_bias: grouped-query, untrimmed.  Each case once unchunked and once with prefill_chunk=2: rows 0
+# and 3 of five then fall into the first two of three chunks, and the third chunk lists no row.
+_PROBES = {
+    "knockout": dict(knockout=lambda cfg, lens: (segments_of(lens), [[1], [], [], [0, 2], []], (1, 2), [1, 3])),
+    "hidden": dict(want_hidden=True),
+    "patch_all_steps": dict(patch=lambda cfg, lens: dict(site=1, vectors=torch.zeros(5, cfg.hidden), mode="add", alpha=0.5,
+                                                         steps="all", rows=[0, 3])),
+    "patch_last_site": dict(patch=lambda cfg, lens: dict(site=cfg.n_layers, vectors=torch.zeros(5, cfg.hidden), rows=[0, 3])),   # no capture
+    "hidden_patch_shared": dict(want_hidden=True,          # the shared vector, all rows: capture and patch in one launch
+                                patch=lambda cfg, lens: dict(site=cfg.n_layers, vectors=torch.zeros(1, cfg.hidden))),
+}
+PROBE_CASES = {}
+for _name, _kw in _PROBES.items():
+    PROBE_CASES[_name] = ({}, GEN_LENS, dict(max_new_tokens=4, **_kw))
+    PROBE_CASES[_name + "_chunk2"] = (dict(prefill_chunk=2), GEN_LENS, dict(max_new_tokens=4, **_kw))
+# overlong="drop" re-slices a probe to the kept rows: a knockout whose dropped row has a non-empty set, and a patch whose rows
+# list the dropped row and one kept row
+PROBE_CASES["drop_knockout"] = ({}, _overlong_third, dict(max_new_tokens=4, overlong="drop", knockout=lambda cfg, lens: (
+    segments_of(lens), [[1], [], [2], [0, 2], []], (1, 2), [1, 3])))
+PROBE_CASES["drop_hidden_patch"] = ({}, _overlong_third, dict(max_new_tokens=4, overlong="drop", want_hidden=True,
+                                                              patch=lambda cfg, lens: dict(site=1, vectors=torch.zeros(5, cfg.hidden),
+                                                                                           rows=[2, 3])))
+GEN_CASES.update(PROBE_CASES)
+# prompt_attention(): name -> (attributes set on the runtime, its keyword arguments besides the segments)
+PA_CASES = {
+    "prompt_attention": ({}, {}),
+    "prompt_attention_chunk2": (dict(prefill_chunk=2), {}),
+    "prompt_attention_probs": ({}, dict(want_probs=True)),
+    "prompt_attention_probs_chunk2": (dict(prefill_chunk=2), dict(want_probs=True)),
+}
+GEN_MATRIX += [(cname, "bf16", name) for cname in ("tiny_h4", "7b_lora", "7b_gqa8_bias") for name in (*PA_CASES, *PROBE_CASES)]
+GEN_MATRIX += [("tiny_h4", "fp8", name) for name in ("patch_all_steps", "hidden")]      # patching works on both KV dtypes
 
 
 def generate_runtime(cname: str, kv: str, rec: Recorder):
@@ -380,12 +425,37 @@ def generate_runtime(cname: str, kv: str, rec: Recorder):
     return rt
 
 
-def run_generate(cname: str, kv: str, name: str) -> str:
-    """The canonical text of one generate() call: launches, plumbing and marks in order, workspace requests, the result."""
-    attrs, lens, kw = GEN_CASES[name]
-    kw = {k: v() if callable(v) else v for k, v in kw.items()}
+def _result_line(res) -> str:
+    out = []
+    for f in fields(res):
+        v = getattr(res, f.name)
+        out.append(f"{f.name}=" + (f"{str(v.dtype).replace('torch.', '')}{list(v.shape)}@{v.device.type}" if isinstance(v, torch.Tensor)
+                                   else repr(v)))
+    return "result " + " ".join(out)
+
+
+def run_prompt_attention(cname: str, kv: str, name: str) -> str:
+    """The canonical text of one prompt_attention() call over GEN_LENS, four segments per prompt."""
+    attrs, kw = PA_CASES[name]
     rec = Recorder()
     rt = generate_runtime(cname, kv, rec)
+    for k, v in attrs.items():
+        setattr(rt, k, v)
+    with generate_recording(rec):
+        res = rt.prompt_attention(prompts_of(), None, segments_of(GEN_LENS), **kw)
+    rec.log.append(_result_line(res))
+    return rec.text()
+
+
+def run_generate(cname: str, kv: str, name: str) -> str:
+    """The canonical text of one generate() call: launches, plumbing and marks in order, workspace requests, the result."""
+    if name in PA_CASES:
+        return run_prompt_attention(cname, kv, name)
+    attrs, lens, kw = GEN_CASES[name]
+    rec = Recorder()
+    rt = generate_runtime(cname, kv, rec)
+    lens = lens(rt.lm_cfg) if callable(lens) else lens
+    kw = {k: v(rt.lm_cfg, lens) if callable(v) else v for k, v in kw.items()}
     for k, v in attrs.items():
         setattr(rt, k, v)
     prompts, speech = prompts_of(lens), None
@@ -393,12 +463,7 @@ def run_generate(cname: str, kv: str, name: str) -> str:
         prompts[0], speech = [[3, 4], ("speech", 1, 3)], _e(1, 8, rt.lm_cfg.hidden, dtype=torch.float32)
     with generate_recording(rec):
         res = rt.generate(prompts, speech, **kw)
-    out = []
-    for f in fields(res):
-        v = getattr(res, f.name)
-        out.append(f"{f.name}=" + (f"{str(v.dtype).replace('torch.', '')}{list(v.shape)}@{v.device.type}" if isinstance(v, torch.Tensor)
-                                   else repr(v)))
-    rec.log.append("result " + " ".join(out))
+    rec.log.append(_result_line(res))
     return rec.text()
 
 
