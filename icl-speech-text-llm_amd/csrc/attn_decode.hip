@@ -322,212 +322,181 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
   }
 }
 
-}  // namespace
+// ---- host ---------------------------------------------------------------------------------------------------------------------
+// One call's arguments: what every form has, in the order of the kernel's list, then the kernel's own tail struct for what only
+// some forms have (FORM_FUSE: cosT .. v_off, with kc / vc / ks / vs the caches again, writable; FORM_MASK: seg .. row_q; zero
+// otherwise, as the kernel is handed it).
+struct DecodeArgs {
+  const void* Q;                // the query rows, or with FORM_FUSE the projection's q | k | v rows
+  int64_t ldq;
+  const void *Kc, *Vc;          // bf16 caches, or the e4m3fn byte planes
+  const float *Ks, *Vs;         // FORM_F8: the scale planes; NULL otherwise
+  void* O;
+  int64_t ldo;
+  const int32_t* lens;
+  int32_t rows;                 // grid rows: n_seqs, or the list entries of FORM_MASK
+  int32_t H, Hkv, D, max_len;   // query heads, heads of the cache (= H unless FORM_GQA / FORM_MASK)
+  float scale;
+  void* stream;
+  DecodeMask tail = {};
+};
+// What an entry point's form has.  FORM_GQA: the entry point takes n_kv_heads (a masked call always does); FORM_EPL16: the bf16
+// reference of the fp8 lane mapping.
+enum : unsigned { FORM_F8 = 1, FORM_FUSE = 2, FORM_GQA = 4, FORM_MASK = 8, FORM_EPL16 = 16 };
 
-// n_heads = heads of the cache, each serving `group` query heads (1: multi-head attention).
-// epl: 8 = the production bf16 kernel; 16 = the fp8 kernel (Ks != NULL) or its bf16 reference instantiation
-static int launch_attn_decode(const void* Q, int64_t ldq, const void* Kc, const void* Vc, const float* Ks, const float* Vs, void* O,
-                              int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads, int group, int32_t head_dim,
-                              int32_t max_len, float scale, const DecodeRope* rope, int epl, void* stream, const char* who) {
-  dim3 grid(n_heads, n_seqs);
-  const bool few = (int64_t)n_seqs * n_heads <= 1024;      // at most four workgroups per CU: latency-bound, not bandwidth-bound
-  const DecodeRope rp = rope ? *rope : DecodeRope{};
-  const bool f8 = Ks != nullptr;
-#define ICL_DECODE_CASE(DD, UU, FF, F8_, EE, GG)                                                                               \
-  hipLaunchKernelGGL((attn_decode_kernel<DD, UU, FF, F8_, EE, GG>), grid, dim3(256), 0, (hipStream_t)stream,                   \
-                     (const unsigned short*)Q, ldq, Kc, Vc, Ks, Vs, (unsigned short*)O, ldo, lens, n_heads, max_len,          \
-                     scale * LOG2E, rp)
-  // few: 16 key rounds at 8 elements per lane, 8 at 16 (the same keys in flight per loop iteration); a full chip: 4
-#define ICL_DECODE_D(FF, F8_, EE)                                                                                              \
-  do {                                                                                                                         \
-    constexpr int UFEW = EE == 8 ? 16 : 8;                                                                                     \
-    if (head_dim == 64) { if (few) ICL_DECODE_CASE(64, UFEW, FF, F8_, EE, 1); else ICL_DECODE_CASE(64, 4, FF, F8_, EE, 1); }   \
-    else                { if (few) ICL_DECODE_CASE(128, UFEW, FF, F8_, EE, 1); else ICL_DECODE_CASE(128, 4, FF, F8_, EE, 1); } \
-  } while (0)
-  // key rounds in flight per group size: 8 (64 VGPRs of loads) next to two heads of state, 4 from three heads on
-#define ICL_GQA_CASE(GG, UU) case GG: ICL_DECODE_CASE(128, UU, false, false, 8, GG); break
-  if (group > 1) {       // the caller has checked: plain bf16, head_dim 128, group <= 8
-    switch (group) {
-      ICL_GQA_CASE(2, 8);
-      ICL_GQA_CASE(3, 4);
-      ICL_GQA_CASE(4, 4);
-      ICL_GQA_CASE(5, 4);
-      ICL_GQA_CASE(6, 4);
-      ICL_GQA_CASE(7, 4);
-      ICL_GQA_CASE(8, 4);
-    }
-  } else if (f8) {
-    if (rope) ICL_DECODE_D(true, true, 16); else ICL_DECODE_D(false, true, 16);
-  } else if (epl == 16) {
-    ICL_DECODE_D(false, false, 16);
-  } else {
-    if (rope) ICL_DECODE_D(true, false, 8); else ICL_DECODE_D(false, false, 8);
+// The checks of every form, each condition once.  Which form tests what (x), G = H / Hkv:
+//                                                          bf16 epl16 fp8 | rope_bf16 rope_fp8 | gqa      | masked
+//   rows 1..65535, n_heads > 0, max_len > 0                  x    x    x  |    x         x     |  x       |   x
+//   operands non-NULL (each form's own)                      x    x    x  |    x         x     |  x       |   x
+//   head_dim 64 or 128                                       x    x    x  |    x         x     |  x       |   x
+//   Hkv 1..65535 divides H, G <= 8, G > 1 only at 128        -    -    -  |    -         -     |  x       |   x
+//   q | k | v blocks: k_off, v_off % 8, disjoint inside ld   -    -    -  |    x         x     |  -       |   -
+//   ldq % 8, Q / Kc / Vc 16-B aligned                        x    x    x  |    x         x     |  x       |   x
+//     scale planes 4-B (fp8), cos / sin 16-B (rope), blocked 4-B (masked) aligned: with the line above
+//   ldq, ldo >= H * head_dim                                 -    -    -  |    -  (ldq: blocks) |  G > 1   |   x
+//   ldo % 8                                                  -    -    -  |    -         -     |  G > 1   |   -
+//   ld_seg >= max_len                                        -    -    -  |    -         -     |  -       |   x
+//   scale finite                                             -    -    -  |    -         -     |  -       |   x
+// The gaps are carried over from when each form had checks of its own: no plain or fused form tests the width of O (the fused ones test that of qkv through the blocks)
+// or a finite scale, none but the grouped one ldo % 8 (O is written two bytes at a time).  Closing them changes what is refused.
+int attn_decode_check(const char* who, unsigned form, const DecodeArgs& a) {
+  const bool f8 = form & FORM_F8, fuse = form & FORM_FUSE, gqa = form & FORM_GQA, mask = form & FORM_MASK;
+  const DecodeMask& t = a.tail;
+  const auto al = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
+  // the sizes first: an empty row list comes with NULL pointers, and is to be called an empty list
+  ICL_CHECK_ARG(a.rows > 0 && a.rows <= 65535 && a.H > 0 && a.max_len > 0, "%s: bad sizes: %s=%d (1..65535), n_heads=%d, max_len=%d", who,
+                mask ? "n_rows" : "n_seqs", a.rows, a.H, a.max_len);
+  ICL_CHECK_ARG(a.Q && a.Kc && a.Vc && a.O && a.lens && (!f8 || (a.Ks && a.Vs)) && (!fuse || (t.cosT && t.sinT && t.pos)) &&
+                    (!mask || (t.seg && t.blocked && t.row_seq && t.row_q)), "%s: NULL pointer", who);
+  ICL_CHECK_ARG(a.D == 64 || a.D == 128, "%s: head_dim=%d (only 64 and 128)", who, a.D);
+  if (gqa || mask) {
+    ICL_CHECK_ARG(a.Hkv > 0 && a.Hkv <= 65535 && a.H % a.Hkv == 0, "%s: n_heads=%d is not a multiple of n_kv_heads=%d", who, a.H, a.Hkv);
+    ICL_CHECK_ARG(a.H / a.Hkv <= 8, "%s: %d query heads per K/V head (G at most 8)", who, a.H / a.Hkv);
+    ICL_CHECK_ARG(a.H == a.Hkv || a.D == 128, "%s: head_dim=%d (grouped-query attention: only 128)", who, a.D);
   }
-#undef ICL_GQA_CASE
-#undef ICL_DECODE_D
-#undef ICL_DECODE_CASE
+  const int64_t cols = (int64_t)a.H * a.D;
+  const bool grouped = gqa && a.H > a.Hkv;      // through the grouped entry point, G = 1 is the multi-head form under its conditions
+  if (fuse)
+    ICL_CHECK_ARG(t.k_off % 8 == 0 && t.v_off % 8 == 0 && t.k_off >= cols && t.v_off >= t.k_off + cols && a.ldq >= t.v_off + cols,
+                  "%s: q | k | v column blocks must be 8-element aligned and disjoint inside a row", who);
+  ICL_CHECK_ARG(a.ldq % 8 == 0 && al(a.Q, 16) && al(a.Kc, 16) && al(a.Vc, 16) && (!f8 || (al(a.Ks, 4) && al(a.Vs, 4))) &&
+                    (!fuse || (al(t.cosT, 16) && al(t.sinT, 16))) && (!mask || al(t.blocked, 4)), "%s: misaligned operands", who);
+  if (mask || grouped)
+    ICL_CHECK_ARG(a.ldq >= cols && a.ldo >= cols, "%s: ldq=%lld / ldo=%lld must hold n_heads * head_dim = %lld columns", who,
+                  (long long)a.ldq, (long long)a.ldo, (long long)cols);
+  if (grouped) ICL_CHECK_ARG(a.ldo % 8 == 0, "%s: ldo=%lld must be a multiple of 8", who, (long long)a.ldo);
+  if (mask) {
+    ICL_CHECK_ARG(t.ld_seg >= a.max_len, "%s: ld_seg=%lld < max_len=%d", who, (long long)t.ld_seg, a.max_len);
+    ICL_CHECK_ARG(__builtin_isfinite(a.scale), "%s: scale is not finite", who);
+  }
+  return ICL_OK;
+}
+
+// One workgroup per (head of the cache, row).  The kernel's argument list, and for an unmasked form the DecodeRope part of the tail.
+template <int D, int UNR, bool FUSE, bool F8, int EPL, int NG, bool MASK>
+void attn_decode_launch(const DecodeArgs& a) {
+  const typename DecodeTail<MASK>::T tail = a.tail;
+  hipLaunchKernelGGL((attn_decode_kernel<D, UNR, FUSE, F8, EPL, NG, MASK>), dim3(a.Hkv, a.rows), dim3(256), 0, (hipStream_t)a.stream,
+                     (const unsigned short*)a.Q, a.ldq, a.Kc, a.Vc, a.Ks, a.Vs, (unsigned short*)a.O, a.ldo, a.lens, a.Hkv, a.max_len,
+                     a.scale * LOG2E, tail);
+}
+
+// Multi-head, UNR by the grid: few workgroups (at most four per CU: latency-bound, not bandwidth-bound) take 16 key rounds at 8
+// elements per lane and 8 at 16 (the same keys in flight per loop iteration), a full chip 4.  MASK: 8 whatever the grid.
+template <bool FUSE, bool F8, int EPL, bool MASK = false>
+void attn_decode_mha(const DecodeArgs& a) {
+  constexpr int UFEW = MASK || EPL == 16 ? 8 : 16, UMANY = MASK ? 8 : 4;
+  const bool few = (int64_t)a.rows * a.Hkv <= 1024;
+  if (a.D == 64) few ? attn_decode_launch<64, UFEW, FUSE, F8, EPL, 1, MASK>(a) : attn_decode_launch<64, UMANY, FUSE, F8, EPL, 1, MASK>(a);
+  else few ? attn_decode_launch<128, UFEW, FUSE, F8, EPL, 1, MASK>(a) : attn_decode_launch<128, UMANY, FUSE, F8, EPL, 1, MASK>(a);
+}
+
+// Grouped-query, G = 2 .. 8 (checked): key rounds in flight per group size, 8 (64 VGPRs of loads) next to two heads of state, 4
+// from three heads on.  Masked and unmasked share the table.
+template <bool MASK>
+void attn_decode_gqa(int G, const DecodeArgs& a) {
+  switch (G) {
+    case 2: return attn_decode_launch<128, 8, false, false, 8, 2, MASK>(a);
+    case 3: return attn_decode_launch<128, 4, false, false, 8, 3, MASK>(a);
+    case 4: return attn_decode_launch<128, 4, false, false, 8, 4, MASK>(a);
+    case 5: return attn_decode_launch<128, 4, false, false, 8, 5, MASK>(a);
+    case 6: return attn_decode_launch<128, 4, false, false, 8, 6, MASK>(a);
+    case 7: return attn_decode_launch<128, 4, false, false, 8, 7, MASK>(a);
+    case 8: return attn_decode_launch<128, 4, false, false, 8, 8, MASK>(a);
+  }
+}
+
+// The one way from an entry point to the kernel: check, pick the instantiation <D, UNR, FUSE, F8, EPL, NG, MASK>, launch.
+int attn_decode_run(const char* who, unsigned form, const DecodeArgs& a) {
+  if (const int rc = attn_decode_check(who, form, a)) return rc;
+  const int G = a.H / a.Hkv;
+  const bool fuse = form & FORM_FUSE;
+  if (form & FORM_MASK) G > 1 ? attn_decode_gqa<true>(G, a) : attn_decode_mha<false, false, 8, true>(a);
+  else if (G > 1) attn_decode_gqa<false>(G, a);
+  else if (form & FORM_F8) fuse ? attn_decode_mha<true, true, 16>(a) : attn_decode_mha<false, true, 16>(a);
+  else if (form & FORM_EPL16) attn_decode_mha<false, false, 16>(a);
+  else fuse ? attn_decode_mha<true, false, 8>(a) : attn_decode_mha<false, false, 8>(a);
   ICL_CHECK_LAUNCH(who);
   return ICL_OK;
 }
 
-#define ICL_DECODE_SIZE_CHECKS(who)                                                                                            \
-  ICL_CHECK_ARG(head_dim == 64 || head_dim == 128, who ": head_dim=%d (only 64 and 128)", head_dim);                           \
-  ICL_CHECK_ARG(n_seqs > 0 && n_seqs <= 65535 && n_heads > 0 && max_len > 0, who ": bad sizes")
-#define ICL_DECODE_CHECKS(who)                                                                                                 \
-  ICL_CHECK_ARG(Q && Kc && Vc && O && lens, who ": NULL pointer");                                                           \
-  ICL_DECODE_SIZE_CHECKS(who);                                                                                                 \
-  ICL_CHECK_ARG(ldq % 8 == 0 && ((uintptr_t)Q & 15) == 0 && ((uintptr_t)Kc & 15) == 0 && ((uintptr_t)Vc & 15) == 0,            \
-                who ": misaligned operands")
-#define ICL_DECODE_SCALE_CHECKS(who)                                                                                           \
-  ICL_CHECK_ARG(kscale && vscale, who ": NULL pointer");                                                                       \
-  ICL_CHECK_ARG(((uintptr_t)kscale & 3) == 0 && ((uintptr_t)vscale & 3) == 0, who ": misaligned operands")
-#define ICL_DECODE_ROPE_CHECKS(who)                                                                                            \
-  ICL_CHECK_ARG(qkv && cosT && sinT && pos && kc && vc && O && lens, who ": NULL pointer");                                    \
-  ICL_DECODE_SIZE_CHECKS(who);                                                                                                 \
-  ICL_CHECK_ARG(ld % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0 && k_off >= (int64_t)n_heads * head_dim &&                     \
-                    v_off >= k_off + (int64_t)n_heads * head_dim && ld >= v_off + (int64_t)n_heads * head_dim,                 \
-                who ": q | k | v column blocks must be 8-element aligned and disjoint inside a row");                           \
-  ICL_CHECK_ARG(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)kc & 15) == 0 && ((uintptr_t)vc & 15) == 0 &&                        \
-                    ((uintptr_t)cosT & 15) == 0 && ((uintptr_t)sinT & 15) == 0, who ": misaligned operands")
+}  // namespace
 
 extern "C" int icl_attn_decode_bf16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O,
                                     int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads,
                                     int32_t head_dim, int32_t max_len, float scale, void* stream) {
-  ICL_DECODE_CHECKS("icl_attn_decode_bf16");
-  return launch_attn_decode(Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, 1, head_dim, max_len, scale, nullptr, 8,
-                            stream, "icl_attn_decode_bf16");
+  return attn_decode_run("icl_attn_decode_bf16", 0,
+                         {Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, n_heads, head_dim, max_len, scale, stream});
 }
 
 extern "C" int icl_attn_decode_bf16_epl16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O,
                                           int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads,
                                           int32_t head_dim, int32_t max_len, float scale, void* stream) {
-  ICL_DECODE_CHECKS("icl_attn_decode_bf16_epl16");
-  return launch_attn_decode(Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, 1, head_dim, max_len, scale, nullptr, 16,
-                            stream, "icl_attn_decode_bf16_epl16");
+  return attn_decode_run("icl_attn_decode_bf16_epl16", FORM_EPL16,
+                         {Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, n_heads, head_dim, max_len, scale, stream});
 }
 
 extern "C" int icl_attn_decode_fp8(const void* Q, int64_t ldq, const void* Kc, const void* Vc, const float* kscale,
                                    const float* vscale, void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads,
                                    int32_t head_dim, int32_t max_len, float scale, void* stream) {
-  ICL_DECODE_CHECKS("icl_attn_decode_fp8");
-  ICL_DECODE_SCALE_CHECKS("icl_attn_decode_fp8");
-  return launch_attn_decode(Q, ldq, Kc, Vc, kscale, vscale, O, ldo, lens, n_seqs, n_heads, 1, head_dim, max_len, scale, nullptr, 16,
-                            stream, "icl_attn_decode_fp8");
+  return attn_decode_run("icl_attn_decode_fp8", FORM_F8,
+                         {Q, ldq, Kc, Vc, kscale, vscale, O, ldo, lens, n_seqs, n_heads, n_heads, head_dim, max_len, scale, stream});
 }
 
 extern "C" int icl_attn_decode_gqa_bf16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O, int64_t ldo,
                                         const int32_t* lens, int32_t n_seqs, int32_t n_heads, int32_t n_kv_heads,
                                         int32_t head_dim, int32_t max_len, float scale, void* stream) {
-  ICL_DECODE_CHECKS("icl_attn_decode_gqa_bf16");
-  ICL_CHECK_ARG(n_kv_heads > 0 && n_kv_heads <= 65535 && n_heads % n_kv_heads == 0,
-                "icl_attn_decode_gqa_bf16: n_heads=%d is not a multiple of n_kv_heads=%d", n_heads, n_kv_heads);
-  const int group = n_heads / n_kv_heads;
-  if (group > 1) {    // 1 is multi-head attention, under the multi-head entry points' conditions
-    ICL_CHECK_ARG(group <= 8, "icl_attn_decode_gqa_bf16: %d query heads per K/V head (at most 8)", group);
-    ICL_CHECK_ARG(head_dim == 128, "icl_attn_decode_gqa_bf16: head_dim=%d (grouped-query attention: only 128)", head_dim);
-    ICL_CHECK_ARG(ldo % 8 == 0 && ldq >= (int64_t)n_heads * head_dim && ldo >= (int64_t)n_heads * head_dim,
-                  "icl_attn_decode_gqa_bf16: ldq / ldo must hold n_heads * head_dim columns (ldo %% 8 == 0)");
-  }
-  return launch_attn_decode(Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_kv_heads, group, head_dim, max_len, scale,
-                            nullptr, 8, stream, "icl_attn_decode_gqa_bf16");
+  return attn_decode_run("icl_attn_decode_gqa_bf16", FORM_GQA,
+                         {Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, n_kv_heads, head_dim, max_len, scale, stream});
 }
 
-// The masked form (attention knockout): the bf16 kernel over a row list, every key under its head's segment mask.  n_heads = heads
-// of the cache.  One UNR per form, no few / many switch: a row's bits do not depend on the list (the resource notes in the header).
-static int launch_attn_decode_masked(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O, int64_t ldo,
-                                     const int32_t* lens, const DecodeMask& mk, int32_t n_rows, int32_t n_heads, int group,
-                                     int32_t head_dim, int32_t max_len, float scale, void* stream, const char* who) {
-  dim3 grid(n_heads, n_rows);
-#define ICL_MASKED_CASE(DD, UU, GG)                                                                                            \
-  hipLaunchKernelGGL((attn_decode_kernel<DD, UU, false, false, 8, GG, true>), grid, dim3(256), 0, (hipStream_t)stream,         \
-                     (const unsigned short*)Q, ldq, Kc, Vc, (const float*)nullptr, (const float*)nullptr, (unsigned short*)O,  \
-                     ldo, lens, n_heads, max_len, scale * LOG2E, mk)
-#define ICL_MASKED_GQA_CASE(GG, UU) case GG: ICL_MASKED_CASE(128, UU, GG); break
-  if (group > 1) {
-    switch (group) {
-      ICL_MASKED_GQA_CASE(2, 8);
-      ICL_MASKED_GQA_CASE(3, 4);
-      ICL_MASKED_GQA_CASE(4, 4);
-      ICL_MASKED_GQA_CASE(5, 4);
-      ICL_MASKED_GQA_CASE(6, 4);
-      ICL_MASKED_GQA_CASE(7, 4);
-      ICL_MASKED_GQA_CASE(8, 4);
-    }
-  } else if (head_dim == 64) {
-    ICL_MASKED_CASE(64, 8, 1);
-  } else {
-    ICL_MASKED_CASE(128, 8, 1);
-  }
-#undef ICL_MASKED_GQA_CASE
-#undef ICL_MASKED_CASE
-  ICL_CHECK_LAUNCH(who);
-  return ICL_OK;
-}
-
+// The masked form (attention knockout): the bf16 kernel over a row list, every key under its head's segment mask.
+// n_kv_heads = 0: n_heads.
 extern "C" int icl_attn_decode_masked_bf16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O, int64_t ldo,
                                            const int32_t* lens, const uint8_t* seg, int64_t ld_seg, const uint32_t* blocked,
                                            const int32_t* row_seq, const int32_t* row_q, int32_t n_rows, int32_t n_heads,
                                            int32_t n_kv_heads, int32_t head_dim, int32_t max_len, float scale, void* stream) {
-#define WHO "icl_attn_decode_masked_bf16"
-  ICL_CHECK_ARG(n_rows > 0 && n_rows <= 65535, WHO ": n_rows=%d (1..65535 list entries)", n_rows);
-  ICL_CHECK_ARG(Q && Kc && Vc && O && lens && seg && blocked && row_seq && row_q,
-                WHO ": NULL pointer (Q / Kc / Vc / O / lens / seg / blocked / row_seq / row_q)");
-  ICL_CHECK_ARG(head_dim == 64 || head_dim == 128, WHO ": head_dim=%d (only 64 and 128)", head_dim);
-  ICL_CHECK_ARG(n_heads > 0 && max_len > 0, WHO ": n_heads=%d, max_len=%d must be positive", n_heads, max_len);
-  if (n_kv_heads == 0) n_kv_heads = n_heads;
-  ICL_CHECK_ARG(n_kv_heads > 0 && n_kv_heads <= 65535 && n_heads % n_kv_heads == 0,
-                WHO ": n_heads=%d is not a multiple of n_kv_heads=%d", n_heads, n_kv_heads);
-  const int group = n_heads / n_kv_heads;
-  ICL_CHECK_ARG(group <= 8, WHO ": %d query heads per K/V head (G at most 8)", group);
-  ICL_CHECK_ARG(group == 1 || head_dim == 128, WHO ": head_dim=%d with G=%d (grouped-query attention: only 128)", head_dim, group);
-  ICL_CHECK_ARG(ld_seg >= max_len, WHO ": ld_seg=%lld < max_len=%d", (long long)ld_seg, max_len);
-  ICL_CHECK_ARG(ldq % 8 == 0 && ((uintptr_t)Q & 15) == 0 && ((uintptr_t)Kc & 15) == 0 && ((uintptr_t)Vc & 15) == 0,
-                WHO ": misaligned Q / Kc / Vc (16 bytes, ldq %% 8 == 0)");
-  ICL_CHECK_ARG(((uintptr_t)blocked & 3) == 0, WHO ": misaligned blocked");
-  ICL_CHECK_ARG(ldq >= (int64_t)n_heads * head_dim && ldo >= (int64_t)n_heads * head_dim,
-                WHO ": ldq=%lld / ldo=%lld must hold n_heads * head_dim = %lld columns", (long long)ldq, (long long)ldo,
-                (long long)n_heads * head_dim);
-  ICL_CHECK_ARG(__builtin_isfinite(scale), WHO ": scale is not finite");
-  DecodeMask mk = {};
-  mk.seg = seg;
-  mk.ld_seg = ld_seg;
-  mk.blocked = blocked;
-  mk.row_seq = row_seq;
-  mk.row_q = row_q;
-  return launch_attn_decode_masked(Q, ldq, Kc, Vc, O, ldo, lens, mk, n_rows, n_kv_heads, group, head_dim, max_len, scale, stream,
-                                   WHO);
-#undef WHO
+  DecodeArgs a = {Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_rows, n_heads, n_kv_heads ? n_kv_heads : n_heads, head_dim, max_len,
+                  scale, stream};
+  a.tail = {{}, seg, ld_seg, blocked, row_seq, row_q};
+  return attn_decode_run("icl_attn_decode_masked_bf16", FORM_MASK, a);
 }
 
-// the RoPE-fused forms: kscale / vscale NULL = the bf16 cache
-static int launch_attn_decode_rope(const void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* cosT, const float* sinT,
-                                   const int32_t* pos, const int32_t* seq_ids, void* kc, void* vc, float* kscale, float* vscale,
-                                   void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads, int32_t head_dim,
-                                   int32_t max_len, float scale, void* stream, const char* who) {
-  const DecodeRope rp = {cosT, sinT, pos, seq_ids, kc, vc, kscale, vscale, k_off, v_off};
-  return launch_attn_decode(qkv, ld, kc, vc, kscale, vscale, O, ldo, lens, n_seqs, n_heads, 1, head_dim, max_len, scale, &rp,
-                            kscale ? 16 : 8, stream, who);
-}
-
+// The RoPE-fused forms: the tail names the caches again, writable, for the appended row.
 extern "C" int icl_attn_decode_rope_bf16(const void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* cosT,
                                          const float* sinT, const int32_t* pos, const int32_t* seq_ids, void* kc, void* vc,
                                          void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads,
                                          int32_t head_dim, int32_t max_len, float scale, void* stream) {
-  ICL_DECODE_ROPE_CHECKS("icl_attn_decode_rope_bf16");
-  return launch_attn_decode_rope(qkv, ld, k_off, v_off, cosT, sinT, pos, seq_ids, kc, vc, nullptr, nullptr, O, ldo, lens, n_seqs,
-                                 n_heads, head_dim, max_len, scale, stream, "icl_attn_decode_rope_bf16");
+  DecodeArgs a = {qkv, ld, kc, vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, n_heads, head_dim, max_len, scale, stream};
+  a.tail = {{cosT, sinT, pos, seq_ids, kc, vc, nullptr, nullptr, k_off, v_off}};
+  return attn_decode_run("icl_attn_decode_rope_bf16", FORM_FUSE, a);
 }
 
 extern "C" int icl_attn_decode_rope_fp8(const void* qkv, int64_t ld, int64_t k_off, int64_t v_off, const float* cosT,
                                         const float* sinT, const int32_t* pos, const int32_t* seq_ids, void* kc, void* vc,
                                         float* kscale, float* vscale, void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs,
                                         int32_t n_heads, int32_t head_dim, int32_t max_len, float scale, void* stream) {
-  ICL_DECODE_ROPE_CHECKS("icl_attn_decode_rope_fp8");
-  ICL_DECODE_SCALE_CHECKS("icl_attn_decode_rope_fp8");
-  return launch_attn_decode_rope(qkv, ld, k_off, v_off, cosT, sinT, pos, seq_ids, kc, vc, kscale, vscale, O, ldo, lens, n_seqs,
-                                 n_heads, head_dim, max_len, scale, stream, "icl_attn_decode_rope_fp8");
+  DecodeArgs a = {qkv, ld, kc, vc, kscale, vscale, O, ldo, lens, n_seqs, n_heads, n_heads, head_dim, max_len, scale, stream};
+  a.tail = {{cosT, sinT, pos, seq_ids, kc, vc, kscale, vscale, k_off, v_off}};
+  return attn_decode_run("icl_attn_decode_rope_fp8", FORM_FUSE | FORM_F8, a);
 }
-#undef ICL_DECODE_ROPE_CHECKS
-#undef ICL_DECODE_SCALE_CHECKS
-#undef ICL_DECODE_CHECKS
-#undef ICL_DECODE_SIZE_CHECKS

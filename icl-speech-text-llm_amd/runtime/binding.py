@@ -53,6 +53,9 @@ class AttnArgs(Structure):
     ]
 
 
+# icl_attn_decode_bf16 and its 16-elements-per-lane reference: Q, ldq, Kc, Vc, O, ldo, lens, n_seqs, n_heads, head_dim, max_len, scale, stream
+_DECODE_PLAIN = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]
+
 # name -> (restype, argtypes); mirrors include/icl_hip.h one to one
 _SIGNATURES = {
     "icl_abi_version": (c_int, []),
@@ -63,8 +66,7 @@ _SIGNATURES = {
     "icl_gemm_select_tile": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "icl_attn_fwd_bf16": (c_int, [POINTER(AttnArgs), c_void_p]),
     "icl_attn_fwd_suffix_bf16": (c_int, [POINTER(AttnArgs), c_void_p, c_void_p]),
-    "icl_attn_decode_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
-                                     c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "icl_attn_decode_bf16": (c_int, _DECODE_PLAIN),
     "icl_attn_decode_gqa_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                          c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
     "icl_attn_segmass_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
@@ -113,8 +115,7 @@ _SIGNATURES = {
                                   c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "icl_rope_kv_fp8": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
-    "icl_attn_decode_bf16_epl16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
-                                           c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "icl_attn_decode_bf16_epl16": (c_int, _DECODE_PLAIN),
     "icl_attn_decode_fp8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                     c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
     "icl_attn_decode_rope_fp8": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -391,26 +392,37 @@ def attn_fwd(q, k, v, out, cu_seqlens, max_seqlen: int, n_heads: int, head_dim: 
     return out
 
 
-def attn_decode(q, kcache, vcache, out, lens, n_heads: int, head_dim: int, max_len: int, scale: float):
-    _require_gpu(q, kcache, vcache, out, lens)
+def _fp8_cache(kq, vq, ks, vs):
+    assert kq.dtype == torch.uint8 and vq.dtype == torch.uint8 and ks.dtype == torch.float32 and vs.dtype == torch.float32
+
+
+def _attn_decode(entry: str, q, out, lens, cache, *args):
+    """What every decode-attention form needs.  ``args`` is the entry point's argument list up to the stream, tensors as tensors
+    (None: a NULL pointer) — the kernel gets no pointer that has not been through the residency check here.  What the kernel
+    assumes of every form: ``q`` (or the qkv rows) and ``out`` are bf16 rows with unit inner stride, ``lens`` is int32, ``cache``
+    is (K, V) in bf16 or (K, V, K scales, V scales) in uint8 / f32 — a wrong dtype would be a garbage read on the GPU."""
+    _require_gpu(*(a for a in args if isinstance(a, torch.Tensor)))
+    assert q.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and q.stride(-1) == 1 and out.stride(-1) == 1
     assert lens.dtype == torch.int32
-    _check(load_library().icl_attn_decode_bf16(q.data_ptr(), q.stride(0), kcache.data_ptr(), vcache.data_ptr(),
-                                               out.data_ptr(), out.stride(0), lens.data_ptr(), q.shape[0],
-                                               n_heads, head_dim, max_len, scale, _stream()),
-           "icl_attn_decode_bf16")
+    if len(cache) == 4:
+        _fp8_cache(*cache)
+    else:
+        assert cache[0].dtype == torch.bfloat16 and cache[1].dtype == torch.bfloat16
+    _check(getattr(load_library(), entry)(*(_ptr(a) if a is None or isinstance(a, torch.Tensor) else a for a in args), _stream()),
+           entry)
     return out
+
+
+def attn_decode(q, kcache, vcache, out, lens, n_heads: int, head_dim: int, max_len: int, scale: float):
+    return _attn_decode("icl_attn_decode_bf16", q, out, lens, (kcache, vcache),
+                        q, q.stride(0), kcache, vcache, out, out.stride(0), lens, q.shape[0], n_heads, head_dim, max_len, scale)
 
 
 def attn_decode_gqa(q, kcache, vcache, out, lens, n_heads: int, n_kv_heads: int, head_dim: int, max_len: int, scale: float):
     """``attn_decode`` for grouped-query attention (icl_attn_decode_gqa_bf16): q / out hold ``n_heads`` heads per row, the caches
     [n_seqs, n_kv_heads, max_len, head_dim]; every cache row is read once for the query heads that share it."""
-    _require_gpu(q, kcache, vcache, out, lens)
-    assert lens.dtype == torch.int32
-    _check(load_library().icl_attn_decode_gqa_bf16(q.data_ptr(), q.stride(0), kcache.data_ptr(), vcache.data_ptr(),
-                                                   out.data_ptr(), out.stride(0), lens.data_ptr(), q.shape[0],
-                                                   n_heads, n_kv_heads, head_dim, max_len, scale, _stream()),
-           "icl_attn_decode_gqa_bf16")
-    return out
+    return _attn_decode("icl_attn_decode_gqa_bf16", q, out, lens, (kcache, vcache),
+                        q, q.stride(0), kcache, vcache, out, out.stride(0), lens, q.shape[0], n_heads, n_kv_heads, head_dim, max_len, scale)
 
 
 def attn_segmass(q, kcache, lens, seg, mass, n_heads: int, head_dim: int, max_len: int, scale: float, *, n_kv_heads: int = 0,
@@ -442,72 +454,46 @@ def attn_decode_masked(q, kcache, vcache, out, lens, seg, blocked, row_seq, row_
     (int32) of ``q`` (bf16, already rotated) and writes that row of ``out``; other rows of ``out`` are not written.  seg: uint8
     [n_seqs, >= max_len], the segment of every key; blocked: int32 (read as u32 bit sets) [n_listed, n_heads], bit g = that query
     head does not read segment g (ids >= 32 are never blocked); lens: int32 [n_seqs], the keys of every cache sequence."""
-    _require_gpu(q, kcache, vcache, out, lens, seg, blocked, row_seq, row_q)
-    assert q.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and kcache.dtype == torch.bfloat16 and vcache.dtype == torch.bfloat16
-    assert lens.dtype == torch.int32 and seg.dtype == torch.uint8 and blocked.dtype == torch.int32
-    assert row_seq.dtype == torch.int32 and row_q.dtype == torch.int32
+    assert seg.dtype == torch.uint8 and blocked.dtype == torch.int32 and row_seq.dtype == torch.int32 and row_q.dtype == torch.int32
     n_seqs, n_rows = lens.numel(), row_seq.numel()
     assert row_q.numel() == n_rows and row_seq.is_contiguous() and row_q.is_contiguous()
     assert seg.dim() == 2 and seg.shape[0] == n_seqs and seg.stride(1) == 1
     assert blocked.is_contiguous() and blocked.dim() == 2 and tuple(blocked.shape) == (n_rows, n_heads)
-    assert kcache.shape[0] == n_seqs and vcache.shape[0] == n_seqs and q.stride(1) == 1 and out.stride(1) == 1
-    _check(load_library().icl_attn_decode_masked_bf16(q.data_ptr(), q.stride(0), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(),
-                                                      out.stride(0), lens.data_ptr(), seg.data_ptr(), seg.stride(0),
-                                                      blocked.data_ptr(), row_seq.data_ptr(), row_q.data_ptr(), n_rows, n_heads,
-                                                      n_kv_heads, head_dim, max_len, scale, _stream()),
-           "icl_attn_decode_masked_bf16")
-    return out
+    assert kcache.shape[0] == n_seqs and vcache.shape[0] == n_seqs
+    return _attn_decode("icl_attn_decode_masked_bf16", q, out, lens, (kcache, vcache),
+                        q, q.stride(0), kcache, vcache, out, out.stride(0), lens, seg, seg.stride(0), blocked, row_seq, row_q, n_rows,
+                        n_heads, n_kv_heads, head_dim, max_len, scale)
 
 
 def attn_decode_rope(qkv, k_off: int, v_off: int, cos, sin, pos, seq_ids, kcache, vcache, out, lens, n_heads: int,
                      head_dim: int, max_len: int, scale: float):
     """One decode step's RoPE + cache append + attention in one launch (icl_attn_decode_rope_bf16): bit-identical to
     ``rope_kv`` followed by ``attn_decode``; ``qkv`` is left as the projection wrote it."""
-    _require_gpu(qkv, cos, sin, pos, seq_ids, kcache, vcache, out, lens)
-    assert lens.dtype == torch.int32 and pos.dtype == torch.int32 and qkv.dtype == torch.bfloat16
-    _check(load_library().icl_attn_decode_rope_bf16(qkv.data_ptr(), qkv.stride(0), k_off, v_off, cos.data_ptr(), sin.data_ptr(),
-                                                    pos.data_ptr(), _ptr(seq_ids), kcache.data_ptr(), vcache.data_ptr(),
-                                                    out.data_ptr(), out.stride(0), lens.data_ptr(), qkv.shape[0], n_heads,
-                                                    head_dim, max_len, scale, _stream()), "icl_attn_decode_rope_bf16")
-    return out
-
-
-def _fp8_cache(kq, vq, ks, vs):
-    assert kq.dtype == torch.uint8 and vq.dtype == torch.uint8 and ks.dtype == torch.float32 and vs.dtype == torch.float32
+    assert pos.dtype == torch.int32
+    return _attn_decode("icl_attn_decode_rope_bf16", qkv, out, lens, (kcache, vcache),
+                        qkv, qkv.stride(0), k_off, v_off, cos, sin, pos, seq_ids, kcache, vcache, out, out.stride(0), lens, qkv.shape[0],
+                        n_heads, head_dim, max_len, scale)
 
 
 def attn_decode_bf16_epl16(q, kcache, vcache, out, lens, n_heads: int, head_dim: int, max_len: int, scale: float):
     """``attn_decode`` with the fp8 kernel's lane mapping (16 elements per lane): the bf16 reference of ``attn_decode_fp8``."""
-    _require_gpu(q, kcache, vcache, out, lens)
-    assert lens.dtype == torch.int32
-    _check(load_library().icl_attn_decode_bf16_epl16(q.data_ptr(), q.stride(0), kcache.data_ptr(), vcache.data_ptr(),
-                                                     out.data_ptr(), out.stride(0), lens.data_ptr(), q.shape[0], n_heads, head_dim,
-                                                     max_len, scale, _stream()), "icl_attn_decode_bf16_epl16")
-    return out
+    return _attn_decode("icl_attn_decode_bf16_epl16", q, out, lens, (kcache, vcache),
+                        q, q.stride(0), kcache, vcache, out, out.stride(0), lens, q.shape[0], n_heads, head_dim, max_len, scale)
 
 
 def attn_decode_fp8(q, kq, vq, ks, vs, out, lens, n_heads: int, head_dim: int, max_len: int, scale: float):
     """``attn_decode`` over an FP8 KV cache (uint8 rows kq / vq, f32 row scales ks / vs): icl_attn_decode_fp8."""
-    _require_gpu(q, kq, vq, ks, vs, out, lens)
-    _fp8_cache(kq, vq, ks, vs)
-    assert lens.dtype == torch.int32
-    _check(load_library().icl_attn_decode_fp8(q.data_ptr(), q.stride(0), kq.data_ptr(), vq.data_ptr(), ks.data_ptr(), vs.data_ptr(),
-                                              out.data_ptr(), out.stride(0), lens.data_ptr(), q.shape[0], n_heads, head_dim,
-                                              max_len, scale, _stream()), "icl_attn_decode_fp8")
-    return out
+    return _attn_decode("icl_attn_decode_fp8", q, out, lens, (kq, vq, ks, vs),
+                        q, q.stride(0), kq, vq, ks, vs, out, out.stride(0), lens, q.shape[0], n_heads, head_dim, max_len, scale)
 
 
 def attn_decode_rope_fp8(qkv, k_off: int, v_off: int, cos, sin, pos, seq_ids, kq, vq, ks, vs, out, lens, n_heads: int,
                          head_dim: int, max_len: int, scale: float):
     """``attn_decode_rope`` over an FP8 KV cache (icl_attn_decode_rope_fp8): the appended row is rounded and served rounded."""
-    _require_gpu(qkv, cos, sin, pos, seq_ids, kq, vq, ks, vs, out, lens)
-    _fp8_cache(kq, vq, ks, vs)
-    assert lens.dtype == torch.int32 and pos.dtype == torch.int32 and qkv.dtype == torch.bfloat16
-    _check(load_library().icl_attn_decode_rope_fp8(qkv.data_ptr(), qkv.stride(0), k_off, v_off, cos.data_ptr(), sin.data_ptr(),
-                                                   pos.data_ptr(), _ptr(seq_ids), kq.data_ptr(), vq.data_ptr(), ks.data_ptr(),
-                                                   vs.data_ptr(), out.data_ptr(), out.stride(0), lens.data_ptr(), qkv.shape[0],
-                                                   n_heads, head_dim, max_len, scale, _stream()), "icl_attn_decode_rope_fp8")
-    return out
+    assert pos.dtype == torch.int32
+    return _attn_decode("icl_attn_decode_rope_fp8", qkv, out, lens, (kq, vq, ks, vs),
+                        qkv, qkv.stride(0), k_off, v_off, cos, sin, pos, seq_ids, kq, vq, ks, vs, out, out.stride(0), lens,
+                        qkv.shape[0], n_heads, head_dim, max_len, scale)
 
 
 def rope_kv_fp8(qkv, k_off: int, v_off: int, cos, sin, pos, seq_ids, kq, vq, ks, vs, n_heads: int, head_dim: int,

@@ -45,6 +45,101 @@ def test_ops_fail_loudly_without_gpu_operands():
             SalmonnRuntime(SalmonnCfg.tiny(), {}, device="cpu")
 
 
+# The decode-attention entry points' argument lists (include/icl_hip.h), under the names of the host layer in csrc/attn_decode.hip:
+# the fused forms' qkv / ld / kc / vc are Q / ldq / Kc / Vc here, n_seqs and the masked form's n_rows are rows.
+_DECODE_TAIL = "O ldo lens rows n_heads head_dim max_len scale stream"
+_DECODE_ENTRIES = {
+    "icl_attn_decode_bf16": "Q ldq Kc Vc " + _DECODE_TAIL,
+    "icl_attn_decode_bf16_epl16": "Q ldq Kc Vc " + _DECODE_TAIL,
+    "icl_attn_decode_fp8": "Q ldq Kc Vc kscale vscale " + _DECODE_TAIL,
+    "icl_attn_decode_gqa_bf16": "Q ldq Kc Vc O ldo lens rows n_heads n_kv_heads head_dim max_len scale stream",
+    "icl_attn_decode_masked_bf16": "Q ldq Kc Vc O ldo lens seg ld_seg blocked row_seq row_q rows n_heads n_kv_heads head_dim max_len scale stream",
+    "icl_attn_decode_rope_bf16": "Q ldq k_off v_off cosT sinT pos seq_ids Kc Vc " + _DECODE_TAIL,
+    "icl_attn_decode_rope_fp8": "Q ldq k_off v_off cosT sinT pos seq_ids Kc Vc kscale vscale " + _DECODE_TAIL,
+}
+
+
+def decode_refusal_cases():
+    """[(entry point, what is broken, the argument list, words of the message)]: for each of the seven entry points one valid call
+    — 4 rows, 32 query heads (over 8 K/V heads where the form takes them), head_dim 128, 64 cache rows; every pointer a made-up
+    address, 1 MiB aligned — with ONE argument broken, one case per condition the form tests (and per pointer it refuses as NULL)."""
+    H, D = 32, 128
+    sizes = dict(ldq=H * D, ldo=H * D, rows=4, n_heads=H, n_kv_heads=8, head_dim=D, max_len=64, ld_seg=64, scale=D ** -0.5,
+                 stream=None, k_off=H * D + 16, v_off=2 * H * D + 32)
+    cases = []
+    for entry, names in _DECODE_ENTRIES.items():
+        names = names.split()
+        base = {n: sizes[n] if n in sizes else (i + 1) << 20 for i, n in enumerate(names)}
+        fused, fp8, masked, kv = "k_off" in base, "kscale" in base, "seg" in base, "n_kv_heads" in base
+        if fused:
+            base["ldq"] = 3 * H * D + 48          # q | k | v blocks with 16 spare columns after each
+
+        def case(what, words, **broken):
+            assert set(broken) <= set(base), (entry, what)
+            cases.append((entry, what, [{**base, **broken}[n] for n in names], words))
+
+        for n in names:                           # every pointer but the two that may be NULL
+            if n not in sizes and n != "seq_ids":
+                case(n + " NULL", "NULL pointer", **{n: None})
+        case("head_dim 96", "head_dim=96 (only 64 and 128)", head_dim=96)
+        rows = "n_rows" if masked else "n_seqs"
+        case("no rows", f"bad sizes: {rows}=0", rows=0)
+        case("65536 rows", f"bad sizes: {rows}=65536", rows=65536)
+        case("n_heads 0", "bad sizes", n_heads=0)
+        case("max_len 0", "bad sizes", max_len=0)
+        case("ldq % 8", "misaligned operands", ldq=base["ldq"] + 4)
+        for n in ("Q", "Kc", "Vc"):
+            case(n + " + 8 bytes", "misaligned operands", **{n: base[n] + 8})
+        if fp8:
+            for n in ("kscale", "vscale"):
+                case(n + " + 2 bytes", "misaligned operands", **{n: base[n] + 2})
+        if fused:
+            for n in ("cosT", "sinT"):
+                case(n + " + 8 bytes", "misaligned operands", **{n: base[n] + 8})
+            blocks = "q | k | v column blocks must be 8-element aligned and disjoint"
+            case("k_off % 8", blocks, k_off=base["k_off"] + 4)
+            case("v_off % 8", blocks, v_off=base["v_off"] + 4)
+            case("k inside q", blocks, k_off=H * D - 8)
+            case("v inside k", blocks, v_off=base["k_off"] + H * D - 8)
+            case("v past the row", blocks, ldq=base["v_off"] + H * D - 8)
+        if kv:
+            multiple = "is not a multiple of n_kv_heads="
+            case("n_kv_heads -1", multiple, n_kv_heads=-1)
+            case("n_kv_heads 65536", multiple, n_heads=65536, n_kv_heads=65536, **({"ldq": 65536 * D, "ldo": 65536 * D} if masked else {}))
+            case("32 % 5", multiple, n_kv_heads=5)
+            case("G = 16", "16 query heads per K/V head (G at most 8)", n_kv_heads=2)
+            case("G = 4 at head_dim 64", "head_dim=64 (grouped-query attention: only 128)", head_dim=64)
+            case("ldq < n_heads * head_dim", "ldq=4088 / ldo=4096 must hold n_heads * head_dim = 4096 columns", ldq=H * D - 8)
+            case("ldo < n_heads * head_dim", "ldq=4096 / ldo=4088 must hold n_heads * head_dim = 4096 columns", ldo=H * D - 8)
+        if kv and not masked:
+            case("n_kv_heads 0", multiple, n_kv_heads=0)        # (the masked form reads 0 as n_heads)
+            case("ldo % 8", "ldo=4100 must be a multiple of 8", ldo=H * D + 4)
+        if masked:
+            case("ldq < n_heads * head_dim, G = 1", "ldq=4088 / ldo=4096 must hold", ldq=H * D - 8, n_kv_heads=0)
+            case("ldo < n_heads * head_dim, G = 1", "ldq=4096 / ldo=4088 must hold", ldo=H * D - 8, n_kv_heads=0)
+            case("ld_seg < max_len", "ld_seg=63 < max_len=64", ld_seg=63)
+            case("blocked + 2 bytes", "misaligned operands", blocked=base["blocked"] + 2)
+            case("scale inf", "scale is not finite", scale=float("inf"))
+            case("scale nan", "scale is not finite", scale=float("nan"))
+    return cases
+
+
+def test_decode_attention_entry_points_refuse_bad_arguments():
+    """Every condition of attn_decode_check (csrc/attn_decode.hip), form by form, through ctypes: ICL_EINVAL and a message that
+    starts with the entry point called and names the condition.  The pointers are made up, so every call has to return before
+    a launch — which is why this never runs where a GPU could take one."""
+    if torch.cuda.is_available():
+        pytest.skip("made-up pointers: a check that wrongly passed would launch on them")
+    import icl_speech_text_llm_amd.runtime.binding as b
+    lib = b.load_library()
+    cases = decode_refusal_cases()
+    assert {e for e, *_ in cases} == {s for s in b.EXPORTED_SYMBOLS if s.startswith("icl_attn_decode_")}
+    for entry, what, args, words in cases:
+        rc = getattr(lib, entry)(*args)
+        msg = (lib.icl_last_error() or b"").decode()
+        assert rc == -1 and msg.startswith(entry + ": ") and words in msg, (entry, what, rc, msg)
+
+
 def test_model_factory_contract():
     from icl_speech_text_llm_amd.models.model_factory import ModelFactory
     with pytest.raises(RuntimeError, match="Failed to create model: Unknown model type"):

@@ -1,6 +1,8 @@
-"""Time the six decode-attention entry points for two or more builds (name=path ...), interleaved, on seeded inputs, and compare
-what they write bit for bit: the output, and for the RoPE-fused forms the caches and scale planes (each build appends to a copy of
-its own).  Loading one build under two names shows the spread that a difference between builds has to exceed.
+"""Time the seven decode-attention entry points — every entry point of csrc/attn_decode.hip — for two or more builds
+(name=path ...), interleaved, on seeded inputs, and compare what they write bit for bit: the output, and for the RoPE-fused forms
+the caches and scale planes (each build appends to a copy of its own).  The masked form runs under a mask that blocks some
+segments for every head and all of them for none.  Loading one build under two names shows the spread that a difference between
+builds has to exceed.
 usage: python tools/attn_decode_ab.py base=lib/libicl_hip_base.so base2=lib/libicl_hip_base2.so new=lib/libicl_hip.so"""
 import ctypes, functools, math, os, statistics, sys
 import torch
@@ -47,11 +49,28 @@ def fused(n, H, Hkv, D, fp8=False):
     return build
 
 
+def masked(n, H, Hkv, D):
+    """n list entries over n cache sequences, in reverse order; 64-key segments, every (entry, head) blocks a random set of the
+    segments 1 .. 6 and never segment 0, so no head is left without a key."""
+    q, (kv, _) = bf16(n, H * D), cache(n, Hkv, D, False)
+    lens = torch.full((n,), LIVE, dtype=torch.int32, device=dev)
+    seg = (torch.arange(L, device=dev) // 64).to(torch.uint8).repeat(n, 1)
+    blocked = (torch.randint(0, 64, (n, H), device=dev) << 1).to(torch.int32)
+    rows = torch.arange(n - 1, -1, -1, dtype=torch.int32, device=dev)
+
+    def build(stream):
+        o = torch.zeros(n, H * D, dtype=torch.bfloat16, device=dev)
+        return [q, H * D, *kv, o, H * D, lens, seg, L, blocked, rows, rows, n, H, Hkv, D, L, D ** -0.5, stream], [o]
+    return build
+
+
 ENTRIES = [("icl_attn_decode_bf16", plain), ("icl_attn_decode_bf16_epl16", plain), ("icl_attn_decode_fp8", functools.partial(plain, fp8=True)),
            ("icl_attn_decode_rope_bf16", fused), ("icl_attn_decode_rope_fp8", functools.partial(fused, fp8=True))]
 MHA = [(n, 32, 32, 128) for n in (1, 16, 256)] + [(n, 16, 16, 64) for n in (1, 256)]           # n_seqs, heads, K/V heads, head_dim
 GQA = [(n, H, Hkv, 128) for H, Hkv in ((32, 16), (32, 8), (28, 4), (32, 4)) for n in (1, 256)]
-CASES = [(e, b, s) for e, b in ENTRIES for s in MHA] + [("icl_attn_decode_gqa_bf16", functools.partial(plain, gqa=True), s) for s in GQA]
+MASKED = [(n, 32, Hkv, 128) for Hkv in (32, 8) for n in (1, 256)]                              # n = list entries
+CASES = ([(e, b, s) for e, b in ENTRIES for s in MHA] + [("icl_attn_decode_gqa_bf16", functools.partial(plain, gqa=True), s) for s in GQA] +
+         [("icl_attn_decode_masked_bf16", masked, s) for s in MASKED])
 
 libs = [(name, ctypes.CDLL(os.path.abspath(path))) for name, path in (spec.split("=", 1) for spec in sys.argv[1:])]
 bits = lambda t: t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()])
