@@ -721,6 +721,27 @@ class CustomSALMONN(BaseModel):
         res = self._generate_resid(samples, patch=dict(site=site, vectors=vectors, mode=mode, alpha=alpha, steps=steps, rows=rows))
         return {"texts": self.decode_ids(res.tokens), "tokens": res.tokens, "first_logits": res.first_logits}
 
+    def head_outputs(self, samples: Dict[str, Any]) -> Dict[str, Any]:
+        """The outputs of single attention heads at the last prompt position, as each layer's o_proj reads them: ``{"head_out":
+        bf16 [B, n_layers, n_heads, head_dim] (device; a dropped row is NaN), "first_logits": f32 [B, V] (device), "tokens":
+        int64 [B, width] (CPU), "texts"}``.  The generation is ``generate_ids``'s, bit for bit;
+        ``runtime.head_contrib(head_out, [(layer, head), ...])`` gives what those heads add to the residual stream — the mean of
+        it over few-shot prompts and a few heads is a function vector, added with ``generate_patched(..., mode="add")``."""
+        res = self._generate_resid(samples, want_heads=True)
+        return {"head_out": res.head_out, "first_logits": res.first_logits, "tokens": res.tokens, "texts": self.decode_ids(res.tokens)}
+
+    def generate_head_patched(self, samples: Dict[str, Any], heads, vectors, mode: str = "replace", alpha: float = 1.0,
+                              steps: str = "prompt", rows=None) -> Dict[str, Any]:
+        """Head ablation and head-level activation patching: generate with the outputs of the ``heads`` ([(layer, head), ...]) at
+        the last prompt position (``steps="all"``: and at every generated one) replaced by ``vectors`` (zeros or a mean: an
+        ablation; ``head_outputs(...)["head_out"][:, l, h]`` of another batch: a patch) or moved by ``alpha * vectors``.
+        ``vectors``: f32 [B, n_pairs, head_dim] in the order of ``heads``, or [n_pairs, head_dim] / [1, n_pairs, head_dim] for all
+        rows; ``rows``: None (all) or the rows of the batch to patch.  Returns ``{"texts", "tokens": int64 [B, width] (CPU),
+        "first_logits": f32 [B, V] (device)}``.  A pair outside the decoder or given twice, a wrong ``vectors`` shape or dtype, a
+        bad mode / steps / alpha / rows and beams are ``ValueError``s raised before anything is launched on the decoder."""
+        res = self._generate_resid(samples, head_patch=dict(heads=heads, vectors=vectors, mode=mode, alpha=alpha, steps=steps, rows=rows))
+        return {"texts": self.decode_ids(res.tokens), "tokens": res.tokens, "first_logits": res.first_logits}
+
     def _label_constraint(self, samples: Dict[str, Any]):
         """``(automaton, start states)`` for a batch that sets ``constrain_labels`` (one grammar per row, by its ``dataset_type``),
         else ``None``.  Automata are built once per set of dataset types from this model's tokenizer and kept."""

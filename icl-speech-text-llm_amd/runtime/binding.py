@@ -142,6 +142,8 @@ _SIGNATURES = {
     "icl_cross_entropy": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "icl_resid_rows_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32,
                                    c_float, c_void_p]),
+    "icl_head_rows_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int32,
+                                   c_void_p, c_int64, c_int32, c_float, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -811,6 +813,34 @@ def resid_rows(h, rows, *, capture=None, vec=None, mode="replace", alpha: float 
     _check(load_library().icl_resid_rows_f32(h.data_ptr(), h.stride(0), rows.data_ptr(), n, hidden, _ptr(capture), ld_cap,
                                              _ptr(vec), ld_vec, mode_i, float(alpha), _stream()), "icl_resid_rows_f32")
     return h
+
+
+def head_rows(att, rows, *, n_heads: int, head_dim: int, capture=None, heads=None, vec=None, mode="replace", alpha: float = 1.0):
+    """Attention-head output capture and patch at the listed rows (icl_head_rows_bf16).  att: bf16 [R, >= n_heads * head_dim] (row
+    stride = its leading dimension), patched in place; rows: int32 [n], distinct rows of att; capture: None or bf16 [n, >= n_heads *
+    head_dim], receives the rows' PRE-patch bits; heads: int32 [n_sel], distinct heads; vec: None or f32 [n, n_sel, head_dim] (one
+    block of vectors per entry) or [1, n_sel, head_dim] / [n_sel, head_dim] (one for all entries), in the order of ``heads``; mode
+    "replace" (att = bf16(vec)) or "add" (att = bf16(fma(alpha, vec, att)))."""
+    _require_gpu(att, rows, capture, heads, vec)
+    assert att.dtype == torch.bfloat16 and att.dim() == 2 and att.stride(1) == 1 and rows.dtype == torch.int32 and rows.is_contiguous()
+    n, n_sel = rows.numel(), 0
+    ld_cap = ld_vec = 0
+    if capture is not None:
+        assert capture.dtype == torch.bfloat16 and capture.dim() == 2 and capture.shape[0] == n and capture.stride(1) == 1
+        ld_cap = capture.stride(0)
+    if heads is not None:
+        assert heads.dtype == torch.int32 and heads.dim() == 1 and heads.is_contiguous()
+        n_sel = heads.numel()
+    if vec is not None:
+        assert heads is not None, "vec needs heads"
+        assert vec.dtype == torch.float32 and vec.dim() in (2, 3) and vec.shape[-2:] == (n_sel, head_dim) and vec[0].is_contiguous()
+        assert vec.dim() == 2 or vec.shape[0] in (1, n), f"{vec.shape[0]} blocks of vectors for {n} rows"
+        ld_vec = vec.stride(0) if vec.dim() == 3 and vec.shape[0] > 1 else 0      # 0: the one block serves every entry
+    mode_i = RESID_MODES[mode] if mode in RESID_MODES else int(mode)   # an integer goes through: the entry point refuses a bad one
+    _check(load_library().icl_head_rows_bf16(att.data_ptr(), att.stride(0), rows.data_ptr(), n, n_heads, head_dim, _ptr(capture),
+                                             ld_cap, _ptr(heads), n_sel, _ptr(vec), ld_vec, mode_i, float(alpha), _stream()),
+           "icl_head_rows_bf16")
+    return att
 
 
 def cross_entropy(logits, labels, row_loss, mean_loss, V=None):

@@ -3,6 +3,7 @@
   the prompt-attention readout   ``AttnReadout``          icl_attn_segmass_bf16         where the row looks, per prompt segment
   attention knockout             ``Knockout``             icl_attn_decode_masked_bf16   the row attends as if segments were absent
   residual capture / patching    a tensor, ``ResidPatch`` icl_resid_rows_f32            the row's residual stream, read and written
+  head-output capture / patching a tensor, ``HeadPatch``  icl_head_rows_bf16            what single heads hand to o_proj, read and written
 
 Host validation (``check_*``), device state (``*_state``), re-slicing to a prefill chunk and to the kept rows of a drop, and
 ``Probes``, the one bundle handed between runtime/salmonn.py and runtime/engines.py.
@@ -22,6 +23,7 @@ MAX_READOUT_SEGMENTS = 32      # icl_attn_segmass_bf16: one thread per (head of 
 MAX_KNOCKOUT_SEGMENTS = 32     # icl_attn_decode_masked_bf16: one bit of a u32 per segment; ids >= 32 are never blocked
 IGNORE_SEGMENT = 255           # a segment id that is counted nowhere and never blocked, whatever n_seg is
 PATCH_KEYS = ("site", "vectors", "mode", "alpha", "rows", "steps")
+HEAD_PATCH_KEYS = ("heads", "vectors", "mode", "alpha", "rows", "steps")
 
 
 # ================================================================================================
@@ -134,6 +136,53 @@ class ResidPatch:
         B.resid_rows(h, rows, capture=capture, vec=self.vectors, mode=self.mode, alpha=self.alpha)
 
 
+@dataclass
+class HeadPatch:
+    """Attention-head output patching at the deciding rows, all on the device: in the attention output of a decoder layer — the
+    operand of its o_proj — the selected heads of the LAST prompt row of the listed sequences, and with ``steps == "all"`` of
+    every generated row, are replaced by their vectors, or get ``alpha`` times their vectors added (icl_head_rows_bf16).
+    ``heads`` int32 [n_pairs]: the head indices of the (layer, head) pairs, sorted by layer and head; ``layers``: (layer, first
+    pair, end pair) of every layer with a selected head, ascending; ``vectors`` f32 [n_listed, n_pairs, head_dim] in that order
+    of pairs, or [1, n_pairs, head_dim]: one block for all listed rows; ``row_seq`` int32 [n_listed]: the listed sequences,
+    ascending and distinct (``listed``: the same on the host).  The runtime keeps the three tensors in graph-visible workspace
+    buffers and refills them on every call, so ``uid`` — what a captured decode graph bakes in besides those pointers: the number
+    of listed rows (a grid size), whether the vectors are shared (a leading dimension), the layers that launch with their head
+    counts (grid sizes and offsets into the buffers), mode, steps and alpha, a by-value kernel argument — keys the decode graphs."""
+    vectors: torch.Tensor
+    heads: torch.Tensor
+    row_seq: torch.Tensor
+    listed: Tuple[int, ...]
+    layers: Tuple[Tuple[int, int, int], ...]
+    mode: str = "replace"
+    alpha: float = 1.0
+    steps: str = "prompt"
+
+    @property
+    def uid(self):
+        return ("head_patch", len(self.listed), int(self.vectors.shape[0]), tuple((l, p1 - p0) for l, p0, p1 in self.layers), self.mode,
+                self.steps, float(self.alpha))
+
+    def rows(self, b0: int, b1: int) -> Optional["HeadPatch"]:
+        """The patch of sequences b0 .. b1-1 (views; sequence ids relative to b0), for a prefill over that chunk of the batch
+        (``KVCache.rows``); None when the chunk lists no row."""
+        part = _listed_rows(self.listed, self.row_seq, b0, b1)
+        if part is None:
+            return None
+        lo, hi, sub, row_seq = part
+        return replace(self, vectors=self.vectors if self.vectors.shape[0] == 1 else self.vectors[lo:hi], row_seq=row_seq, listed=sub)
+
+    def pairs(self, layer: int) -> Optional[Tuple[int, int]]:
+        """(first pair, end pair) of ``layer``, or None: no head of the layer is selected."""
+        return next(((p0, p1) for l, p0, p1 in self.layers if l == layer), None)
+
+    def launch(self, layer: int, att: torch.Tensor, rows: torch.Tensor, cfg, capture: Optional[torch.Tensor] = None) -> None:
+        """Patch the layer's selected heads in rows ``rows`` (int32 [n_listed]) of ``att``; ``capture`` bf16 [n_listed, n_heads *
+        head_dim] receives the rows' pre-patch bits."""
+        p0, p1 = self.pairs(layer)
+        B.head_rows(att, rows, n_heads=cfg.n_heads, head_dim=cfg.head_dim, capture=capture, heads=self.heads[p0:p1],
+                    vec=self.vectors[:, p0:p1], mode=self.mode, alpha=self.alpha)
+
+
 # ================================================================================================
 # The bundle the layers hand to each other
 # ================================================================================================
@@ -141,20 +190,27 @@ class ResidPatch:
 class Probes:
     """The probes of one call, each optional: what ``generate`` / ``prompt_attention`` build, ``_prefill_logits`` slices per
     chunk and ``LlamaHIP.prefill`` / ``_last_layer_rows`` / ``decode_step`` call at their hook points.  ``capture``: f32 [n_seqs,
-    n_layers + 1, hidden], receives the residual stream of every sequence's last prompt row at every site, pre-patch."""
+    n_layers + 1, hidden], receives the residual stream of every sequence's last prompt row at every site, pre-patch;
+    ``head_capture``: bf16 [n_seqs, n_layers, n_heads, head_dim], receives the head outputs of that row in every layer, as o_proj
+    would have read them (after a knockout's rewrite), before a head patch."""
     readout: Optional[AttnReadout] = None
     knockout: Optional[Knockout] = None
     capture: Optional[torch.Tensor] = None
     patch: Optional[ResidPatch] = None
+    head_capture: Optional[torch.Tensor] = None
+    head_patch: Optional[HeadPatch] = None
     # host tables of the prefill in progress (``start_prefill``), all int32 on the device: the sequences' last packed rows, the
-    # prompt lengths as the masked launch's key counts, the last packed rows of the knockout's and of the patch's listed sequences
+    # prompt lengths as the masked launch's key counts, the last packed rows of the knockout's, of the patch's and of the head
+    # patch's listed sequences
     _last: Optional[torch.Tensor] = field(default=None, init=False, repr=False)
     _key_counts: Optional[torch.Tensor] = field(default=None, init=False, repr=False)
     _ko_last: Optional[torch.Tensor] = field(default=None, init=False, repr=False)
     _pt_last: Optional[torch.Tensor] = field(default=None, init=False, repr=False)
+    _hp_last: Optional[torch.Tensor] = field(default=None, init=False, repr=False)
 
     def _or_none(self) -> Optional["Probes"]:
-        return None if all(p is None for p in (self.readout, self.knockout, self.capture, self.patch)) else self
+        return None if all(p is None for p in (self.readout, self.knockout, self.capture, self.patch, self.head_capture,
+                                               self.head_patch)) else self
 
     def rows(self, b0: int, b1: int) -> Optional["Probes"]:
         """The bundle of a prefill over sequences b0 .. b1-1.  A probe that lists no row of the chunk is absent from it, and a
@@ -162,15 +218,20 @@ class Probes:
         return Probes(None if self.readout is None else self.readout.rows(b0, b1),
                       None if self.knockout is None else self.knockout.rows(b0, b1),
                       None if self.capture is None else self.capture[b0:b1],
-                      None if self.patch is None else self.patch.rows(b0, b1))._or_none()
+                      None if self.patch is None else self.patch.rows(b0, b1),
+                      None if self.head_capture is None else self.head_capture[b0:b1],
+                      None if self.head_patch is None else self.head_patch.rows(b0, b1))._or_none()
 
     def decode_steps(self) -> Optional["Probes"]:
-        """The bundle of the decode steps: the knockout, and a patch of every step; None when the steps are the plain ones."""
-        return Probes(knockout=self.knockout, patch=self.patch if self.patch is not None and self.patch.steps == "all" else None)._or_none()
+        """The bundle of the decode steps: the knockout, and a patch and a head patch of every step; None when the steps are the
+        plain ones."""
+        return Probes(knockout=self.knockout, patch=self.patch if self.patch is not None and self.patch.steps == "all" else None,
+                      head_patch=self.head_patch if self.head_patch is not None and self.head_patch.steps == "all" else None)._or_none()
 
     def graph_key(self) -> tuple:
         """What a captured decode loop bakes in of its probes besides pointers: appended to the graph key of the plain call."""
-        every_step = (self.knockout, self.patch if self.patch is not None and self.patch.steps == "all" else None)
+        every_step = (self.knockout, self.patch if self.patch is not None and self.patch.steps == "all" else None,
+                      self.head_patch if self.head_patch is not None and self.head_patch.steps == "all" else None)
         return tuple(p.uid for p in every_step if p is not None)
 
     # ---- a prefill: preconditions and host tables, once per call of LlamaHIP.prefill ----
@@ -180,11 +241,13 @@ class Probes:
         assert self.readout is None or (last and bf16), "the attention readout reads the last rows' q and a bf16 K cache"
         assert self.knockout is None or (last and bf16), "attention knockout rewrites the last rows from a bf16 KV cache"
         assert (self.capture is None and self.patch is None) or last, "residual capture / patching works on the last rows (last_rows_only)"
-        ko, pt = self.knockout, self.patch
+        assert (self.head_capture is None and self.head_patch is None) or last, "head capture / patching works on the last rows (last_rows_only)"
+        ko, pt, hp = self.knockout, self.patch, self.head_patch
         self._last = last_idx
         self._key_counts = None if ko is None else _i32(seq_lens, last_idx.device)
         self._ko_last = None if ko is None else _i32([cu_h[b + 1] - 1 for b in ko.listed], last_idx.device)
         self._pt_last = None if pt is None else _i32([cu_h[b + 1] - 1 for b in pt.listed], last_idx.device)
+        self._hp_last = None if hp is None else _i32([cu_h[b + 1] - 1 for b in hp.listed], last_idx.device)
 
     # ---- the three hook points of a layer.  ``packed``: the rows of h / q / att are the packed rows of a prefill, where the
     # deciding row of a sequence is its last one; otherwise row b is sequence b's (a decode step, the gathered last rows) ----
@@ -214,10 +277,24 @@ class Probes:
     def attention_written(self, layer: int, q: torch.Tensor, att: torch.Tensor, kc, vc, cfg, max_len: int,
                           lens: Optional[torch.Tensor] = None, packed: bool = False) -> None:
         """The layer's attention output is in ``att``: a knockout that covers the layer rewrites the listed deciding rows under
-        their masks.  ``lens``: int32 [n_seqs] key counts (a decode step's; None in a prefill: the prompt lengths)."""
+        their masks.  ``lens``: int32 [n_seqs] key counts (a decode step's; None in a prefill: the prompt lengths).  Then the
+        head outputs, as o_proj is about to read them: ``head_capture[:, layer]`` receives the deciding row of every sequence, and
+        a head patch with a selected head in this layer rewrites those heads in the rows of its listed sequences.  One launch
+        does both when the patch lists every sequence; a patch of some sequences next to a capture of all is a capture launch
+        and then a patch launch (``residual_site``'s rule).  A layer with neither launches nothing."""
         ko = self.knockout
         if ko is not None and ko.covers(layer):
             ko.launch(q, att, self._ko_last if packed else ko.row_seq, kc, vc, self._key_counts if lens is None else lens, cfg, max_len)
+        cap = None if self.head_capture is None else self.head_capture[:, layer].flatten(1)
+        hp = self.head_patch if self.head_patch is not None and self.head_patch.pairs(layer) is not None else None
+        if cap is not None:
+            n = cap.shape[0]
+            all_rows = self._last if packed else _i32(list(range(n)), att.device)
+            if hp is not None and hp.listed == tuple(range(n)):
+                return hp.launch(layer, att, all_rows, cfg, capture=cap)
+            B.head_rows(att, all_rows, n_heads=cfg.n_heads, head_dim=cfg.head_dim, capture=cap)
+        if hp is not None:
+            hp.launch(layer, att, self._hp_last if packed else hp.row_seq, cfg)
 
     def masks_attention(self, cache) -> bool:
         """Does a knockout rewrite rows of this decode step's attention output?  It then needs q rotated in place (the
@@ -350,6 +427,36 @@ def knockout_state(ws: Workspace, cfg, knockout, max_len: int) -> Knockout:
     return Knockout(seg_d, blk_d, rows_d, listed, layers)
 
 
+def _patch_options(d: dict, n_prompts: int, what: str):
+    """``mode``, ``steps``, ``alpha`` and ``rows`` of a ``patch`` / ``head_patch`` dict, validated: (mode, steps, alpha as a float,
+    the rows as an ascending list — all prompts for None)."""
+    mode, steps = d.get("mode", "replace"), d.get("steps", "prompt")
+    if mode not in ("replace", "add"):
+        raise ValueError(f"{what}: mode must be 'replace' or 'add', not {mode!r}")
+    if steps not in ("prompt", "all"):
+        raise ValueError(f"{what}: steps must be 'prompt' or 'all', not {steps!r}")
+    try:
+        alpha = float(d.get("alpha", 1.0))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: alpha must be a finite number, not {d.get('alpha')!r}") from None
+    if not math.isfinite(alpha):
+        raise ValueError(f"{what}: alpha must be finite, not {alpha}")
+    rows = d.get("rows")
+    if rows is None:
+        rows = list(range(n_prompts))
+    else:
+        try:
+            rows = [int(b) for b in rows]
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: rows must be None or a list of prompt indices, not {d.get('rows')!r}") from None
+        if len(set(rows)) != len(rows):
+            raise ValueError(f"{what}: rows {rows} lists a prompt twice")
+        if rows and not (0 <= min(rows) and max(rows) < n_prompts):
+            raise ValueError(f"{what}: rows {rows} outside 0..{n_prompts - 1}")
+        rows = sorted(rows)
+    return mode, steps, alpha, rows
+
+
 def check_patch(patch, cfg, n_prompts: int, num_beams: int, knockout):
     """Host validation of ``generate(patch=...)``: everything is a ``ValueError`` raised before any launch.  Returns the
     patch as a dict of all ``PATCH_KEYS`` — ``vectors`` f32 [n_prompts or 1, hidden], ``rows`` an ascending list — or None
@@ -369,30 +476,7 @@ def check_patch(patch, cfg, n_prompts: int, num_beams: int, knockout):
     if vec.dim() != 2 or vec.shape[1] != cfg.hidden or vec.shape[0] not in (1, n_prompts):
         raise ValueError(f"patch: vectors of shape {tuple(patch['vectors'].shape)}: [{n_prompts}, {cfg.hidden}] (one per prompt), "
                          f"[1, {cfg.hidden}] or [{cfg.hidden}] (shared)")
-    mode, steps = patch.get("mode", "replace"), patch.get("steps", "prompt")
-    if mode not in ("replace", "add"):
-        raise ValueError(f"patch: mode must be 'replace' or 'add', not {mode!r}")
-    if steps not in ("prompt", "all"):
-        raise ValueError(f"patch: steps must be 'prompt' or 'all', not {steps!r}")
-    try:
-        alpha = float(patch.get("alpha", 1.0))
-    except (TypeError, ValueError):
-        raise ValueError(f"patch: alpha must be a finite number, not {patch.get('alpha')!r}") from None
-    if not math.isfinite(alpha):
-        raise ValueError(f"patch: alpha must be finite, not {alpha}")
-    rows = patch.get("rows")
-    if rows is None:
-        rows = list(range(n_prompts))
-    else:
-        try:
-            rows = [int(b) for b in rows]
-        except (TypeError, ValueError):
-            raise ValueError(f"patch: rows must be None or a list of prompt indices, not {patch.get('rows')!r}") from None
-        if len(set(rows)) != len(rows):
-            raise ValueError(f"patch: rows {rows} lists a prompt twice")
-        if rows and not (0 <= min(rows) and max(rows) < n_prompts):
-            raise ValueError(f"patch: rows {rows} outside 0..{n_prompts - 1}")
-        rows = sorted(rows)
+    mode, steps, alpha, rows = _patch_options(patch, n_prompts, "patch")
     if num_beams != 1:
         raise ValueError("patch runs with greedy, sampled and label-constrained decoding, not with beams (num_beams > 1)")
     if knockout is not None:
@@ -415,13 +499,85 @@ def patch_state(ws: Workspace, cfg, patch) -> ResidPatch:
     return ResidPatch(vec_d, rows_d, tuple(rows), patch["site"], patch["mode"], patch["alpha"], patch["steps"])
 
 
-def keep_rows(knockout, patch, keep: List[int]):
-    """``overlong="drop"``: a validated knockout and patch for the call over the prompts ``keep`` — the surviving rows' entries
-    and vectors, a patch's rows under the indices they have among the survivors."""
+def check_head_patch(hp, cfg, n_prompts: int, num_beams: int, knockout, patch):
+    """Host validation of ``generate(head_patch=...)``: everything is a ``ValueError`` raised before any launch.  Returns the
+    patch as a dict of all ``HEAD_PATCH_KEYS`` — ``heads`` a list of (layer, head) as given, ``vectors`` f32 [n_prompts or 1,
+    n_pairs, head_dim] in that order, ``rows`` an ascending list — or None when ``rows`` is empty."""
+    if not isinstance(hp, dict):
+        raise ValueError(f"head_patch must be a dict with the keys {HEAD_PATCH_KEYS}")
+    unknown = set(hp) - set(HEAD_PATCH_KEYS)
+    if unknown or "heads" not in hp or "vectors" not in hp:
+        raise ValueError("head_patch holds 'heads' and 'vectors', and optionally 'mode', 'alpha', 'rows' and 'steps' "
+                         f"(unknown: {sorted(unknown)})")
+    pairs = check_head_pairs(hp["heads"], cfg, "head_patch")
+    vec, D = hp["vectors"], cfg.head_dim
+    if not isinstance(vec, torch.Tensor) or vec.dtype != F32:
+        raise ValueError("head_patch: vectors must be a float32 tensor")
+    if vec.dim() == 2:
+        vec = vec[None]
+    if vec.dim() != 3 or tuple(vec.shape[1:]) != (len(pairs), D) or vec.shape[0] not in (1, n_prompts):
+        raise ValueError(f"head_patch: vectors of shape {tuple(hp['vectors'].shape)}: [{n_prompts}, {len(pairs)}, {D}] (one block per "
+                         f"prompt), [1, {len(pairs)}, {D}] or [{len(pairs)}, {D}] (shared), in the order of heads")
+    mode, steps, alpha, rows = _patch_options(hp, n_prompts, "head_patch")
+    if num_beams != 1:
+        raise ValueError("head_patch runs with greedy, sampled and label-constrained decoding, not with beams (num_beams > 1)")
+    if knockout is not None or patch is not None:
+        raise ValueError("head_patch together with knockout or with patch is not supported")
+    if not rows:
+        return None
+    return dict(heads=pairs, vectors=vec, mode=mode, alpha=alpha, rows=rows, steps=steps)
+
+
+def check_head_pairs(heads, cfg, what: str) -> List[Tuple[int, int]]:
+    """(layer, head) pairs as a list of int tuples: inside [0, n_layers) x [0, n_heads), non-empty, none given twice."""
+    try:
+        pairs = [(int(l), int(h)) for l, h in heads]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: heads must be a list of (layer, head) pairs, not {heads!r}") from None
+    if not pairs:
+        raise ValueError(f"{what}: heads is empty")
+    bad = [p for p in pairs if not (0 <= p[0] < cfg.n_layers and 0 <= p[1] < cfg.n_heads)]
+    if bad:
+        raise ValueError(f"{what}: pairs {bad} outside [0, {cfg.n_layers}) x [0, {cfg.n_heads})")
+    if len(set(pairs)) != len(pairs):
+        raise ValueError(f"{what}: heads {pairs} holds a pair twice")
+    return pairs
+
+
+def head_patch_state(ws: Workspace, cfg, hp) -> HeadPatch:
+    """The validated head patch on the device, in graph-visible workspace buffers refilled on every call: the head indices
+    sorted by (layer, head), the listed rows' vectors permuted to that order (one block when they are shared) and the listed
+    sequences."""
+    pairs, vec, rows = hp["heads"], hp["vectors"], hp["rows"]
+    order = sorted(range(len(pairs)), key=lambda i: pairs[i])
+    vec = vec[:, torch.tensor(order, device=vec.device)]
+    if vec.shape[0] != 1:
+        vec = vec[torch.tensor(rows, device=vec.device)]
+    layers, p0 = [], 0
+    for p1 in range(1, len(order) + 1):
+        if p1 == len(order) or pairs[order[p1]][0] != pairs[order[p0]][0]:
+            layers.append((pairs[order[p0]][0], p0, p1))
+            p0 = p1
+    vec_d = ws.get("gen_hp_vec", (vec.shape[0], len(pairs), cfg.head_dim), F32)
+    heads_d = ws.get("gen_hp_heads", (len(pairs),), I32)
+    rows_d = ws.get("gen_hp_rows", (len(rows),), I32)
+    vec_d.copy_(vec, non_blocking=True)
+    heads_d.copy_(torch.tensor([pairs[i][1] for i in order], dtype=I32), non_blocking=True)
+    rows_d.copy_(torch.tensor(rows, dtype=I32), non_blocking=True)
+    return HeadPatch(vec_d, heads_d, rows_d, tuple(rows), tuple(layers), hp["mode"], hp["alpha"], hp["steps"])
+
+
+def keep_rows(knockout, patch, keep: List[int], head_patch=None):
+    """``overlong="drop"``: a validated knockout, patch and head patch for the call over the prompts ``keep`` — the surviving
+    rows' entries and vectors, a patch's rows under the indices they have among the survivors."""
+    if head_patch is not None:
+        vec = head_patch["vectors"]
+        head_patch = dict(head_patch, vectors=vec if vec.shape[0] == 1 else vec[torch.tensor(keep, device=vec.device)],
+                          rows=[keep.index(b) for b in head_patch["rows"] if b in keep])
     if knockout is not None:
         knockout = ([knockout[0][b] for b in keep], [knockout[1][b] for b in keep]) + tuple(knockout[2:])
     if patch is not None:
         vec = patch["vectors"]
         patch = dict(patch, vectors=vec if vec.shape[0] == 1 else vec[torch.tensor(keep, device=vec.device)],
                      rows=[keep.index(b) for b in patch["rows"] if b in keep])
-    return knockout, patch
+    return knockout, patch, head_patch

@@ -41,6 +41,8 @@ class GenerateResult:
     hidden = None    # or f32 [B, n_layers + 1, hidden] (device), with ``want_hidden``: the residual stream of the last prompt row at
     #                  every site, pre-patch at a patched site.  An attribute set after construction, not a dataclass field: the
     #                  fields are what a result of a plain call consists of (the pinned generate trace lists them)
+    head_out = None  # or bf16 [B, n_layers, n_heads, head_dim] (device), with ``want_heads``: the head outputs of the last prompt row
+    #                  in every layer, as o_proj would have read them, pre-patch.  Set after construction, like ``hidden``
 
 
 @dataclass
@@ -69,6 +71,8 @@ def _undrop(sub: GenerateResult, keep: List[int], bad: List[int], n: int, pad: i
                          token_logprobs=spread(sub.token_logprobs, 0, nan))
     if sub.hidden is not None:
         res.hidden = spread(sub.hidden, 0, nan)
+    if sub.head_out is not None:
+        res.head_out = spread(sub.head_out, 0, nan)
     return res
 
 
@@ -260,7 +264,7 @@ class CausalLMRuntimeMixin:
                  top_k: int = 50, repetition_penalty: float = 1.0, generator: Optional[torch.Generator] = None,
                  sample_debug=None, want_step_logits: bool = False, overlong: str = "raise", num_beams: int = 1,
                  length_penalty: float = 1.0, beam_debug: Optional[dict] = None, constraint=None,
-                 knockout=None, want_hidden: bool = False, patch=None) -> GenerateResult:
+                 knockout=None, want_hidden: bool = False, patch=None, want_heads: bool = False, head_patch=None) -> GenerateResult:
         """Greedy search with HF ``generate(inputs_embeds=…)`` semantics (models/custom_salmon.py:704-720): returns only
         the new tokens; a row that has emitted EOS is filled with pad; the width is that of the longest row
         (``min_length`` is a no-op with inputs_embeds).  All steps are enqueued without a host sync; the
@@ -312,7 +316,22 @@ class CausalLMRuntimeMixin:
         ``steps="all"`` one per decode step plus the patched layer's input norm as a launch of its own; rows not listed keep
         their bits.  Works with every tail above, both KV dtypes and both weight dtypes.  ``ValueError`` before any launch:
         unknown keys, a site outside 0..n_layers, vectors of the wrong shape or dtype, a bad mode or steps, a non-finite alpha,
-        a duplicate or out-of-range row, beams, ``patch`` together with ``knockout``."""
+        a duplicate or out-of-range row, beams, ``patch`` together with ``knockout``.
+
+        ``want_heads`` and ``head_patch``: the output of single attention heads at the deciding rows — the head_dim-vector a head
+        hands to o_proj — read and written.  ``want_heads``: the result's ``head_out`` bf16 [B, n_layers, n_heads, head_dim]
+        (device) holds the LAST prompt row's head outputs in every layer, as o_proj would have read them (after a knockout's
+        rewrite), before a head patch (dropped rows: NaN); ``head_contrib`` turns them into the heads' summands of the residual
+        stream.  ``head_patch`` = a dict ``heads`` ([(layer, head), ...], distinct), ``vectors`` (f32, CPU or device: [B, n_pairs,
+        head_dim] one block per prompt, or [n_pairs, head_dim] / [1, n_pairs, head_dim] shared, in the order of ``heads``), and
+        ``mode``, ``alpha``, ``rows``, ``steps`` as for ``patch`` (replace: head = bf16(vector); add: head = bf16(fma(alpha,
+        vector, head))).  One launch (icl_head_rows_bf16) per layer and prefill chunk with ``want_heads``; a patch alone launches
+        only in the layers that hold a selected head and in the chunks that list a row, and with ``steps="all"`` once per such
+        layer and decode step; the decode steps keep their form (the fused RoPE + attention launch writes the buffer too).  Heads
+        not selected and rows not listed keep their bits.  Works with every tail above, both KV dtypes and both weight dtypes,
+        grouped-query and QK-norm decoders.  ``ValueError`` before any launch: unknown keys, a pair outside [0, n_layers) x [0,
+        n_heads) or given twice, vectors of the wrong shape or dtype, a bad mode or steps, a non-finite alpha, a duplicate or
+        out-of-range row, beams (also for ``want_heads``), ``head_patch`` together with ``knockout`` or with ``patch``."""
         args = {k: v for k, v in locals().items() if k not in ("self", "prompts", "speech")}   # the keyword arguments, as given
         c, ws = self.lm_cfg, self.ws
         # ---- 1. validate: every caller error is raised here, before anything is launched
@@ -327,6 +346,10 @@ class CausalLMRuntimeMixin:
             knockout = args["knockout"] = P.check_knockout(knockout, c, self.kv_dtype, plens, num_beams)   # None: every blocked set is empty
         if patch is not None:
             patch = args["patch"] = P.check_patch(patch, c, len(plens), num_beams, knockout)     # None: an empty row list
+        if head_patch is not None:
+            head_patch = args["head_patch"] = P.check_head_patch(head_patch, c, len(plens), num_beams, knockout, patch)
+        if want_heads and num_beams != 1:
+            raise ValueError("want_heads runs with greedy, sampled and label-constrained decoding, not with beams (num_beams > 1)")
         if want_hidden and num_beams != 1:
             raise ValueError("want_hidden runs with greedy, sampled and label-constrained decoding, not with beams (num_beams > 1)")
         bad = [b for b, n in enumerate(plens) if n + max_new_tokens > limit]
@@ -364,7 +387,7 @@ class CausalLMRuntimeMixin:
             keep = [b for b in range(len(plens)) if b not in set(bad)]
             if constraint is not None:
                 args["constraint"] = (constraint[0], [constraint[1][b] for b in keep])
-            args["knockout"], args["patch"] = P.keep_rows(knockout, patch, keep)
+            args["knockout"], args["patch"], args["head_patch"] = P.keep_rows(knockout, patch, keep, head_patch)
             return _undrop(self.generate([prompts[b] for b in keep], speech, **args), keep, bad, len(plens), pad)
         # ---- 3. beams
         if num_beams != 1:
@@ -380,8 +403,10 @@ class CausalLMRuntimeMixin:
         if marks is not None:
             marks["prefill_start"].record()
         hidden = ws.get("gen_hidden", (Bn, c.n_layers + 1, c.hidden), F32) if want_hidden else None
+        head_out = ws.get("gen_head_out", (Bn, c.n_layers, c.n_heads, c.head_dim), BF16) if want_heads else None
         probes = P.Probes(knockout=None if knockout is None else P.knockout_state(ws, c, knockout, max_len), capture=hidden,
-                          patch=None if patch is None else P.patch_state(ws, c, patch))      # (never both a knockout and a patch)
+                          patch=None if patch is None else P.patch_state(ws, c, patch),      # (never both a knockout and a patch)
+                          head_capture=head_out, head_patch=None if head_patch is None else P.head_patch_state(ws, c, head_patch))
         logits = self._prefill_logits(h, lens, cache, ws.get("gen_last", (Bn, c.hidden), F32), probes=probes)
         first = logits.clone() if want_first_logits else None
         trace = ws.get("gen_logits_trace", (max_new_tokens, Bn, c.vocab), F32) if want_step_logits else None
@@ -423,6 +448,8 @@ class CausalLMRuntimeMixin:
                              token_logprobs=lps.cpu()[:, :width].contiguous() if lps is not None else None)
         if hidden is not None:
             res.hidden = hidden.clone()
+        if head_out is not None:
+            res.head_out = head_out.clone()
         return res
 
     # ---- the residual stream at the deciding rows: the logit lens and generate(patch=...) ----
@@ -439,6 +466,26 @@ class CausalLMRuntimeMixin:
         out = torch.empty((hidden.shape[0], c.n_layers + 1, c.vocab), dtype=F32, device=self.device)
         for site in range(c.n_layers + 1):
             out[:, site].copy_(self.llama.logits(self.ws, hidden[:, site].contiguous(), name="lens_logits"))
+        return out
+
+    HEAD_CONTRIB_TILE = 2      # the 64x64 tile, whatever the batch: a row's bits do not depend on its neighbours
+
+    def head_contrib(self, head_out: torch.Tensor, heads) -> torch.Tensor:
+        """What single heads add to the residual stream.  ``head_out`` bf16 [B, n_layers, n_heads, head_dim]
+        (``generate(want_heads=True)``), ``heads`` [(layer, head), ...] -> f32 [B, n_pairs, hidden] on the device: for pair (l, h)
+        ``head_out[:, l, h] @ Wo_l[:, h*D:(h+1)*D]^T``, the summand the layer's ``o`` GEMM adds to the stream for that head — one
+        icl_gemm_bf16 launch per pair on the column slice of the weight (K = head_dim, lda = the capture's row stride, ldw =
+        hidden, f32 output) on ``HEAD_CONTRIB_TILE``.  In FP8 weight mode Wo is W', the bf16 weight the prefill multiplies by."""
+        c = self.lm_cfg
+        D = c.head_dim
+        if not (isinstance(head_out, torch.Tensor) and head_out.dtype == BF16 and head_out.dim() == 4
+                and tuple(head_out.shape[1:]) == (c.n_layers, c.n_heads, D)):
+            raise ValueError(f"head_out must be bf16 [B, {c.n_layers}, {c.n_heads}, {D}]")
+        pairs = P.check_head_pairs(heads, c, "head_contrib")
+        head_out = head_out.to(self.device).contiguous()
+        out = torch.empty((head_out.shape[0], len(pairs), c.hidden), dtype=F32, device=self.device)
+        for i, (l, h) in enumerate(pairs):
+            B.gemm(head_out[:, l, h], self.llama.w.layers[l].wo[:, h * D:(h + 1) * D], out[:, i], K=D, tile=self.HEAD_CONTRIB_TILE)
         return out
 
     # ---- the prompt-attention readout: generate()'s prefill plus one launch per layer ----

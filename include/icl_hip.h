@@ -538,6 +538,31 @@ int icl_gather_rows_bf16(const void* src, int64_t ld_src, const int32_t* idx, vo
 int icl_resid_rows_f32(float* h, int64_t ldh, const int32_t* rows, int32_t n_rows, int32_t hidden, float* capture,
                        int64_t ld_cap, const float* vec, int64_t ld_vec, int32_t mode, float alpha, void* stream);
 
+/* ---- attention-head output capture and patching at listed rows -------------------------------------------------------
+ * The read and the write of single heads' outputs — the D-vector a head hands to o_proj — on the bf16 attention-output buffer
+ * att [.][ld_att] (transformers: a forward pre-hook on self_attn.o_proj).  Head h of a row is columns h*D .. h*D + D - 1,
+ * D = head_dim.  List entry r (0 <= r < n_rows) works on row = rows[r] of att, in this order:
+ *   capture (unless NULL):  capture[r*ld_cap + c] = att[row*ld_att + c] for c < n_heads*D, copied as bits (NaN payloads, -0.0
+ *                           and subnormals survive): always the value BEFORE the patch;
+ *   vec (unless NULL), for s < n_sel, h = heads[s], i < D, v = vec[r*ld_vec + s*D + i] (ld_vec == 0: one block of n_sel vectors
+ *   for all entries), a = att[row*ld_att + h*D + i]:
+ *     mode 0, replace:  a = bf16(v): f32_to_bf16_bits, round to nearest even, NaN stays NaN; a v that is a bf16 value comes back
+ *                       as its bits;
+ *     mode 1, add:      a = bf16(__fmaf_rn(alpha, v, (float)a)): ONE f32 rounding of the exact alpha*v + a, then the bf16 rounding.
+ *                       Mode 0 does not use alpha (still checked).
+ * Rows that no entry lists, heads that heads[] does not hold, and the columns at or beyond n_heads*D are not written.  rows values
+ * must be rows of att (the caller's duty: the call cannot see that extent); heads values must be distinct and inside
+ * 0..n_heads-1, and no row may be listed twice (two threads would race on it) — the host layers above refuse such lists.
+ * capture and vec must not overlap att.  16-byte moves, one per thread; all address arithmetic in int64_t (ld_att may exceed 2^32).
+ * ICL_EINVAL (before any launch, naming the argument): att or rows NULL; capture and vec both NULL; vec without heads; n_rows
+ * outside 1..65535; head_dim not 64 or 128; n_heads outside 1..65535; with vec, n_sel outside 1..n_heads; ld_att or ld_cap (with
+ * capture) below n_heads*D or not a multiple of 8; a non-zero ld_vec (with vec) below n_sel*D or not a multiple of 4; att,
+ * capture or vec not 16-byte aligned; mode outside {0, 1}; alpha not finite.
+ */
+int icl_head_rows_bf16(void* att, int64_t ld_att, const int32_t* rows, int32_t n_rows, int32_t n_heads, int32_t head_dim,
+                       void* capture, int64_t ld_cap, const int32_t* heads, int32_t n_sel, const float* vec, int64_t ld_vec,
+                       int32_t mode, float alpha, void* stream);
+
 /* ---- K11 (beam search): one step of HF's static-shaped beam search + the cache reorder ------------------------------
  * icl_beam_step, per batch row b (num_beams K <= 8, max_new_tokens T <= 64, V >= 2K): log-softmax of the K beams' logits
  *   (row b*rows_per_batch + k; rows_per_batch == 1 at step 0, where the K beams still share the prompt's one distribution) plus
