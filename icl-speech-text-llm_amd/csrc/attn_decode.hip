@@ -1,5 +1,5 @@
 // attn_decode.hip — single-token decode attention over the KV cache (HBM-bound KV stream): ONE kernel,
-// attn_decode_kernel<D, UNR, FUSE, F8, EPL, NG, MASK>, behind every icl_attn_decode_* entry point.
+// attn_decode_kernel<D, UNR, FUSE, F8, EPL, NG, MASK, R>, behind every icl_attn_decode_* entry point and icl_attn_cut_rows_bf16.
 // Cache layout [n_seqs][n_heads][max_len][D] bf16: the keys of one (sequence, head) are one
 // contiguous stream, read with 16-B loads straight to VGPRs (no LDS round trip: guide §5 table row
 // "GEMV / M <= 16 decode").  D/8 lanes cover one key row, so a wave-instruction fetches 64/(D/8)
@@ -50,6 +50,17 @@ constexpr float LOG2E = 1.4426950408889634f;
 //   <128, 4, .., 4>   152 / 59 / 3  (160 / 32 / 3)      <128, 4, .., 5>   169 / 76 / 2  (165 / 42 / 3)
 //   <128, 4, .., 6>   212 / 91 / 2  (206 / 42 / 2)      <128, 4, .., 7>   241 / 104 / 2 (239 / 46 / 2)
 //   <128, 4, .., 8>   256 + 3 AGPRs / 101 / 1  (254 / 32 / 2): UNR 4 is the smallest there is, so G = 8 runs one wave per SIMD
+// R (icl_attn_cut_rows_bf16, attention cuts between prompt segments) > 0: a form of MASK over TILES of R listed rows of one cache
+// sequence — hundreds of interior prompt rows per sequence, not one — so that one pass over the sequence's K / V stream serves R
+// rows as it serves NG heads: R * NG states per lane, each with its own key count and mask.  ONE instantiation per (head_dim, G)
+// whatever the grid and the list, UNR 4 (the grouped table's from three states on): a slot's bits are the same alone in a tile,
+// in any slot, next to any companions.  R = 4 at G = 1, 2 at G = 2, 1 from G = 3 on (cut_tile_rows).  The same remark for
+// <D, 4, .., NG, MASK, R>, VGPRs / SGPRs / waves per SIMD; no instantiation uses scratch or spills:
+//   <64, 4, .., 1, 4>   194 / 54 / 2     <128, 4, .., 1, 4>  172 / 54 / 2     <128, 4, .., 2, 2>  144 / 52 / 3
+//   <128, 4, .., 3, 1>  126 / 47 / 4     <128, 4, .., 4, 1>  144 / 51 / 3     <128, 4, .., 5, 1>  162 / 55 / 3
+//   <128, 4, .., 6, 1>  212 / 53 / 2     <128, 4, .., 7, 1>  230 / 57 / 2     <128, 4, .., 8, 1>  248 / 61 / 2
+// (four slots of one head hold more than four heads of one row — 172 against 152 VGPRs — because each slot brings its own key
+// count into the predicate; still two waves per SIMD and no scratch, so R = 4 stays.)
 struct DecodeRope {
   const float* cosT;
   const float* sinT;
@@ -70,8 +81,16 @@ struct DecodeMask : DecodeRope {
   const int* row_seq;         // list entry r: the cache sequence ...
   const int* row_q;           // ... and the row of Q / O
 };
-template <bool MASK> struct DecodeTail { typedef DecodeRope T; };
-template <> struct DecodeTail<true> { typedef DecodeMask T; };
+// R > 0: the tiles of icl_attn_cut_rows_bf16 behind the mask's seg / ld_seg / blocked / row_q (row_seq unused), one entry per
+// tile or per slot t * R + r
+struct DecodeCut : DecodeMask {
+  const int* tile_seq;            // [n_tiles]: the cache sequence of a tile
+  const int* row_len;             // [n_tiles * R]: the keys a slot's query may see
+  const unsigned char* head_on;   // [query heads] or NULL (all): a head that is off is not written
+};
+template <bool MASK, int R> struct DecodeTail { typedef DecodeRope T; };
+template <> struct DecodeTail<true, 0> { typedef DecodeMask T; };
+template <int R> struct DecodeTail<true, R> { typedef DecodeCut T; };
 
 template <int EPL> struct KvWords;                       // EPL bf16 of a lane: EPL / 2 dwords
 template <> struct KvWords<8> { typedef u32x4 T; };
@@ -101,16 +120,25 @@ __device__ __forceinline__ typename KvWords<EPL>::T kv_words(typename KvRaw<F8, 
 // One segment byte per key a lane group loads (UNR bytes in flight next to the UNR K / V rows); the NG masks of a K/V group are
 // wave-uniform (SGPRs) and each head's own mask meets the shared K / V chunk inside the per-head loop.  A stream folds the keys
 // the unmasked kernel gives it, in its groups of four: a masked key is a key past the end, s = NEG_BIG and p = 0.
-template <int D, int UNR, bool FUSE, bool F8, int EPL, int NG, bool MASK = false>
+// R > 0 (icl_attn_cut_rows_bf16, attention cuts): blockIdx.y = t, a TILE of R slots — listed rows of ONE cache sequence tile_seq[t],
+// slot r being entry t * R + r of row_q / row_len / blocked (row_q < 0: an empty slot) — and the NG loop runs over the R * NG
+// queries (slot r, head g of the group) that share the loaded K / V chunk.  The block walks keys 0 .. max row_len of its live
+// slots - 1 once; key j counts for a state iff j < row_len[slot] and not blocked by the slot's mask, so the keys a slot meets past
+// its own row_len are keys past the end (s = NEG_BIG, p = 0: m, l and o keep their bits; a group of four wholly past it is not
+// entered).  Heads that are off and empty slots are not written; a K/V group whose heads are all off returns at once.
+template <int D, int UNR, bool FUSE, bool F8, int EPL, int NG, bool MASK = false, int R = 0>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* Q, int64_t ldq, const void* Kc, const void* Vc,
                                                            const float* Ks, const float* Vs, unsigned short* O, int64_t ldo,
                                                            const int* lens, int n_heads, int max_len, float scale_log2e,
-                                                           typename DecodeTail<MASK>::T rp) {
+                                                           typename DecodeTail<MASK, R>::T rp) {
   typedef typename KvRaw<F8, EPL>::T Raw;
   typedef typename KvWords<EPL>::T Wd;
   static_assert(!F8 || EPL == 16, "the fp8 cache is read 16 elements per lane");
   static_assert(NG == 1 || (!FUSE && !F8 && D == 128 && EPL == 8), "grouped-query: the plain bf16 form at head_dim 128 only");
   static_assert(!MASK || (!FUSE && !F8 && EPL == 8), "masked: the plain bf16 forms only");
+  static_assert(R == 0 || MASK, "row tiles: a form of the masked kernel");
+  constexpr bool TILE = R > 0;
+  constexpr int NQ = (TILE ? R : 1) * NG;   // online-softmax states of a lane: one per (slot, head of the group)
   constexpr int NW = EPL / 2;      // bf16 words per lane
   constexpr int EB = F8 ? 1 : 2;   // bytes per cache element
   constexpr int LPR = D / EPL;     // lanes per key row
@@ -121,23 +149,44 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int dc = lane % LPR, sub = lane / LPR;
   int bs = b, bq = b;              // the cache sequence, and the row of Q / O
-  unsigned blk[NG] = {};
+  unsigned blk[NQ] = {};
+  int rq[NQ], qlen[NQ];            // TILE: the row of Q / O of a state's slot, and the keys its query may see (0: nothing to do)
   const unsigned char* segp = nullptr;
-  if constexpr (MASK) {
+  int len;
+  if constexpr (TILE) {
+    bs = rp.tile_seq[b];
+    unsigned on = 0;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) on |= (rp.head_on == nullptr || rp.head_on[h * NG + g]) ? 1u << g : 0u;
+    if (!on) return;
+    len = 0;
+#pragma unroll
+    for (int x = 0; x < NQ; ++x) {
+      const int e = b * R + x / NG;
+      rq[x] = rp.row_q[e];
+      const bool live = rq[x] >= 0 && ((on >> (x % NG)) & 1u);
+      qlen[x] = live ? min(rp.row_len[e], max_len) : 0;
+      if (!live) rq[x] = -1;
+      blk[x] = rp.blocked[e];
+      len = max(len, qlen[x]);
+    }
+    if (len <= 0) return;
+    segp = rp.seg + (int64_t)bs * rp.ld_seg;
+  } else if constexpr (MASK) {
     bs = rp.row_seq[b];
     bq = rp.row_q[b];
 #pragma unroll
     for (int g = 0; g < NG; ++g) blk[g] = rp.blocked[((int64_t)b * n_heads + h) * NG + g];
     segp = rp.seg + (int64_t)bs * rp.ld_seg;
   }
-  const int len = min(lens[bs], max_len);
+  if constexpr (!TILE) len = min(lens[bs], max_len);
   const int crow = FUSE && rp.seq_ids ? rp.seq_ids[b] : bs;
   const int64_t base = ((int64_t)crow * n_heads + h) * (int64_t)max_len * D;
   const int64_t sbase = base / D;     // F8: the scale of row (crow, h, key) is Ks[sbase + key]
   const char* kp = (const char*)Kc + (base + dc * EPL) * EB;
   const char* vp = (const char*)Vc + (base + dc * EPL) * EB;
 
-  Wd q_raw[NG];
+  Wd q_raw[NQ];
   Raw k_new = {}, v_new = {};
   float ks_new = 1.f, vs_new = 1.f;
   int pos_new = -1;
@@ -194,13 +243,17 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
         rp.vs[sbase + pos_new] = vs_new;
       }
     }
+  } else if constexpr (TILE) {
+#pragma unroll
+    for (int x = 0; x < NQ; ++x)
+      q_raw[x] = rq[x] >= 0 ? *(const Wd*)(Q + (int64_t)rq[x] * ldq + (h * NG + x % NG) * D + dc * EPL) : Wd{};
   } else {
 #pragma unroll
     for (int g = 0; g < NG; ++g) q_raw[g] = *(const Wd*)(Q + (int64_t)bq * ldq + (h * NG + g) * D + dc * EPL);
   }
-  float q[NG][EPL], m[NG], l[NG], o[NG][EPL];
+  float q[NQ][EPL], m[NQ], l[NQ], o[NQ][EPL];
 #pragma unroll
-  for (int g = 0; g < NG; ++g) {
+  for (int g = 0; g < NQ; ++g) {
 #pragma unroll
     for (int t = 0; t < NW; ++t) {
       q[g][2 * t] = __uint_as_float(q_raw[g][t] << 16) * scale_log2e;
@@ -248,7 +301,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
 #pragma unroll
     for (int gk = 0; gk < UNR / G; ++gk) {
 #pragma unroll
-      for (int g = 0; g < NG; ++g) {
+      for (int g = 0; g < NQ; ++g) {
+        if constexpr (TILE) {
+          if (j0 + gk * G * 4 * KPW >= qlen[g]) continue;     // wave-uniform: every key of the group is past this state's end
+        }
         float s[G];
         bool ok[G];
 #pragma unroll
@@ -263,7 +319,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
           }
 #pragma unroll
           for (int x = 1; x < LPR; x <<= 1) d += __shfl_xor(d, x, 64);
-          ok[i] = j0 + u * 4 * KPW + sub < len;
+          ok[i] = j0 + u * 4 * KPW + sub < (TILE ? qlen[g] : len);
           if constexpr (MASK) ok[i] = ok[i] && !(blk[g] & sgr[u]);
           s[i] = ok[i] ? d : NEG_BIG;
         }
@@ -293,7 +349,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
   }
   const int stream = wave * KPW + sub;
 #pragma unroll
-  for (int g = 0; g < NG; ++g) {       // one head at a time through the one merge buffer
+  for (int g = 0; g < NQ; ++g) {       // one head (of one slot) at a time through the one merge buffer
     if (g) __syncthreads();            // the previous head's readers are done
 #pragma unroll
     for (int t = 0; t < EPL; ++t) sm[stream][dc * EPL + t] = o[g][t];
@@ -317,7 +373,11 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const unsigned short* 
       // F8: a NaN cache row (a non-finite appended k / v) makes L NaN, and the output of this (sequence, head) NaN; the bf16
       // kernel's L > 0 test would turn it into zeros.  Identical for every finite input.
       const bool live = F8 ? !(L <= 0.f) : L > 0.f;
-      O[(int64_t)bq * ldo + (h * NG + g) * D + d] = f32_to_bf16_bits(live ? acc / L : 0.f);
+      if constexpr (TILE) {
+        if (rq[g] >= 0) O[(int64_t)rq[g] * ldo + (h * NG + g % NG) * D + d] = f32_to_bf16_bits(live ? acc / L : 0.f);
+      } else {
+        O[(int64_t)bq * ldo + (h * NG + g) * D + d] = f32_to_bf16_bits(live ? acc / L : 0.f);
+      }
     }
   }
 }
@@ -334,15 +394,20 @@ struct DecodeArgs {
   void* O;
   int64_t ldo;
   const int32_t* lens;
-  int32_t rows;                 // grid rows: n_seqs, or the list entries of FORM_MASK
-  int32_t H, Hkv, D, max_len;   // query heads, heads of the cache (= H unless FORM_GQA / FORM_MASK)
+  int32_t rows;                 // grid rows: n_seqs, the list entries of FORM_MASK, or the tiles of FORM_CUT
+  int32_t H, Hkv, D, max_len;   // query heads, heads of the cache (= H unless FORM_GQA / FORM_MASK / FORM_CUT)
   float scale;
   void* stream;
-  DecodeMask tail = {};
+  DecodeCut tail = {};
+  int32_t tile_rows = 0;        // FORM_CUT: the slots per tile the caller built its tables for
 };
 // What an entry point's form has.  FORM_GQA: the entry point takes n_kv_heads (a masked call always does); FORM_EPL16: the bf16
-// reference of the fp8 lane mapping.
-enum : unsigned { FORM_F8 = 1, FORM_FUSE = 2, FORM_GQA = 4, FORM_MASK = 8, FORM_EPL16 = 16 };
+// reference of the fp8 lane mapping; FORM_CUT: row tiles (lens is NULL: every slot brings its own key count).
+enum : unsigned { FORM_F8 = 1, FORM_FUSE = 2, FORM_GQA = 4, FORM_MASK = 8, FORM_EPL16 = 16, FORM_CUT = 32 };
+
+// Slots per tile of FORM_CUT by group size G (checked: 1..8): R * G <= 4 online-softmax states next to UNR = 4 key rounds are
+// what the table above shows without scratch; from G = 3 on a tile is one row.
+constexpr int cut_tile_rows(int G) { return G == 1 ? 4 : G == 2 ? 2 : 1; }
 
 // The checks of every form, each condition once.  Which form tests what (x), G = H / Hkv:
 //                                                          bf16 epl16 fp8 | rope_bf16 rope_fp8 | gqa      | masked
@@ -357,23 +422,29 @@ enum : unsigned { FORM_F8 = 1, FORM_FUSE = 2, FORM_GQA = 4, FORM_MASK = 8, FORM_
 //   ldo % 8                                                  -    -    -  |    -         -     |  G > 1   |   -
 //   ld_seg >= max_len                                        -    -    -  |    -         -     |  -       |   x
 //   scale finite                                             -    -    -  |    -         -     |  -       |   x
+// FORM_CUT (icl_attn_cut_rows_bf16) tests what masked tests — rows = n_tiles; lens is not an operand, tile_seq and row_len are,
+// head_on may be NULL — and tile_rows == cut_tile_rows(G).
 // The gaps are carried over from when each form had checks of its own: no plain or fused form tests the width of O (the fused ones test that of qkv through the blocks)
 // or a finite scale, none but the grouped one ldo % 8 (O is written two bytes at a time).  Closing them changes what is refused.
 int attn_decode_check(const char* who, unsigned form, const DecodeArgs& a) {
-  const bool f8 = form & FORM_F8, fuse = form & FORM_FUSE, gqa = form & FORM_GQA, mask = form & FORM_MASK;
-  const DecodeMask& t = a.tail;
+  const bool f8 = form & FORM_F8, fuse = form & FORM_FUSE, gqa = form & FORM_GQA, cut = form & FORM_CUT, mask = (form & FORM_MASK) || cut;
+  const DecodeCut& t = a.tail;
   const auto al = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
   // the sizes first: an empty row list comes with NULL pointers, and is to be called an empty list
   ICL_CHECK_ARG(a.rows > 0 && a.rows <= 65535 && a.H > 0 && a.max_len > 0, "%s: bad sizes: %s=%d (1..65535), n_heads=%d, max_len=%d", who,
-                mask ? "n_rows" : "n_seqs", a.rows, a.H, a.max_len);
-  ICL_CHECK_ARG(a.Q && a.Kc && a.Vc && a.O && a.lens && (!f8 || (a.Ks && a.Vs)) && (!fuse || (t.cosT && t.sinT && t.pos)) &&
-                    (!mask || (t.seg && t.blocked && t.row_seq && t.row_q)), "%s: NULL pointer", who);
+                cut ? "n_tiles" : mask ? "n_rows" : "n_seqs", a.rows, a.H, a.max_len);
+  ICL_CHECK_ARG(a.Q && a.Kc && a.Vc && a.O && (cut || a.lens) && (!f8 || (a.Ks && a.Vs)) && (!fuse || (t.cosT && t.sinT && t.pos)) &&
+                    (!mask || (t.seg && t.blocked && t.row_q)) && (!mask || cut || t.row_seq) && (!cut || (t.tile_seq && t.row_len)),
+                "%s: NULL pointer", who);
   ICL_CHECK_ARG(a.D == 64 || a.D == 128, "%s: head_dim=%d (only 64 and 128)", who, a.D);
   if (gqa || mask) {
     ICL_CHECK_ARG(a.Hkv > 0 && a.Hkv <= 65535 && a.H % a.Hkv == 0, "%s: n_heads=%d is not a multiple of n_kv_heads=%d", who, a.H, a.Hkv);
     ICL_CHECK_ARG(a.H / a.Hkv <= 8, "%s: %d query heads per K/V head (G at most 8)", who, a.H / a.Hkv);
     ICL_CHECK_ARG(a.H == a.Hkv || a.D == 128, "%s: head_dim=%d (grouped-query attention: only 128)", who, a.D);
   }
+  if (cut)
+    ICL_CHECK_ARG(a.tile_rows == cut_tile_rows(a.H / a.Hkv), "%s: tile_rows=%d, the form's tiles hold %d rows (icl_attn_cut_tile_rows)", who,
+                  a.tile_rows, cut_tile_rows(a.H / a.Hkv));
   const int64_t cols = (int64_t)a.H * a.D;
   const bool grouped = gqa && a.H > a.Hkv;      // through the grouped entry point, G = 1 is the multi-head form under its conditions
   if (fuse)
@@ -393,10 +464,10 @@ int attn_decode_check(const char* who, unsigned form, const DecodeArgs& a) {
 }
 
 // One workgroup per (head of the cache, row).  The kernel's argument list, and for an unmasked form the DecodeRope part of the tail.
-template <int D, int UNR, bool FUSE, bool F8, int EPL, int NG, bool MASK>
+template <int D, int UNR, bool FUSE, bool F8, int EPL, int NG, bool MASK, int R = 0>
 void attn_decode_launch(const DecodeArgs& a) {
-  const typename DecodeTail<MASK>::T tail = a.tail;
-  hipLaunchKernelGGL((attn_decode_kernel<D, UNR, FUSE, F8, EPL, NG, MASK>), dim3(a.Hkv, a.rows), dim3(256), 0, (hipStream_t)a.stream,
+  const typename DecodeTail<MASK, R>::T tail = a.tail;
+  hipLaunchKernelGGL((attn_decode_kernel<D, UNR, FUSE, F8, EPL, NG, MASK, R>), dim3(a.Hkv, a.rows), dim3(256), 0, (hipStream_t)a.stream,
                      (const unsigned short*)a.Q, a.ldq, a.Kc, a.Vc, a.Ks, a.Vs, (unsigned short*)a.O, a.ldo, a.lens, a.Hkv, a.max_len,
                      a.scale * LOG2E, tail);
 }
@@ -426,12 +497,29 @@ void attn_decode_gqa(int G, const DecodeArgs& a) {
   }
 }
 
-// The one way from an entry point to the kernel: check, pick the instantiation <D, UNR, FUSE, F8, EPL, NG, MASK>, launch.
+// Row tiles (FORM_CUT): one workgroup per (K/V head, tile), ONE instantiation per (head_dim, G) whatever the grid — R =
+// cut_tile_rows(G) slots, UNR 4: the grouped table's for R * G = 3 .. 8 states.
+void attn_decode_cut(int G, const DecodeArgs& a) {
+  switch (G) {
+    case 1: return a.D == 64 ? attn_decode_launch<64, 4, false, false, 8, 1, true, cut_tile_rows(1)>(a)
+                             : attn_decode_launch<128, 4, false, false, 8, 1, true, cut_tile_rows(1)>(a);
+    case 2: return attn_decode_launch<128, 4, false, false, 8, 2, true, cut_tile_rows(2)>(a);
+    case 3: return attn_decode_launch<128, 4, false, false, 8, 3, true, 1>(a);
+    case 4: return attn_decode_launch<128, 4, false, false, 8, 4, true, 1>(a);
+    case 5: return attn_decode_launch<128, 4, false, false, 8, 5, true, 1>(a);
+    case 6: return attn_decode_launch<128, 4, false, false, 8, 6, true, 1>(a);
+    case 7: return attn_decode_launch<128, 4, false, false, 8, 7, true, 1>(a);
+    case 8: return attn_decode_launch<128, 4, false, false, 8, 8, true, 1>(a);
+  }
+}
+
+// The one way from an entry point to the kernel: check, pick the instantiation <D, UNR, FUSE, F8, EPL, NG, MASK, R>, launch.
 int attn_decode_run(const char* who, unsigned form, const DecodeArgs& a) {
   if (const int rc = attn_decode_check(who, form, a)) return rc;
   const int G = a.H / a.Hkv;
   const bool fuse = form & FORM_FUSE;
-  if (form & FORM_MASK) G > 1 ? attn_decode_gqa<true>(G, a) : attn_decode_mha<false, false, 8, true>(a);
+  if (form & FORM_CUT) attn_decode_cut(G, a);
+  else if (form & FORM_MASK) G > 1 ? attn_decode_gqa<true>(G, a) : attn_decode_mha<false, false, 8, true>(a);
   else if (G > 1) attn_decode_gqa<false>(G, a);
   else if (form & FORM_F8) fuse ? attn_decode_mha<true, true, 16>(a) : attn_decode_mha<false, true, 16>(a);
   else if (form & FORM_EPL16) attn_decode_mha<false, false, 16>(a);
@@ -478,8 +566,29 @@ extern "C" int icl_attn_decode_masked_bf16(const void* Q, int64_t ldq, const voi
                                            int32_t n_kv_heads, int32_t head_dim, int32_t max_len, float scale, void* stream) {
   DecodeArgs a = {Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, lens, n_rows, n_heads, n_kv_heads ? n_kv_heads : n_heads, head_dim, max_len,
                   scale, stream};
-  a.tail = {{}, seg, ld_seg, blocked, row_seq, row_q};
+  a.tail = {{{}, seg, ld_seg, blocked, row_seq, row_q}};
   return attn_decode_run("icl_attn_decode_masked_bf16", FORM_MASK, a);
+}
+
+// Attention cuts: the masked kernel over TILES of listed rows of one cache sequence, every slot under its own key count and mask.
+extern "C" int icl_attn_cut_tile_rows(int32_t n_heads, int32_t n_kv_heads, int32_t head_dim) {
+  const int Hkv = n_kv_heads ? n_kv_heads : n_heads;
+  if (n_heads <= 0 || Hkv <= 0 || n_heads % Hkv || n_heads / Hkv > 8 || (head_dim != 64 && head_dim != 128) ||
+      (n_heads != Hkv && head_dim != 128))
+    return -1;
+  return cut_tile_rows(n_heads / Hkv);
+}
+
+extern "C" int icl_attn_cut_rows_bf16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O, int64_t ldo,
+                                      const uint8_t* seg, int64_t ld_seg, const int32_t* tile_seq, const int32_t* row_q,
+                                      const int32_t* row_len, const uint32_t* blocked, const uint8_t* head_on, int32_t n_tiles,
+                                      int32_t tile_rows, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int32_t max_len,
+                                      float scale, void* stream) {
+  DecodeArgs a = {Q, ldq, Kc, Vc, nullptr, nullptr, O, ldo, nullptr, n_tiles, n_heads, n_kv_heads ? n_kv_heads : n_heads, head_dim,
+                  max_len, scale, stream};
+  a.tail = {{{}, seg, ld_seg, blocked, nullptr, row_q}, tile_seq, row_len, head_on};
+  a.tile_rows = tile_rows;
+  return attn_decode_run("icl_attn_cut_rows_bf16", FORM_CUT, a);
 }
 
 // The RoPE-fused forms: the tail names the caches again, writable, for the appended row.
@@ -488,7 +597,7 @@ extern "C" int icl_attn_decode_rope_bf16(const void* qkv, int64_t ld, int64_t k_
                                          void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs, int32_t n_heads,
                                          int32_t head_dim, int32_t max_len, float scale, void* stream) {
   DecodeArgs a = {qkv, ld, kc, vc, nullptr, nullptr, O, ldo, lens, n_seqs, n_heads, n_heads, head_dim, max_len, scale, stream};
-  a.tail = {{cosT, sinT, pos, seq_ids, kc, vc, nullptr, nullptr, k_off, v_off}};
+  a.tail = {{{cosT, sinT, pos, seq_ids, kc, vc, nullptr, nullptr, k_off, v_off}}};
   return attn_decode_run("icl_attn_decode_rope_bf16", FORM_FUSE, a);
 }
 
@@ -497,6 +606,6 @@ extern "C" int icl_attn_decode_rope_fp8(const void* qkv, int64_t ld, int64_t k_o
                                         float* kscale, float* vscale, void* O, int64_t ldo, const int32_t* lens, int32_t n_seqs,
                                         int32_t n_heads, int32_t head_dim, int32_t max_len, float scale, void* stream) {
   DecodeArgs a = {qkv, ld, kc, vc, kscale, vscale, O, ldo, lens, n_seqs, n_heads, n_heads, head_dim, max_len, scale, stream};
-  a.tail = {{cosT, sinT, pos, seq_ids, kc, vc, kscale, vscale, k_off, v_off}};
+  a.tail = {{{cosT, sinT, pos, seq_ids, kc, vc, kscale, vscale, k_off, v_off}}};
   return attn_decode_run("icl_attn_decode_rope_fp8", FORM_FUSE | FORM_F8, a);
 }

@@ -683,6 +683,52 @@ class CustomSALMONN(BaseModel):
                                     knockout=([self.piece_ids(s) for s in segs], blocked, layers, heads))
         return {"texts": self.decode_ids(res.tokens), "tokens": res.tokens, "first_logits": res.first_logits, "pieces": pieces}
 
+    def generate_cut(self, samples: Dict[str, Any], cuts, layers=None, heads=None, generated=None) -> Dict[str, Any]:
+        """Attention cuts between pieces of the prompt: generate while, in decoder layers ``layers`` (a half-open range, None: all)
+        and query heads ``heads`` (None: all), the positions of a query piece — interior prompt rows included, not only the deciding
+        ones — cannot read the keys of a key piece.  ``cuts``: pairs ``(query piece, key piece)`` in the vocabulary of
+        ``prompt_attention``'s ``pieces``, such as ``(("example", 2), ("example", 1))`` or ``(("text", 3), ("speech", 0))`` — one list
+        for all rows, or one list per row (an empty list leaves that row untouched).  ``generated``: the piece whose pairs the
+        generated positions query under (None: the piece of the prompt's last position).  A piece a row does not have, and more
+        than 32 pieces in a row, are ``ValueError``s naming the row, raised before anything is launched on the decoder
+        (``generate_knockout``'s rules).  Returns ``{"texts", "tokens": int64 [B, width] (CPU), "first_logits": f32 [B, V]
+        (device), "pieces"}``; generation knobs are read from the batch as ``generate_ids`` reads them (no beams)."""
+        samples = self._host_counts(samples)
+        constraint = self._label_constraint(samples)
+        speech_embeds, _, example_embeds, _ = self.get_speech_embeddings(samples)
+        num_examples = samples.get("num_examples", torch.zeros(len(samples["prompt"]), dtype=torch.long))
+        segs, speech, pieces = self._segments_and_pieces(speech_embeds, samples["prompt"], num_examples, example_embeds)
+        cuts = list(cuts)
+        is_piece = lambda x: isinstance(x, (tuple, list)) and len(x) == 2 and isinstance(x[0], str)
+        is_pair = lambda x: isinstance(x, (tuple, list)) and len(x) == 2 and is_piece(x[0]) and is_piece(x[1])
+        per_row = len(cuts) > 0 and not any(is_pair(x) for x in cuts)         # one list per row (of pairs, possibly empty)
+        if per_row and len(cuts) != len(pieces):
+            raise ValueError(f"{len(cuts)} cut lists for {len(pieces)} rows")
+
+        def piece_id(b, pc, piece):
+            piece = (str(piece[0]), int(piece[1]))
+            if piece not in pc:
+                raise ValueError(f"row {b}: the wrapped prompt has no piece {piece} (its pieces: {pc})")
+            return pc.index(piece)
+        pairs, gen = [], []
+        for b, pc in enumerate(pieces):
+            if len(pc) > self.MAX_PIECES:
+                raise ValueError(f"row {b}: {len(pc)} pieces in the wrapped prompt, cuts run between at most {self.MAX_PIECES}")
+            pairs.append([(piece_id(b, pc, q), piece_id(b, pc, k)) for q, k in (cuts[b] if per_row else cuts)])
+            if generated is not None:
+                gen.append(piece_id(b, pc, generated))
+        res = self.runtime.generate(segs, speech, max_new_tokens=int(samples.get("max_new_tokens", 10)),
+                                    eos_id=self.llama_tokenizer.eos_token_id, pad_id=self.llama_tokenizer.pad_token_id,
+                                    do_sample=bool(samples.get("do_sample", False)),
+                                    temperature=float(samples.get("temperature", 0.8)), top_p=float(samples.get("top_p", 0.9)),
+                                    top_k=int(self.hf_generation_defaults.get("top_k", 50)),
+                                    repetition_penalty=float(samples.get("repetition_penalty", 1.0)),
+                                    generator=samples.get("generator"), want_first_logits=True, overlong="drop",
+                                    num_beams=int(samples.get("num_beams", 1)), constraint=constraint,
+                                    cuts=dict(segments=[self.piece_ids(s) for s in segs], pairs=pairs, layers=layers, heads=heads,
+                                              generated=gen if generated is not None else None))
+        return {"texts": self.decode_ids(res.tokens), "tokens": res.tokens, "first_logits": res.first_logits, "pieces": pieces}
+
     def _generate_resid(self, samples: Dict[str, Any], **resid) -> Any:
         """``runtime.generate`` on the batch as ``generate_ids`` reads it (greedy, sampled or label-constrained; no beams), with
         the residual-stream arguments ``resid`` (``want_hidden`` / ``patch``) and the first-step logits."""

@@ -74,6 +74,10 @@ _SIGNATURES = {
     "icl_attn_decode_masked_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                             c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float,
                                             c_void_p]),
+    "icl_attn_cut_tile_rows": (c_int, [c_int32, c_int32, c_int32]),
+    "icl_attn_cut_rows_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                       c_float, c_void_p]),
     "icl_attn_decode_rope_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float,
                                           c_void_p]),
@@ -465,6 +469,34 @@ def attn_decode_masked(q, kcache, vcache, out, lens, seg, blocked, row_seq, row_
     return _attn_decode("icl_attn_decode_masked_bf16", q, out, lens, (kcache, vcache),
                         q, q.stride(0), kcache, vcache, out, out.stride(0), lens, seg, seg.stride(0), blocked, row_seq, row_q, n_rows,
                         n_heads, n_kv_heads, head_dim, max_len, scale)
+
+
+def attn_cut_tile_rows(n_heads: int, head_dim: int, n_kv_heads: int = 0) -> int:
+    """Rows per tile of ``attn_cut_rows`` for a form (icl_attn_cut_tile_rows): 4 multi-head, 2 at two query heads per K/V head,
+    1 from three on.  A host query, no launch; a form the kernel does not have is an ``IclError``."""
+    R = load_library().icl_attn_cut_tile_rows(n_heads, n_kv_heads, head_dim)
+    if R <= 0:
+        raise IclError(f"icl_attn_cut_tile_rows: no row-tile form for n_heads={n_heads}, n_kv_heads={n_kv_heads}, head_dim={head_dim}")
+    return R
+
+
+def attn_cut_rows(q, kcache, vcache, out, seg, tile_seq, row_q, row_len, blocked, n_heads: int, head_dim: int, max_len: int,
+                  scale: float, *, tile_rows: int, n_kv_heads: int = 0, head_on=None):
+    """Attention cuts between prompt segments (icl_attn_cut_rows_bf16): the masked decode kernel over TILES of ``tile_rows``
+    listed rows of one cache sequence.  Tile t works on cache sequence ``tile_seq[t]`` (int32 [n_tiles]); its slot e = t *
+    tile_rows + r reads the query at row ``row_q[e]`` (int32 [n_tiles * tile_rows]; < 0: an empty slot) of ``q`` (bf16, already
+    rotated), attends over the keys j < ``row_len[e]`` (int32) whose segment ``seg[tile_seq[t], j]`` (uint8 [n_seqs, >= max_len])
+    is not a bit of ``blocked[e]`` (int32, read as a u32 bit set; ids >= 32 are never blocked), and writes that row of ``out``.
+    ``head_on``: None, or uint8 [n_heads] — a query head that is off is not written.  Rows no slot lists are not written."""
+    assert seg.dtype == torch.uint8 and blocked.dtype == torch.int32 and tile_seq.dtype == torch.int32 and row_q.dtype == torch.int32
+    n_tiles = tile_seq.numel()
+    for t in (row_q, row_len, blocked):
+        assert t.is_contiguous() and t.numel() == n_tiles * tile_rows
+    assert tile_seq.is_contiguous() and seg.dim() == 2 and seg.stride(1) == 1 and seg.shape[0] == kcache.shape[0] == vcache.shape[0]
+    assert head_on is None or (head_on.dtype == torch.uint8 and head_on.is_contiguous() and head_on.numel() == n_heads)
+    return _attn_decode("icl_attn_cut_rows_bf16", q, out, row_len, (kcache, vcache),
+                        q, q.stride(0), kcache, vcache, out, out.stride(0), seg, seg.stride(0), tile_seq, row_q, row_len, blocked,
+                        head_on, n_tiles, tile_rows, n_heads, n_kv_heads, head_dim, max_len, scale)
 
 
 def attn_decode_rope(qkv, k_off: int, v_off: int, cos, sin, pos, seq_ids, kcache, vcache, out, lens, n_heads: int,

@@ -5,6 +5,9 @@
   residual capture / patching    a tensor, ``ResidPatch`` icl_resid_rows_f32            the row's residual stream, read and written
   head-output capture / patching a tensor, ``HeadPatch``  icl_head_rows_bf16            what single heads hand to o_proj, read and written
 
+and of ANY prompt row: attention cuts between prompt segments, ``Cuts`` (icl_attn_cut_rows_bf16; in the decode steps the knockout's
+icl_attn_decode_masked_bf16) — a query of one segment attends as if the keys of another were absent.
+
 Host validation (``check_*``), device state (``*_state``), re-slicing to a prefill chunk and to the kept rows of a drop, and
 ``Probes``, the one bundle handed between runtime/salmonn.py and runtime/engines.py.
 """
@@ -14,6 +17,7 @@ import math
 from dataclasses import dataclass, field, replace
 from typing import List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import binding as B
@@ -21,6 +25,8 @@ from .engines import F32, I32, Workspace, _i32
 
 MAX_READOUT_SEGMENTS = 32      # icl_attn_segmass_bf16: one thread per (head of a K/V group, segment)
 MAX_KNOCKOUT_SEGMENTS = 32     # icl_attn_decode_masked_bf16: one bit of a u32 per segment; ids >= 32 are never blocked
+MAX_CUT_SEGMENTS = 32          # icl_attn_cut_rows_bf16: the same bit set per listed row
+CUT_KEYS = ("segments", "pairs", "layers", "heads", "generated")
 IGNORE_SEGMENT = 255           # a segment id that is counted nowhere and never blocked, whatever n_seg is
 PATCH_KEYS = ("site", "vectors", "mode", "alpha", "rows", "steps")
 HEAD_PATCH_KEYS = ("heads", "vectors", "mode", "alpha", "rows", "steps")
@@ -183,6 +189,83 @@ class HeadPatch:
                     vec=self.vectors[:, p0:p1], mode=self.mode, alpha=self.alpha)
 
 
+@dataclass
+class Cuts:
+    """Attention cuts between prompt segments: in decoder layers ``layers[0] .. layers[1] - 1`` and the query heads that are on, a
+    query of segment s at ANY prompt position attends as if the keys of the segments K(s) cut for it were absent
+    (icl_attn_cut_rows_bf16 rewrites the listed rows of the attention output after the layer's ordinary attention launch).
+    ``entries[b]``: the listed positions of sequence b, ascending, and their u32 bit sets, two int64 arrays ``(positions, masks)``
+    — on the HOST: a prefill builds its tile tables from them (``tile_tables``), ``tile_rows`` rows of one sequence per tile.  ``seg`` uint8
+    [n_seqs, >= cache max_len]: the segment of every cache position, 255 past the prompt (generated positions are always
+    visible); ``head_on``: None (all heads) or uint8 [n_heads].  The decode steps' state, for the sequences whose generated rows
+    cut something (``gen_listed``, ascending; ``gen_row_seq``: the same on the device): ``gen_blocked`` int32 [n_listed,
+    n_heads], the knockout's operand of icl_attn_decode_masked_bf16.  ``seg``, ``head_on`` and the decode state live in
+    graph-visible workspace buffers refilled on every call, so ``uid`` — what a captured decode graph bakes in besides those
+    pointers: the number of sequences listed in the decode steps (a grid size) and the layer window — keys the decode graphs;
+    nothing of the prefill's tables reaches a decode graph."""
+    seg: torch.Tensor
+    entries: Tuple[Tuple[np.ndarray, np.ndarray], ...]
+    layers: Tuple[int, int]
+    n_layers: int
+    tile_rows: int
+    head_on: Optional[torch.Tensor] = None
+    gen_listed: Tuple[int, ...] = ()
+    gen_row_seq: Optional[torch.Tensor] = None
+    gen_blocked: Optional[torch.Tensor] = None
+
+    @property
+    def uid(self):
+        return ("cuts", len(self.gen_listed), self.layers[0], self.layers[1])
+
+    def rows(self, b0: int, b1: int) -> Optional["Cuts"]:
+        """The cuts of sequences b0 .. b1-1 (views; sequence ids relative to b0), for a prefill over that chunk of the batch
+        (``KVCache.rows``); None when the chunk lists no row.  The decode state stays behind: a prefill does not read it."""
+        if not any(len(pos) for pos, _ in self.entries[b0:b1]):
+            return None
+        return Cuts(self.seg[b0:b1], self.entries[b0:b1], self.layers, self.n_layers, self.tile_rows, self.head_on)
+
+    def covers(self, layer: int) -> bool:
+        return self.layers[0] <= layer < self.layers[1]
+
+    def tile_tables(self, seq_lens: List[int], cu_h: Optional[List[int]], last_only: bool, device, max_tiles: int = 65535):
+        """The tile tables of a prefill, one tuple (tile_seq, row_q, row_len, blocked) of int32 device tensors per launch (a
+        launch holds at most ``max_tiles`` tiles).  Entries ascend by (sequence, position) and a tile holds ``tile_rows``
+        consecutive entries of ONE sequence, so its row_lens are close; the tail of a sequence's last tile is empty slots (row_q
+        -1).  Position p of sequence b is row ``cu_h[b] + p`` of Q / O, or with ``cu_h`` None (gathered last rows) row b.
+        ``last_only``: only the sequences' last positions (the model's last layer, where no other row can influence anything)."""
+        R = self.tile_rows
+        tile_seq, row_q, row_len, blocked = [], [], [], []
+        for b, (pos, msk) in enumerate(self.entries):
+            if last_only:
+                keep = pos == seq_lens[b] - 1
+                pos, msk = pos[keep], msk[keep]
+            if not len(pos):
+                continue
+            n_tiles = -(-len(pos) // R)
+            pad = np.zeros(n_tiles * R - len(pos), dtype=np.int64)
+            tile_seq.append(np.full(n_tiles, b, dtype=np.int64))
+            row_q.append(np.concatenate([pos + cu_h[b] if cu_h is not None else np.full(len(pos), b, dtype=np.int64), pad - 1]))
+            row_len.append(np.concatenate([pos + 1, pad]))
+            blocked.append(np.concatenate([np.where(msk >= 1 << 31, msk - (1 << 32), msk), pad]))     # the u32 bit set in an int32
+        if not tile_seq:
+            return []
+        tile_seq, row_q, row_len, blocked = (np.concatenate(x) for x in (tile_seq, row_q, row_len, blocked))
+        tile_seq, row_q, row_len, blocked = (x.astype(np.int32) for x in (tile_seq, row_q, row_len, blocked))
+        return [(_i32(tile_seq[i:i + max_tiles], device),) + tuple(_i32(x[i * R:(i + max_tiles) * R], device) for x in (row_q, row_len, blocked))
+                for i in range(0, len(tile_seq), max_tiles)]
+
+    def launch(self, tables, q: torch.Tensor, att: torch.Tensor, kc, vc, cfg, max_len: int) -> None:
+        """Rewrite the rows of ``att`` that ``tables`` list from the same rows of ``q`` (rotated) over the bf16 cache."""
+        for tile_seq, row_q, row_len, blocked in tables:
+            B.attn_cut_rows(q, kc, vc, att, self.seg, tile_seq, row_q, row_len, blocked, cfg.n_heads, cfg.head_dim, max_len,
+                            cfg.head_dim ** -0.5, tile_rows=self.tile_rows, n_kv_heads=cfg.kv_heads, head_on=self.head_on)
+
+    def launch_step(self, q: torch.Tensor, att: torch.Tensor, kc, vc, lens: torch.Tensor, cfg, max_len: int) -> None:
+        """A decode step: the generated rows of the listed sequences under K(generated), the knockout's launch."""
+        B.attn_decode_masked(q, kc, vc, att, lens, self.seg, self.gen_blocked, self.gen_row_seq, self.gen_row_seq, cfg.n_heads,
+                             cfg.head_dim, max_len, cfg.head_dim ** -0.5, n_kv_heads=cfg.kv_heads)
+
+
 # ================================================================================================
 # The bundle the layers hand to each other
 # ================================================================================================
@@ -199,6 +282,7 @@ class Probes:
     patch: Optional[ResidPatch] = None
     head_capture: Optional[torch.Tensor] = None
     head_patch: Optional[HeadPatch] = None
+    cuts: Optional[Cuts] = None
     # host tables of the prefill in progress (``start_prefill``), all int32 on the device: the sequences' last packed rows, the
     # prompt lengths as the masked launch's key counts, the last packed rows of the knockout's, of the patch's and of the head
     # patch's listed sequences
@@ -207,10 +291,14 @@ class Probes:
     _ko_last: Optional[torch.Tensor] = field(default=None, init=False, repr=False)
     _pt_last: Optional[torch.Tensor] = field(default=None, init=False, repr=False)
     _hp_last: Optional[torch.Tensor] = field(default=None, init=False, repr=False)
+    # ... and what the cuts' tile tables are built from and kept in: (prompt lengths, first packed rows), tables by (last rows
+    # only, packed rows)
+    _ct_prefill: Optional[tuple] = field(default=None, init=False, repr=False)
+    _ct_tables: dict = field(default_factory=dict, init=False, repr=False)
 
     def _or_none(self) -> Optional["Probes"]:
         return None if all(p is None for p in (self.readout, self.knockout, self.capture, self.patch, self.head_capture,
-                                               self.head_patch)) else self
+                                               self.head_patch, self.cuts)) else self
 
     def rows(self, b0: int, b1: int) -> Optional["Probes"]:
         """The bundle of a prefill over sequences b0 .. b1-1.  A probe that lists no row of the chunk is absent from it, and a
@@ -220,18 +308,21 @@ class Probes:
                       None if self.capture is None else self.capture[b0:b1],
                       None if self.patch is None else self.patch.rows(b0, b1),
                       None if self.head_capture is None else self.head_capture[b0:b1],
-                      None if self.head_patch is None else self.head_patch.rows(b0, b1))._or_none()
+                      None if self.head_patch is None else self.head_patch.rows(b0, b1),
+                      None if self.cuts is None else self.cuts.rows(b0, b1))._or_none()
 
     def decode_steps(self) -> Optional["Probes"]:
-        """The bundle of the decode steps: the knockout, and a patch and a head patch of every step; None when the steps are the
-        plain ones."""
+        """The bundle of the decode steps: the knockout, a patch and a head patch of every step, and cuts whose generated rows
+        cut something; None when the steps are the plain ones."""
         return Probes(knockout=self.knockout, patch=self.patch if self.patch is not None and self.patch.steps == "all" else None,
-                      head_patch=self.head_patch if self.head_patch is not None and self.head_patch.steps == "all" else None)._or_none()
+                      head_patch=self.head_patch if self.head_patch is not None and self.head_patch.steps == "all" else None,
+                      cuts=self.cuts if self.cuts is not None and self.cuts.gen_listed else None)._or_none()
 
     def graph_key(self) -> tuple:
         """What a captured decode loop bakes in of its probes besides pointers: appended to the graph key of the plain call."""
         every_step = (self.knockout, self.patch if self.patch is not None and self.patch.steps == "all" else None,
-                      self.head_patch if self.head_patch is not None and self.head_patch.steps == "all" else None)
+                      self.head_patch if self.head_patch is not None and self.head_patch.steps == "all" else None,
+                      self.cuts if self.cuts is not None and self.cuts.gen_listed else None)
         return tuple(p.uid for p in every_step if p is not None)
 
     # ---- a prefill: preconditions and host tables, once per call of LlamaHIP.prefill ----
@@ -242,6 +333,8 @@ class Probes:
         assert self.knockout is None or (last and bf16), "attention knockout rewrites the last rows from a bf16 KV cache"
         assert (self.capture is None and self.patch is None) or last, "residual capture / patching works on the last rows (last_rows_only)"
         assert (self.head_capture is None and self.head_patch is None) or last, "head capture / patching works on the last rows (last_rows_only)"
+        assert self.cuts is None or (last and bf16), "attention cuts rewrite the listed rows from a bf16 KV cache (last_rows_only)"
+        self._ct_prefill, self._ct_tables = (list(seq_lens), list(cu_h)), {}
         ko, pt, hp = self.knockout, self.patch, self.head_patch
         self._last = last_idx
         self._key_counts = None if ko is None else _i32(seq_lens, last_idx.device)
@@ -282,9 +375,14 @@ class Probes:
         a head patch with a selected head in this layer rewrites those heads in the rows of its listed sequences.  One launch
         does both when the patch lists every sequence; a patch of some sequences next to a capture of all is a capture launch
         and then a patch launch (``residual_site``'s rule).  A layer with neither launches nothing."""
-        ko = self.knockout
+        ko, ct = self.knockout, self.cuts
         if ko is not None and ko.covers(layer):
             ko.launch(q, att, self._ko_last if packed else ko.row_seq, kc, vc, self._key_counts if lens is None else lens, cfg, max_len)
+        if ct is not None and ct.covers(layer):
+            if lens is not None:
+                ct.launch_step(q, att, kc, vc, lens, cfg, max_len)
+            else:
+                ct.launch(self._cut_tables(layer == ct.n_layers - 1, packed, att.device), q, att, kc, vc, cfg, max_len)
         cap = None if self.head_capture is None else self.head_capture[:, layer].flatten(1)
         hp = self.head_patch if self.head_patch is not None and self.head_patch.pairs(layer) is not None else None
         if cap is not None:
@@ -296,11 +394,22 @@ class Probes:
         if hp is not None:
             hp.launch(layer, att, self._hp_last if packed else hp.row_seq, cfg)
 
+    def _cut_tables(self, last_only: bool, packed: bool, device):
+        """The cuts' tile tables of the prefill in progress, built once per (last rows only, packed rows).  In the model's last
+        layer only the sequences' last rows can influence anything, so only they are launched — exact, not an approximation;
+        where that layer is trimmed (``packed`` False) row b of q / att is sequence b's last row."""
+        key = (last_only, packed)
+        if key not in self._ct_tables:
+            seq_lens, cu_h = self._ct_prefill
+            assert packed or last_only, "gathered rows hold the sequences' last rows only"
+            self._ct_tables[key] = self.cuts.tile_tables(seq_lens, cu_h if packed else None, last_only, device)
+        return self._ct_tables[key]
+
     def masks_attention(self, cache) -> bool:
-        """Does a knockout rewrite rows of this decode step's attention output?  It then needs q rotated in place (the
-        two-launch RoPE + attention form) and a bf16 cache."""
-        assert self.knockout is None or cache.dtype == "bf16", "attention knockout reads a bf16 KV cache"
-        return self.knockout is not None
+        """Does a knockout, or do cuts, rewrite rows of this decode step's attention output?  It then needs q rotated in place
+        (the two-launch RoPE + attention form) and a bf16 cache."""
+        assert (self.knockout is None and self.cuts is None) or cache.dtype == "bf16", "attention knockout / cuts read a bf16 KV cache"
+        return self.knockout is not None or self.cuts is not None
 
 
 # ================================================================================================
@@ -425,6 +534,137 @@ def knockout_state(ws: Workspace, cfg, knockout, max_len: int) -> Knockout:
     blk_d.copy_(torch.tensor(bits, dtype=I32), non_blocking=True)
     rows_d.copy_(torch.tensor(listed, dtype=I32), non_blocking=True)
     return Knockout(seg_d, blk_d, rows_d, listed, layers)
+
+
+def _cut_pairs(pairs, n_prompts: int):
+    """``pairs`` of a ``cuts`` dict as one {query segment: u32 bit set of key segments} per prompt: one list of (q_seg, k_seg)
+    for all prompts, or one such list per prompt."""
+    def one(lst, where):
+        K = {}
+        try:
+            lst = [(int(a), int(b)) for a, b in lst]
+        except (TypeError, ValueError):
+            raise ValueError(f"cuts: {where} must be a list of (q_seg, k_seg) pairs, not {lst!r}") from None
+        for a, b in lst:
+            if not (0 <= a < MAX_CUT_SEGMENTS and 0 <= b < MAX_CUT_SEGMENTS):
+                raise ValueError(f"cuts: {where} holds the pair ({a}, {b}): both segment ids of a pair are 0..{MAX_CUT_SEGMENTS - 1}")
+            K[a] = K.get(a, 0) | (1 << b)
+        return K
+    try:
+        items = list(pairs)
+    except TypeError:
+        raise ValueError(f"cuts: pairs must be a list of (q_seg, k_seg) pairs, or one such list per prompt, not {pairs!r}") from None
+    is_int = lambda x: isinstance(x, int) and not isinstance(x, bool)
+    if all(isinstance(e, (tuple, list)) and len(e) == 2 and is_int(e[0]) and is_int(e[1]) for e in items):
+        return [one(items, "pairs")] * n_prompts
+    if len(items) != n_prompts:
+        raise ValueError(f"cuts: pairs is neither one list of (q_seg, k_seg) pairs nor one list per prompt ({len(items)} lists for "
+                         f"{n_prompts} prompts)")
+    return [one(lst, f"pairs[{b}]") for b, lst in enumerate(items)]
+
+
+def check_cuts(cuts, cfg, kv_dtype: str, plens: List[int], num_beams: int, knockout=None, patch=None, head_patch=None):
+    """Host validation of ``generate(cuts=...)``: everything is a ``ValueError`` raised before any launch.  Returns a dict —
+    the arguments in one form (``segments`` as int64 arrays, ``pairs`` one list per prompt, ``generated`` one id per prompt,
+    ``layers`` (l0, l1), ``heads`` a tuple or None: itself a valid ``cuts``) and what follows from them: ``entries[b]`` the listed
+    positions of prompt b and their bit sets K(seg[p]), two int64 arrays, ``gen[b]`` the bit set of prompt b's generated rows (0:
+    untouched) — or None when no row is listed and no generated row cuts anything: the call is then the plain one.
+
+    Position p of prompt b is listed iff at least one key j <= p has seg[j] in K(seg[p])."""
+    if not isinstance(cuts, dict):
+        raise ValueError(f"cuts must be a dict with the keys {CUT_KEYS}")
+    unknown = set(cuts) - set(CUT_KEYS)
+    if unknown or "segments" not in cuts or "pairs" not in cuts:
+        raise ValueError(f"cuts holds 'segments' and 'pairs', and optionally 'layers', 'heads' and 'generated' (unknown keys: {sorted(unknown)})")
+    segments, n = cuts["segments"], len(plens)
+    if len(segments) != n:
+        raise ValueError(f"cuts: {len(segments)} segment lists for {n} prompts")
+    segs = []
+    for b, (sg, m) in enumerate(zip(segments, plens)):
+        try:
+            sg = np.asarray(sg.cpu() if isinstance(sg, torch.Tensor) else sg).astype(np.int64).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError(f"cuts: segments[{b}] must be a list of segment ids") from None
+        _check_segments(b, len(sg), m, int(sg.min()) if len(sg) else 0, int(sg.max()) if len(sg) else 0, "cuts: ",
+                        f"ids >= {MAX_CUT_SEGMENTS} are never cut")
+        segs.append(sg)
+    Ks = _cut_pairs(cuts["pairs"], n)
+    layers, heads, generated = cuts.get("layers"), cuts.get("heads"), cuts.get("generated")
+    if layers is None:
+        layers = (0, cfg.n_layers)
+    try:
+        l0, l1 = (int(x) for x in layers)
+    except (TypeError, ValueError):
+        raise ValueError(f"cuts: layers must be a half-open range (l0, l1), not {layers!r}") from None
+    if not 0 <= l0 < l1 <= cfg.n_layers:
+        raise ValueError(f"cuts: layer window ({l0}, {l1}) must be a non-empty range inside [0, {cfg.n_layers}]")
+    if heads is not None:
+        try:
+            heads = tuple(sorted({int(x) for x in heads}))
+        except (TypeError, ValueError):
+            raise ValueError(f"cuts: heads must be None or a list of query-head indices, not {cuts['heads']!r}") from None
+        if not heads or heads[0] < 0 or heads[-1] >= cfg.n_heads:
+            raise ValueError(f"cuts: head indices {list(heads)} must be a non-empty subset of 0..{cfg.n_heads - 1}")
+    if generated is None:
+        gen_ids = [int(sg[-1]) if len(sg) else IGNORE_SEGMENT for sg in segs]
+    else:
+        try:
+            gen_ids = [int(generated)] * n if isinstance(generated, int) and not isinstance(generated, bool) else [int(x) for x in generated]
+        except (TypeError, ValueError):
+            raise ValueError(f"cuts: generated must be None, a segment id or one id per prompt, not {generated!r}") from None
+        if len(gen_ids) != n or not all(0 <= g <= 255 for g in gen_ids):
+            raise ValueError(f"cuts: generated = {generated!r}: one segment id 0..255 for all prompts, or one per prompt ({n})")
+    entries, gen = [], []
+    for b, (sg, K) in enumerate(zip(segs, Ks)):
+        low = sg < MAX_CUT_SEGMENTS
+        listed, masks = np.zeros(len(sg), dtype=bool), np.zeros(len(sg), dtype=np.int64)
+        for s, m in K.items():
+            cut = np.cumsum(low & ((m >> np.where(low, sg, 0)) & 1 == 1))        # keys j <= p that segment s does not read
+            mine = (sg == s) & (cut > 0)
+            blind = mine & (cut == np.arange(1, len(sg) + 1))
+            if blind.any():
+                raise ValueError(f"cuts: prompt {b}, position {int(np.argmax(blind))} (segment {s}): the cut segments "
+                                 f"{[g for g in range(MAX_CUT_SEGMENTS) if (m >> g) & 1]} cover every key it could read")
+            listed |= mine
+            masks[mine] = m
+        entries.append((np.nonzero(listed)[0], masks[listed]))
+        seen = sum(1 << int(g) for g in np.unique(sg[low]))
+        gen.append(K.get(gen_ids[b], 0) & seen)       # a key segment the prompt does not hold is no cut
+    if not any(len(pos) for pos, _ in entries) and not any(gen):
+        return None
+    _need_bf16_kv("cuts", kv_dtype)
+    if num_beams != 1:
+        raise ValueError("cuts run with greedy, sampled and label-constrained decoding, not with beams (num_beams > 1)")
+    if knockout is not None or patch is not None or head_patch is not None:
+        raise ValueError("cuts together with knockout, patch or head_patch is not supported")
+    pairs = [[(a, g) for a, m in sorted(K.items()) for g in range(MAX_CUT_SEGMENTS) if (m >> g) & 1] for K in Ks]
+    return dict(segments=segs, pairs=pairs, generated=gen_ids, entries=tuple(entries), gen=gen, layers=(l0, l1), heads=heads)
+
+
+def cuts_state(ws: Workspace, cfg, cuts, max_len: int) -> Cuts:
+    """The validated cuts: the per-sequence host lists of listed positions and bit sets, and on the device, in graph-visible
+    workspace buffers refilled on every call, the segment table padded to the cache length, the head switch, and the decode
+    steps' state for the sequences whose generated rows cut something (the knockout's operands)."""
+    heads, gen = cuts["heads"], cuts["gen"]
+    seg_d = _segment_table(ws, "gen_ct_seg", [sg.astype(np.uint8) for sg in cuts["segments"]], max_len)
+    head_on = None
+    if heads is not None and len(heads) < cfg.n_heads:
+        head_on = ws.get("gen_ct_heads", (cfg.n_heads,), torch.uint8)
+        head_on.copy_(torch.tensor([int(h in heads) for h in range(cfg.n_heads)], dtype=torch.uint8), non_blocking=True)
+    R = B.load_library().icl_attn_cut_tile_rows(cfg.n_heads, cfg.kv_heads, cfg.head_dim)      # a host query of the library, no launch
+    if R <= 0:
+        raise ValueError(f"cuts: no row-tile attention form for n_heads={cfg.n_heads}, n_kv_heads={cfg.kv_heads}, head_dim={cfg.head_dim}")
+    state = Cuts(seg_d, cuts["entries"], cuts["layers"], cfg.n_layers, R, head_on)
+    listed = tuple(b for b, m in enumerate(gen) if m)
+    if listed:
+        on = set(range(cfg.n_heads) if heads is None else heads)
+        bits = [[(gen[b] - (1 << 32) if gen[b] >= (1 << 31) else gen[b]) if h in on else 0 for h in range(cfg.n_heads)] for b in listed]
+        state.gen_listed = listed
+        state.gen_blocked = ws.get("gen_ct_blocked", (len(listed), cfg.n_heads), I32)
+        state.gen_row_seq = ws.get("gen_ct_rows", (len(listed),), I32)
+        state.gen_blocked.copy_(torch.tensor(bits, dtype=I32), non_blocking=True)
+        state.gen_row_seq.copy_(torch.tensor(listed, dtype=I32), non_blocking=True)
+    return state
 
 
 def _patch_options(d: dict, n_prompts: int, what: str):
@@ -565,6 +805,14 @@ def head_patch_state(ws: Workspace, cfg, hp) -> HeadPatch:
     heads_d.copy_(torch.tensor([pairs[i][1] for i in order], dtype=I32), non_blocking=True)
     rows_d.copy_(torch.tensor(rows, dtype=I32), non_blocking=True)
     return HeadPatch(vec_d, heads_d, rows_d, tuple(rows), tuple(layers), hp["mode"], hp["alpha"], hp["steps"])
+
+
+def keep_cut_rows(cuts, keep: List[int]):
+    """``overlong="drop"``: validated cuts as the ``cuts`` argument of the call over the prompts ``keep``."""
+    if cuts is None:
+        return None
+    return dict(segments=[cuts["segments"][b] for b in keep], pairs=[cuts["pairs"][b] for b in keep], layers=cuts["layers"],
+                heads=cuts["heads"], generated=[cuts["generated"][b] for b in keep])
 
 
 def keep_rows(knockout, patch, keep: List[int], head_patch=None):

@@ -264,7 +264,8 @@ class CausalLMRuntimeMixin:
                  top_k: int = 50, repetition_penalty: float = 1.0, generator: Optional[torch.Generator] = None,
                  sample_debug=None, want_step_logits: bool = False, overlong: str = "raise", num_beams: int = 1,
                  length_penalty: float = 1.0, beam_debug: Optional[dict] = None, constraint=None,
-                 knockout=None, want_hidden: bool = False, patch=None, want_heads: bool = False, head_patch=None) -> GenerateResult:
+                 knockout=None, want_hidden: bool = False, patch=None, want_heads: bool = False, head_patch=None,
+                 cuts=None) -> GenerateResult:
         """Greedy search with HF ``generate(inputs_embeds=…)`` semantics (models/custom_salmon.py:704-720): returns only
         the new tokens; a row that has emitted EOS is filled with pad; the width is that of the longest row
         (``min_length`` is a no-op with inputs_embeds).  All steps are enqueued without a host sync; the
@@ -331,7 +332,24 @@ class CausalLMRuntimeMixin:
         not selected and rows not listed keep their bits.  Works with every tail above, both KV dtypes and both weight dtypes,
         grouped-query and QK-norm decoders.  ``ValueError`` before any launch: unknown keys, a pair outside [0, n_layers) x [0,
         n_heads) or given twice, vectors of the wrong shape or dtype, a bad mode or steps, a non-finite alpha, a duplicate or
-        out-of-range row, beams (also for ``want_heads``), ``head_patch`` together with ``knockout`` or with ``patch``."""
+        out-of-range row, beams (also for ``want_heads``), ``head_patch`` together with ``knockout`` or with ``patch``.
+
+        ``cuts`` = a dict ``segments``, ``pairs``, and optionally ``layers``, ``heads``, ``generated``: opt-in attention cuts
+        between prompt segments, the edges of an information-flow study whose QUERY is an interior prompt row.  ``segments`` as
+        for the knockout; ``pairs``: one list of ``(q_seg, k_seg)`` (both 0..31) for all prompts, or one list per prompt;
+        ``layers`` / ``heads`` as for the knockout.  In those layers and heads a query at prompt position p whose segment is q_seg
+        attends as if every key j <= p of segment k_seg were absent — transformers' 4-D additive mask with -inf at row i, column
+        j where j > i or seg[j] is cut for seg[i].  A generated row reads every generated key and queries under the pairs of
+        ``generated`` (a segment id per prompt or one for all; None: the segment of the prompt's last position; an id >= 32 or
+        one without pairs leaves the generated rows, the decode steps and their graph key the plain ones).  Position p is
+        LISTED iff a key it could read is cut: one more launch (icl_attn_cut_rows_bf16) per windowed layer and prefill chunk
+        rewrites the listed rows of the attention output from the rotated q and the bf16 cache, tiles of rows of one sequence
+        sharing one pass over its K / V; rows not listed keep their bits, and cuts that list no row are no cuts.  In the
+        model's last layer only the sequences' last rows are launched (no other row of that layer can influence anything:
+        exact).  The decode steps use the knockout's launch.  Works with every tail above, ``want_hidden`` / ``want_heads``,
+        grouped-query and QK-norm decoders.  ``ValueError`` before any launch: unknown keys, a segment list of the wrong number
+        or length, ids outside 0..255, a pair id outside 0..31, a bad ``layers``, ``heads`` or ``generated``, beams, the FP8 KV
+        cache, ``cuts`` together with ``knockout``, ``patch`` or ``head_patch``, a listed row left without a visible key."""
         args = {k: v for k, v in locals().items() if k not in ("self", "prompts", "speech")}   # the keyword arguments, as given
         c, ws = self.lm_cfg, self.ws
         # ---- 1. validate: every caller error is raised here, before anything is launched
@@ -348,6 +366,8 @@ class CausalLMRuntimeMixin:
             patch = args["patch"] = P.check_patch(patch, c, len(plens), num_beams, knockout)     # None: an empty row list
         if head_patch is not None:
             head_patch = args["head_patch"] = P.check_head_patch(head_patch, c, len(plens), num_beams, knockout, patch)
+        if cuts is not None:
+            cuts = args["cuts"] = P.check_cuts(cuts, c, self.kv_dtype, plens, num_beams, knockout, patch, head_patch)   # None: no row listed
         if want_heads and num_beams != 1:
             raise ValueError("want_heads runs with greedy, sampled and label-constrained decoding, not with beams (num_beams > 1)")
         if want_hidden and num_beams != 1:
@@ -388,6 +408,7 @@ class CausalLMRuntimeMixin:
             if constraint is not None:
                 args["constraint"] = (constraint[0], [constraint[1][b] for b in keep])
             args["knockout"], args["patch"], args["head_patch"] = P.keep_rows(knockout, patch, keep, head_patch)
+            args["cuts"] = P.keep_cut_rows(cuts, keep)
             return _undrop(self.generate([prompts[b] for b in keep], speech, **args), keep, bad, len(plens), pad)
         # ---- 3. beams
         if num_beams != 1:
@@ -406,7 +427,8 @@ class CausalLMRuntimeMixin:
         head_out = ws.get("gen_head_out", (Bn, c.n_layers, c.n_heads, c.head_dim), BF16) if want_heads else None
         probes = P.Probes(knockout=None if knockout is None else P.knockout_state(ws, c, knockout, max_len), capture=hidden,
                           patch=None if patch is None else P.patch_state(ws, c, patch),      # (never both a knockout and a patch)
-                          head_capture=head_out, head_patch=None if head_patch is None else P.head_patch_state(ws, c, head_patch))
+                          head_capture=head_out, head_patch=None if head_patch is None else P.head_patch_state(ws, c, head_patch),
+                          cuts=None if cuts is None else P.cuts_state(ws, c, cuts, max_len))
         logits = self._prefill_logits(h, lens, cache, ws.get("gen_last", (Bn, c.hidden), F32), probes=probes)
         first = logits.clone() if want_first_logits else None
         trace = ws.get("gen_logits_trace", (max_new_tokens, Bn, c.vocab), F32) if want_step_logits else None

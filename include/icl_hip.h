@@ -269,6 +269,31 @@ int icl_attn_decode_masked_bf16(const void* Q, int64_t ldq, const void* Kc, cons
                                 const int32_t* row_seq, const int32_t* row_q, int32_t n_rows, int32_t n_heads, int32_t n_kv_heads,
                                 int32_t head_dim, int32_t max_len, float scale, void* stream);
 
+/* ---- attention cuts between prompt segments: the masked kernel over TILES of listed rows of one cache sequence ----
+ * The knockout above rewrites one row per sequence; an edge whose QUERY is an interior prompt row ("the label positions may not
+ * read their demonstration's text") lists hundreds.  A tile t (0 <= t < n_tiles) holds tile_rows = R slots, all of cache
+ * sequence tile_seq[t]; slot e = t * R + r reads the query (bf16, already rotated) at row row_q[e] of Q and writes row row_q[e] of
+ * O (row_q[e] < 0: an empty slot, nothing read or written).  One workgroup per (K/V head, tile) walks keys 0 .. max row_len of its
+ * live slots - 1 ONCE for its R slots (and the G query heads of the group):
+ *   key j counts for slot e iff j < row_len[e] (its query's position + 1: the causal bound) and not (seg_j < 32 and bit seg_j of
+ *   blocked[e]); seg[tile_seq[t] * ld_seg + j] is the segment of key j, ids >= 32 are never blocked.
+ *   head_on  u8 [n_heads] or NULL (all): a query head that is off is NOT written; a K/V group whose heads are all off does nothing.
+ * The softmax runs over the keys that count, in the stream order of the decode kernels; a live slot without a key that counts
+ * writes zeros.  R is a property of the form — icl_attn_cut_tile_rows: 4 for multi-head (head_dim 64 / 128), 2 for G = 2, 1 for
+ * G = 3 .. 8 (head_dim 128), -1 for a form the kernel does not have — and one instantiation serves a form whatever n_tiles is: a
+ * slot's output bits do not depend on its slot, its companions or the grid.  Rows of one tile should be close in row_len (the
+ * tile streams up to its longest); row_q / tile_seq values must be rows of Q / O and sequences of the cache (the caller's duty).
+ * ICL_EINVAL (before any launch, naming the argument): a NULL pointer but head_on, n_tiles outside 1..65535, tile_rows not the
+ * form's R, head_dim not 64 / 128, n_kv_heads not dividing n_heads, G > 8, G > 1 at head_dim 64, ld_seg < max_len, ldq / ldo <
+ * n_heads * head_dim, misaligned Q / Kc / Vc (16 B; ldq % 8) or blocked (4 B), a scale that is not finite.
+ */
+int icl_attn_cut_tile_rows(int32_t n_heads, int32_t n_kv_heads /* 0 = n_heads */, int32_t head_dim);
+int icl_attn_cut_rows_bf16(const void* Q, int64_t ldq, const void* Kc, const void* Vc, void* O, int64_t ldo,
+                           const uint8_t* seg, int64_t ld_seg, const int32_t* tile_seq, const int32_t* row_q,
+                           const int32_t* row_len, const uint32_t* blocked, const uint8_t* head_on, int32_t n_tiles,
+                           int32_t tile_rows, int32_t n_heads, int32_t n_kv_heads /* 0 = n_heads */, int32_t head_dim,
+                           int32_t max_len, float scale, void* stream);
+
 /* ---- K11: the decode step's RoPE + KV-cache append + attention as ONE launch --------------------
  * icl_rope_kv_bf16 (M = n_seqs rows, one new position each) followed by icl_attn_decode_bf16, fused: qkv bf16 [n_seqs][ld] holds
  * the QKV projection's raw q | k | v row of every sequence (column blocks at 0 | k_off | v_off, n_heads*head_dim wide);
