@@ -587,6 +587,20 @@ class CustomSALMONN(BaseModel):
             samples = dict(samples, num_examples=ne.cpu())
         return samples
 
+    def _generate(self, samples: Dict[str, Any], segs, speech, constraint, want_first_logits: bool = True, **extra):
+        """``runtime.generate`` over wrapped prompts with the generation knobs of the batch and their defaults as the reference
+        reads them (:708-715): min_length is a no-op with inputs_embeds and length_penalty only acts on beams (num_beams > 1: HF
+        beam search, early_stopping at its default False).  ``extra``: the probe arguments of the caller."""
+        return self.runtime.generate(segs, speech, max_new_tokens=int(samples.get("max_new_tokens", 10)),
+                                     eos_id=self.llama_tokenizer.eos_token_id, pad_id=self.llama_tokenizer.pad_token_id,
+                                     do_sample=bool(samples.get("do_sample", False)),
+                                     temperature=float(samples.get("temperature", 0.8)), top_p=float(samples.get("top_p", 0.9)),
+                                     top_k=int(self.hf_generation_defaults.get("top_k", 50)),   # not a key the reference reads (:705-715)
+                                     repetition_penalty=float(samples.get("repetition_penalty", 1.0)),
+                                     generator=samples.get("generator"), want_first_logits=want_first_logits,
+                                     overlong="drop", num_beams=int(samples.get("num_beams", 1)),
+                                     length_penalty=float(samples.get("length_penalty", 1.0)), constraint=constraint, **extra)
+
     def generate_ids(self, samples: Dict[str, Any], want_first_logits: bool = False):
         """The arithmetic half of ``generate_output``: batch dict -> ``GenerateResult`` (new token ids int64 [B, width] with HF's
         EOS / pad / width rules, and the first-step logits f32 [B, V] on request).  The data-parallel CLI gathers these as
@@ -599,17 +613,7 @@ class CustomSALMONN(BaseModel):
         num_examples = samples.get("num_examples", torch.zeros(len(samples["prompt"]), dtype=torch.long))
         segs, speech = self._segments(speech_embeds, samples["prompt"], num_examples, example_embeds)
         t2 = time.perf_counter()
-        # generation knobs and their defaults as the reference reads them (:708-715); min_length is a no-op with inputs_embeds
-        # and length_penalty only acts on beams (num_beams > 1: HF beam search, early_stopping at its default False)
-        res = self.runtime.generate(segs, speech, max_new_tokens=int(samples.get("max_new_tokens", 10)),
-                                    eos_id=self.llama_tokenizer.eos_token_id, pad_id=self.llama_tokenizer.pad_token_id,
-                                    do_sample=bool(samples.get("do_sample", False)),
-                                    temperature=float(samples.get("temperature", 0.8)), top_p=float(samples.get("top_p", 0.9)),
-                                    top_k=int(self.hf_generation_defaults.get("top_k", 50)),   # not a key the reference reads (:705-715)
-                                    repetition_penalty=float(samples.get("repetition_penalty", 1.0)),
-                                    generator=samples.get("generator"), want_first_logits=want_first_logits,
-                                    overlong="drop", num_beams=int(samples.get("num_beams", 1)),
-                                    length_penalty=float(samples.get("length_penalty", 1.0)), constraint=constraint)
+        res = self._generate(samples, segs, speech, constraint, want_first_logits=want_first_logits)
         # a prompt over max_pos costs ITS utterance, not the batch (the reference runs batch 1: inference/inference.py:370-373);
         # such rows come back pad-filled and are listed here for the caller (the CLI reports them as missing indices)
         self.last_dropped_rows = tuple(res.dropped)
@@ -642,6 +646,27 @@ class CustomSALMONN(BaseModel):
         res = self.runtime.prompt_attention(segs, speech, [self.piece_ids(s) for s in segs], n_seg=max(len(pc) for pc in pieces))
         return {"mass": res.mass, "pieces": pieces, "first_logits": res.first_logits}
 
+    def _wrapped_pieces(self, samples: Dict[str, Any], limit: str):
+        """What ``generate_knockout`` and ``generate_cut`` start from: ``(the batch with its counts on the host, the label
+        constraint, the rows' segment lists, the speech rows, the rows' pieces, piece_id)``, where ``piece_id(b, piece)`` is the
+        segment id of a piece of row b.  More than ``MAX_PIECES`` pieces in a row (``limit``: what the caller does among them) and
+        a piece a row does not have are ``ValueError``s naming the row."""
+        samples = self._host_counts(samples)
+        constraint = self._label_constraint(samples)
+        speech_embeds, _, example_embeds, _ = self.get_speech_embeddings(samples)
+        num_examples = samples.get("num_examples", torch.zeros(len(samples["prompt"]), dtype=torch.long))
+        segs, speech, pieces = self._segments_and_pieces(speech_embeds, samples["prompt"], num_examples, example_embeds)
+        for b, pc in enumerate(pieces):
+            if len(pc) > self.MAX_PIECES:
+                raise ValueError(f"row {b}: {len(pc)} pieces in the wrapped prompt, {limit} at most {self.MAX_PIECES}")
+
+        def piece_id(b, piece):
+            piece = (str(piece[0]), int(piece[1]))
+            if piece not in pieces[b]:
+                raise ValueError(f"row {b}: the wrapped prompt has no piece {piece} (its pieces: {pieces[b]})")
+            return pieces[b].index(piece)
+        return samples, constraint, segs, speech, pieces, piece_id
+
     def generate_knockout(self, samples: Dict[str, Any], block, layers=None, heads=None) -> Dict[str, Any]:
         """Attention knockout, the causal companion of ``prompt_attention``: generate while the deciding positions — the last
         prompt position and every generated one — cannot read the pieces in ``block``, in decoder layers ``layers`` (a half-open
@@ -651,36 +676,14 @@ class CustomSALMONN(BaseModel):
         the row, raised before anything is launched on the decoder.  Returns ``{"texts", "tokens": int64 [B, width] (CPU),
         "first_logits": f32 [B, V] (device), "pieces"}``; generation knobs are read from the batch as ``generate_ids`` reads them
         (greedy, sampled or label-constrained; no beams)."""
-        samples = self._host_counts(samples)
-        constraint = self._label_constraint(samples)
-        speech_embeds, _, example_embeds, _ = self.get_speech_embeddings(samples)
-        num_examples = samples.get("num_examples", torch.zeros(len(samples["prompt"]), dtype=torch.long))
-        segs, speech, pieces = self._segments_and_pieces(speech_embeds, samples["prompt"], num_examples, example_embeds)
+        samples, constraint, segs, speech, pieces, piece_id = self._wrapped_pieces(samples, "a knockout blocks among")
         block = list(block)
         is_piece = lambda x: isinstance(x, (tuple, list)) and len(x) == 2 and isinstance(x[0], str)
         per_row = len(block) > 0 and not any(is_piece(x) for x in block)      # one list per row (of pieces, possibly empty)
         if per_row and len(block) != len(pieces):
             raise ValueError(f"{len(block)} block lists for {len(pieces)} rows")
-        blocked = []
-        for b, pc in enumerate(pieces):
-            if len(pc) > self.MAX_PIECES:
-                raise ValueError(f"row {b}: {len(pc)} pieces in the wrapped prompt, a knockout blocks among at most {self.MAX_PIECES}")
-            ids = []
-            for piece in (block[b] if per_row else block):
-                piece = (str(piece[0]), int(piece[1]))
-                if piece not in pc:
-                    raise ValueError(f"row {b}: the wrapped prompt has no piece {piece} (its pieces: {pc})")
-                ids.append(pc.index(piece))
-            blocked.append(ids)
-        res = self.runtime.generate(segs, speech, max_new_tokens=int(samples.get("max_new_tokens", 10)),
-                                    eos_id=self.llama_tokenizer.eos_token_id, pad_id=self.llama_tokenizer.pad_token_id,
-                                    do_sample=bool(samples.get("do_sample", False)),
-                                    temperature=float(samples.get("temperature", 0.8)), top_p=float(samples.get("top_p", 0.9)),
-                                    top_k=int(self.hf_generation_defaults.get("top_k", 50)),
-                                    repetition_penalty=float(samples.get("repetition_penalty", 1.0)),
-                                    generator=samples.get("generator"), want_first_logits=True, overlong="drop",
-                                    num_beams=int(samples.get("num_beams", 1)), constraint=constraint,
-                                    knockout=([self.piece_ids(s) for s in segs], blocked, layers, heads))
+        blocked = [[piece_id(b, piece) for piece in (block[b] if per_row else block)] for b in range(len(pieces))]
+        res = self._generate(samples, segs, speech, constraint, knockout=([self.piece_ids(s) for s in segs], blocked, layers, heads))
         return {"texts": self.decode_ids(res.tokens), "tokens": res.tokens, "first_logits": res.first_logits, "pieces": pieces}
 
     def generate_cut(self, samples: Dict[str, Any], cuts, layers=None, heads=None, generated=None) -> Dict[str, Any]:
@@ -693,40 +696,17 @@ class CustomSALMONN(BaseModel):
         than 32 pieces in a row, are ``ValueError``s naming the row, raised before anything is launched on the decoder
         (``generate_knockout``'s rules).  Returns ``{"texts", "tokens": int64 [B, width] (CPU), "first_logits": f32 [B, V]
         (device), "pieces"}``; generation knobs are read from the batch as ``generate_ids`` reads them (no beams)."""
-        samples = self._host_counts(samples)
-        constraint = self._label_constraint(samples)
-        speech_embeds, _, example_embeds, _ = self.get_speech_embeddings(samples)
-        num_examples = samples.get("num_examples", torch.zeros(len(samples["prompt"]), dtype=torch.long))
-        segs, speech, pieces = self._segments_and_pieces(speech_embeds, samples["prompt"], num_examples, example_embeds)
+        samples, constraint, segs, speech, pieces, piece_id = self._wrapped_pieces(samples, "cuts run between")
         cuts = list(cuts)
         is_piece = lambda x: isinstance(x, (tuple, list)) and len(x) == 2 and isinstance(x[0], str)
         is_pair = lambda x: isinstance(x, (tuple, list)) and len(x) == 2 and is_piece(x[0]) and is_piece(x[1])
         per_row = len(cuts) > 0 and not any(is_pair(x) for x in cuts)         # one list per row (of pairs, possibly empty)
         if per_row and len(cuts) != len(pieces):
             raise ValueError(f"{len(cuts)} cut lists for {len(pieces)} rows")
-
-        def piece_id(b, pc, piece):
-            piece = (str(piece[0]), int(piece[1]))
-            if piece not in pc:
-                raise ValueError(f"row {b}: the wrapped prompt has no piece {piece} (its pieces: {pc})")
-            return pc.index(piece)
-        pairs, gen = [], []
-        for b, pc in enumerate(pieces):
-            if len(pc) > self.MAX_PIECES:
-                raise ValueError(f"row {b}: {len(pc)} pieces in the wrapped prompt, cuts run between at most {self.MAX_PIECES}")
-            pairs.append([(piece_id(b, pc, q), piece_id(b, pc, k)) for q, k in (cuts[b] if per_row else cuts)])
-            if generated is not None:
-                gen.append(piece_id(b, pc, generated))
-        res = self.runtime.generate(segs, speech, max_new_tokens=int(samples.get("max_new_tokens", 10)),
-                                    eos_id=self.llama_tokenizer.eos_token_id, pad_id=self.llama_tokenizer.pad_token_id,
-                                    do_sample=bool(samples.get("do_sample", False)),
-                                    temperature=float(samples.get("temperature", 0.8)), top_p=float(samples.get("top_p", 0.9)),
-                                    top_k=int(self.hf_generation_defaults.get("top_k", 50)),
-                                    repetition_penalty=float(samples.get("repetition_penalty", 1.0)),
-                                    generator=samples.get("generator"), want_first_logits=True, overlong="drop",
-                                    num_beams=int(samples.get("num_beams", 1)), constraint=constraint,
-                                    cuts=dict(segments=[self.piece_ids(s) for s in segs], pairs=pairs, layers=layers, heads=heads,
-                                              generated=gen if generated is not None else None))
+        pairs = [[(piece_id(b, q), piece_id(b, k)) for q, k in (cuts[b] if per_row else cuts)] for b in range(len(pieces))]
+        gen = None if generated is None else [piece_id(b, generated) for b in range(len(pieces))]
+        res = self._generate(samples, segs, speech, constraint, cuts=dict(segments=[self.piece_ids(s) for s in segs], pairs=pairs,
+                                                                          layers=layers, heads=heads, generated=gen))
         return {"texts": self.decode_ids(res.tokens), "tokens": res.tokens, "first_logits": res.first_logits, "pieces": pieces}
 
     def _generate_resid(self, samples: Dict[str, Any], **resid) -> Any:
@@ -737,14 +717,7 @@ class CustomSALMONN(BaseModel):
         speech_embeds, _, example_embeds, _ = self.get_speech_embeddings(samples)
         num_examples = samples.get("num_examples", torch.zeros(len(samples["prompt"]), dtype=torch.long))
         segs, speech = self._segments(speech_embeds, samples["prompt"], num_examples, example_embeds)
-        return self.runtime.generate(segs, speech, max_new_tokens=int(samples.get("max_new_tokens", 10)),
-                                     eos_id=self.llama_tokenizer.eos_token_id, pad_id=self.llama_tokenizer.pad_token_id,
-                                     do_sample=bool(samples.get("do_sample", False)),
-                                     temperature=float(samples.get("temperature", 0.8)), top_p=float(samples.get("top_p", 0.9)),
-                                     top_k=int(self.hf_generation_defaults.get("top_k", 50)),
-                                     repetition_penalty=float(samples.get("repetition_penalty", 1.0)),
-                                     generator=samples.get("generator"), want_first_logits=True, overlong="drop",
-                                     num_beams=int(samples.get("num_beams", 1)), constraint=constraint, **resid)
+        return self._generate(samples, segs, speech, constraint, **resid)
 
     def task_vectors(self, samples: Dict[str, Any]) -> Dict[str, Any]:
         """The residual stream of the last prompt position — the "task vector" of a few-shot prompt — at every site: ``{"hidden":

@@ -360,18 +360,9 @@ class CausalLMRuntimeMixin:
                                                 num_beams, suppress_eos)
         limit = c.max_pos // cache_len_multiple * cache_len_multiple      # cache lengths are multiples of cache_len_multiple
         plens = self._prompt_lengths(prompts)
-        if knockout is not None:
-            knockout = args["knockout"] = P.check_knockout(knockout, c, self.kv_dtype, plens, num_beams)   # None: every blocked set is empty
-        if patch is not None:
-            patch = args["patch"] = P.check_patch(patch, c, len(plens), num_beams, knockout)     # None: an empty row list
-        if head_patch is not None:
-            head_patch = args["head_patch"] = P.check_head_patch(head_patch, c, len(plens), num_beams, knockout, patch)
-        if cuts is not None:
-            cuts = args["cuts"] = P.check_cuts(cuts, c, self.kv_dtype, plens, num_beams, knockout, patch, head_patch)   # None: no row listed
-        if want_heads and num_beams != 1:
-            raise ValueError("want_heads runs with greedy, sampled and label-constrained decoding, not with beams (num_beams > 1)")
-        if want_hidden and num_beams != 1:
-            raise ValueError("want_hidden runs with greedy, sampled and label-constrained decoding, not with beams (num_beams > 1)")
+        checked = P.check_probes(c, self.kv_dtype, plens, num_beams, knockout=knockout, patch=patch, head_patch=head_patch, cuts=cuts,
+                                 want_hidden=want_hidden, want_heads=want_heads)      # a probe that lists nothing is None in it
+        args.update(vars(checked))
         bad = [b for b, n in enumerate(plens) if n + max_new_tokens > limit]
         if bad and (overlong == "raise" or len(bad) == len(plens)):
             raise ValueError(f"prompt + new tokens of row(s) {bad} ({[plens[b] + max_new_tokens for b in bad]} positions) "
@@ -407,8 +398,7 @@ class CausalLMRuntimeMixin:
             keep = [b for b in range(len(plens)) if b not in set(bad)]
             if constraint is not None:
                 args["constraint"] = (constraint[0], [constraint[1][b] for b in keep])
-            args["knockout"], args["patch"], args["head_patch"] = P.keep_rows(knockout, patch, keep, head_patch)
-            args["cuts"] = P.keep_cut_rows(cuts, keep)
+            args.update(vars(checked.kept(keep)))
             return _undrop(self.generate([prompts[b] for b in keep], speech, **args), keep, bad, len(plens), pad)
         # ---- 3. beams
         if num_beams != 1:
@@ -423,12 +413,8 @@ class CausalLMRuntimeMixin:
         marks = getattr(self, "phase_marks", None)     # optional {name: torch.cuda.Event}: bench.py times prefill / decode with it
         if marks is not None:
             marks["prefill_start"].record()
-        hidden = ws.get("gen_hidden", (Bn, c.n_layers + 1, c.hidden), F32) if want_hidden else None
-        head_out = ws.get("gen_head_out", (Bn, c.n_layers, c.n_heads, c.head_dim), BF16) if want_heads else None
-        probes = P.Probes(knockout=None if knockout is None else P.knockout_state(ws, c, knockout, max_len), capture=hidden,
-                          patch=None if patch is None else P.patch_state(ws, c, patch),      # (never both a knockout and a patch)
-                          head_capture=head_out, head_patch=None if head_patch is None else P.head_patch_state(ws, c, head_patch),
-                          cuts=None if cuts is None else P.cuts_state(ws, c, cuts, max_len))
+        probes = checked.state(ws, c, Bn, max_len)
+        hidden, head_out = probes.capture, probes.head_capture
         logits = self._prefill_logits(h, lens, cache, ws.get("gen_last", (Bn, c.hidden), F32), probes=probes)
         first = logits.clone() if want_first_logits else None
         trace = ws.get("gen_logits_trace", (max_new_tokens, Bn, c.vocab), F32) if want_step_logits else None

@@ -151,13 +151,9 @@ def data(kind, form, ents, seed=kr.SEED):
 
 
 def _entry_ref(e: Entry, qbuf, kc, vc, seg, form, scale, row_len=None, blocked=None, mod32=False):
-    D, H, Hkv = form
-    G = H // Hkv
     rl = e.row_len if row_len is None else row_len
     vis = kr.visible_of(seg[e.seq], rl, e.blocked if blocked is None else blocked, mod32=mod32)
-    heads = [oa._group_ref(qbuf[e.row_q].view(H, 1, D)[h:h + 1], kc[e.seq, h // G:h // G + 1, :rl], vc[e.seq, h // G:h // G + 1, :rl],
-                           vis[None], scale, None, None, None, e.seq, [rl - 1]) for h in range(H)]
-    return kr._cat_heads(heads)
+    return kr.entry_ref(qbuf[e.row_q], kc[e.seq], vc[e.seq], [vis] * form[1], form, scale, e.seq)
 
 
 def reference(tb: Tables, qbuf, kc, vc, seg, form, scale, mutate=None) -> oa.Ref:
@@ -242,46 +238,17 @@ def as_i32(bits):
 # an f32 emulation of the kernel's stream order
 # ------------------------------------------------------------------------------------------------------------------
 def emulate_f32(tb: Tables, qbuf, kc, vc, seg, form, scale):
-    """attn_decode_kernel<.., MASK, R> in numpy float32, bf16 [live slots, H, D] in table order: the stream order of
-    attn_knockout_ref.emulate_f32 — 4 * KPW streams, groups of four keys, one running-maximum update per group — over the keys 0 ..
-    the TILE's largest row_len - 1, a key at or past the slot's own row_len or under its mask as score -1e30 and weight 0; a group
-    of four wholly past the slot's row_len is not entered."""
+    """attn_decode_kernel<.., MASK, R> in numpy float32, bf16 [live slots, H, D] in table order: the stream order of the knockout's
+    kernel (``attn_knockout_ref.emulate_head_f32``), every slot walking the keys 0 .. the TILE's largest row_len - 1 — a key at or
+    past the slot's own row_len or under its mask has weight 0, and a group of four wholly past its row_len is not entered."""
     D, H, Hkv = form
     G, NS = H // Hkv, 4 * (64 // (D // 8))
-    f = np.float32
     outs = []
     for t in range(len(tb.tile_seq)):
         live = [e for e in tb.slots[t * tb.R:(t + 1) * tb.R] if e is not None]
         Lt = max(e.row_len for e in live)
-        T = -(-Lt // (4 * NS)) * 4 * NS
         for e in live:
-            s, o_e = e.seq, np.zeros((H, D), dtype=f)
-            for h in range(H):
-                ok = np.zeros(T, dtype=bool)
-                ok[:e.row_len] = kr.visible_of(seg[s], e.row_len, e.blocked).numpy()
-                qv = (qbuf[e.row_q].view(H, D)[h].float().numpy() * f(scale * 1.4426950408889634)).astype(f)
-                k, v = np.zeros((T, D), dtype=f), np.zeros((T, D), dtype=f)
-                k[:Lt], v[:Lt] = kc[s, h // G, :Lt].float().numpy(), vc[s, h // G, :Lt].float().numpy()
-                sc = np.where(ok, (k @ qv).astype(f), f(-1.0e30)).reshape(-1, 4, NS)
-                okr, vr = ok.reshape(-1, 4, NS), v.reshape(-1, 4, NS, D)
-                m, l, o = np.full(NS, -1.0e30, dtype=f), np.zeros(NS, dtype=f), np.zeros((NS, D), dtype=f)
-                for it in range(sc.shape[0]):
-                    first = (it * 4 * NS + np.arange(NS) // (NS // 4) * (NS // 4))          # the group's first key of the stream's wave
-                    go = first < e.row_len
-                    m_new = np.maximum(m, sc[it].max(0))
-                    alpha = np.exp2(m - m_new).astype(f)
-                    pe = np.where(okr[it], np.exp2(sc[it] - m_new[None]).astype(f), f(0))
-                    l2 = (l * alpha + ((pe[0] + pe[1]) + (pe[2] + pe[3]))).astype(f)
-                    o2 = (o * alpha[:, None]).astype(f)
-                    for i in range(4):
-                        o2 = (o2 + pe[i][:, None] * vr[it, i]).astype(f)
-                    m, l, o = np.where(go, m_new, m), np.where(go, l2, l), np.where(go[:, None], o2, o)
-                M = m.max()
-                w = np.exp2(m - M).astype(f)
-                Lsum, acc = f(0), np.zeros(D, dtype=f)
-                for st in range(NS):
-                    Lsum = f(Lsum + l[st] * w[st])
-                    acc = (acc + o[st] * w[st]).astype(f)
-                o_e[h] = acc / Lsum if Lsum > 0 else 0
-            outs.append(o_e)
+            ok = kr.visible_of(seg[e.seq], e.row_len, e.blocked)
+            outs.append(np.stack([kr.emulate_head_f32(qbuf[e.row_q].view(H, D)[h], kc[e.seq, h // G], vc[e.seq, h // G], ok, Lt, NS, scale)
+                                  for h in range(H)]))
     return kr._bf16_round(np.stack(outs))

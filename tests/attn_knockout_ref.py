@@ -165,6 +165,19 @@ def _cat_heads(parts):
     return oa.Ref(*out)
 
 
+def entry_ref(q_row, kc_s, vc_s, visible, form, scale, seq) -> oa.Ref:
+    """The fp64 reference of one listed row, a Ref row with H heads: the query ``q_row`` [H * D] over the cache of one sequence
+    (``kc_s``, ``vc_s`` [Hkv, max_len, D]), head h over the keys ``visible[h]`` (bool [n keys]: the row reads keys 0 .. n - 1)."""
+    D, H, Hkv = form
+    G = H // Hkv
+    heads = []
+    for h, vis in enumerate(visible):
+        n, kh = len(vis), h // G
+        heads.append(oa._group_ref(q_row.view(H, 1, D)[h:h + 1], kc_s[kh:kh + 1, :n], vc_s[kh:kh + 1, :n], vis[None], scale,
+                                   None, None, None, seq, [n - 1]))
+    return _cat_heads(heads)
+
+
 def reference(qbuf, kc, vc, lens, seg, blocked, row_seq, row_q, form, scale, mutate=None) -> oa.Ref:
     """One Ref row per list entry, in list order: what row row_q[r] of O must hold.  ``mutate``: one of MUTANTS — admit_one (the
     first blocked key of a (entry, head) counts), drop_after (the first key after a blocked run is dropped too), mod32 (an id >= 32
@@ -172,8 +185,7 @@ def reference(qbuf, kc, vc, lens, seg, blocked, row_seq, row_q, form, scale, mut
     and row_q change places: the wrong query meets the wrong sequence)."""
     assert mutate is None or mutate in MUTANTS
     D, H, Hkv = form
-    G, rows = H // Hkv, []
-    n_list = len(row_seq)
+    rows, n_list = [], len(row_seq)
     for r in range(n_list):
         s, rq = (row_q[r], row_seq[r]) if mutate == "swap_rows" else (row_seq[r], row_q[r])
         L = int(lens[s])
@@ -188,10 +200,8 @@ def reference(qbuf, kc, vc, lens, seg, blocked, row_seq, row_q, form, scale, mut
                 after = [int(j) + 1 for j in gone if int(j) + 1 < L and bool(vis[int(j) + 1])]
                 if after:
                     vis[after[0]] = False
-            kh = h // G
-            heads.append(oa._group_ref(qbuf[rq].view(H, 1, D)[h:h + 1], kc[s, kh:kh + 1, :L], vc[s, kh:kh + 1, :L], vis[None], scale,
-                                       None, None, None, s, [L - 1]))
-        rows.append(_cat_heads(heads))
+            heads.append(vis)
+        rows.append(entry_ref(qbuf[rq], kc[s], vc[s], heads, form, scale, s))
     return oa.Ref.cat(rows)
 
 
@@ -223,43 +233,50 @@ def _bf16_round(x):
     return torch.from_numpy(np.asarray(x, dtype=np.float32)).to(torch.bfloat16)
 
 
+def emulate_head_f32(qh, k, v, ok, walk, NS, scale):
+    """One (listed row, query head) of attn_decode_kernel<.., MASK[, R]> in numpy float32, f32 [D]: 4 * KPW = ``NS`` streams (key j
+    belongs to stream j mod NS, KPW = 64 / (D / 8)), each folding its keys in groups of four with one running-maximum update per
+    group, base-2 exponentials of scores scaled by scale * log2(e); the streams merged once (zeros where no key counts).  ``qh``
+    bf16 [D]; ``k``, ``v`` bf16 [>= walk, D]; ``ok`` bool [row_len]: the keys that count.  The keys 0 .. ``walk`` - 1 are walked (the
+    row's own row_len, or the largest of its tile); a key at or past row_len or not ``ok`` has score -1e30 and weight 0, and a
+    group of four wholly past row_len is not entered."""
+    f, D, row_len = np.float32, k.shape[1], len(ok)
+    T = -(-walk // (4 * NS)) * 4 * NS
+    okT = np.zeros(T, dtype=bool)
+    okT[:row_len] = ok.numpy()
+    qv = (qh.float().numpy() * f(scale * 1.4426950408889634)).astype(f)
+    kT, vT = np.zeros((T, D), dtype=f), np.zeros((T, D), dtype=f)
+    kT[:walk], vT[:walk] = k[:walk].float().numpy(), v[:walk].float().numpy()
+    sc = np.where(okT, (kT @ qv).astype(f), f(-1.0e30)).reshape(-1, 4, NS)                 # key = (it * 4 + i) * NS + stream
+    okr, vr = okT.reshape(-1, 4, NS), vT.reshape(-1, 4, NS, D)
+    m, l, o = np.full(NS, -1.0e30, dtype=f), np.zeros(NS, dtype=f), np.zeros((NS, D), dtype=f)
+    for it in range(sc.shape[0]):
+        go = it * 4 * NS + np.arange(NS) // (NS // 4) * (NS // 4) < row_len                 # the group's first key of the stream's wave
+        m_new = np.maximum(m, sc[it].max(0))
+        alpha = np.exp2(m - m_new).astype(f)
+        pe = np.where(okr[it], np.exp2(sc[it] - m_new[None]).astype(f), f(0))
+        l2 = (l * alpha + ((pe[0] + pe[1]) + (pe[2] + pe[3]))).astype(f)
+        o2 = (o * alpha[:, None]).astype(f)
+        for i in range(4):
+            o2 = (o2 + pe[i][:, None] * vr[it, i]).astype(f)
+        m, l, o = np.where(go, m_new, m), np.where(go, l2, l), np.where(go[:, None], o2, o)
+    w = np.exp2(m - m.max()).astype(f)
+    Lsum, acc = f(0), np.zeros(D, dtype=f)
+    for st in range(NS):
+        Lsum = f(Lsum + l[st] * w[st])
+        acc = (acc + o[st] * w[st]).astype(f)
+    return acc / Lsum if Lsum > 0 else np.zeros(D, dtype=f)
+
+
 def emulate_f32(qbuf, kc, vc, lens, seg, blocked, row_seq, row_q, form, scale):
-    """attn_decode_kernel<.., MASK> in numpy float32: 4 * KPW streams (key j belongs to stream j mod (4 * KPW), KPW = 64 / (D / 8)),
-    each folding its keys in groups of four with one running-maximum update per group, base-2 exponentials of scores scaled by
-    scale * log2(e), a masked or out-of-range key as score -1e30 and weight 0; the streams merged once.  Returns bf16 [n_list, H, D]
-    in list order (zeros where no key counts)."""
+    """attn_decode_kernel<.., MASK> in numpy float32 (``emulate_head_f32``, every row walking its own keys): bf16 [n_list, H, D] in
+    list order."""
     D, H, Hkv = form
     G, NS = H // Hkv, 4 * (64 // (D // 8))
-    f = np.float32
     out = np.zeros((len(row_seq), H, D), dtype=np.float32)
     for r, (s, rq) in enumerate(zip(row_seq, row_q)):
         L = int(lens[s])
-        T = -(-L // (4 * NS)) * 4 * NS
         for h in range(H):
-            ok = np.zeros(T, dtype=bool)
-            ok[:L] = visible_of(seg[s], L, int(blocked[r, h])).numpy()
-            qv = (qbuf[rq].view(H, D)[h].float().numpy() * f(scale * 1.4426950408889634)).astype(f)
-            k = np.zeros((T, D), dtype=f)
-            v = np.zeros((T, D), dtype=f)
-            k[:L], v[:L] = kc[s, h // G, :L].float().numpy(), vc[s, h // G, :L].float().numpy()
-            sc = np.where(ok, (k @ qv).astype(f), f(-1.0e30)).reshape(-1, 4, NS)           # key = (it * 4 + i) * NS + stream
-            okr, vr = ok.reshape(-1, 4, NS), v.reshape(-1, 4, NS, D)
-            m, l, o = np.full(NS, -1.0e30, dtype=f), np.zeros(NS, dtype=f), np.zeros((NS, D), dtype=f)
-            for it in range(sc.shape[0]):
-                m_new = np.maximum(m, sc[it].max(0))
-                alpha = np.exp2(m - m_new).astype(f)
-                pe = np.where(okr[it], np.exp2(sc[it] - m_new[None]).astype(f), f(0))
-                l = (l * alpha + ((pe[0] + pe[1]) + (pe[2] + pe[3]))).astype(f)
-                o = (o * alpha[:, None]).astype(f)
-                for i in range(4):
-                    o = (o + pe[i][:, None] * vr[it, i]).astype(f)
-                m = m_new
-            M = m.max()
-            w = np.exp2(m - M).astype(f)
-            Lsum = f(0)
-            acc = np.zeros(D, dtype=f)
-            for st in range(NS):
-                Lsum = f(Lsum + l[st] * w[st])
-                acc = (acc + o[st] * w[st]).astype(f)
-            out[r, h] = acc / Lsum if Lsum > 0 else 0
+            out[r, h] = emulate_head_f32(qbuf[rq].view(H, D)[h], kc[s, h // G], vc[s, h // G], visible_of(seg[s], L, int(blocked[r, h])),
+                                         L, NS, scale)
     return _bf16_round(out)

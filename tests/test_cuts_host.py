@@ -111,23 +111,25 @@ def test_the_listing_rule():
     # (3, 3): a query that does not read its own segment is listed from the segment's first position on; every prompt starts with
     # a key of segment 0, which segment 3 may read, so no row is left without a key
     segs = [[0] + s for s in segs]
-    v = P.check_cuts(dict(segments=segs, pairs=pairs), cfg, "bf16", [len(s) for s in segs], 1)
+    check = lambda cuts, plens=[len(s) for s in segs]: P.check_probes(cfg, "bf16", plens, 1, cuts=cuts).cuts
+    all_of = P.check_probes(cfg, "bf16", [len(s) for s in segs], 1, cuts=dict(segments=segs, pairs=pairs))
+    v = all_of.cuts
     assert _pairs_of(v["entries"]) == [_listed(s, K) for s in segs]
     assert any(_pairs_of(v["entries"])) and v["layers"] == (0, cfg.n_layers) and v["heads"] is None
     # per-prompt pairs; ids >= 32 and 255 are never cut (40 is not 8 mod 32) and never a query segment
-    per = P.check_cuts(dict(segments=segs, pairs=[pairs, [], [(1, 0)], [(1, 8), (8, 1), (2, 0)]]), cfg, "bf16", [len(s) for s in segs], 1)
+    per = check(dict(segments=segs, pairs=[pairs, [], [(1, 0)], [(1, 8), (8, 1), (2, 0)]]))
     assert _pairs_of(per["entries"]) == [_listed(segs[0], K), [], _listed(segs[2], {1: {0}}), _listed(segs[3], {2: {0}})]
     # generated: None = the segment of the last position; an id >= 32 or without pairs = 0; a key segment the prompt lacks = no cut
     assert v["gen"] == [sum(1 << g for g in K.get(s[-1], ()) if g in s) for s in segs]
-    assert P.check_cuts(dict(segments=segs, pairs=pairs, generated=255), cfg, "bf16", [len(s) for s in segs], 1)["gen"] == [0] * 4
-    assert P.check_cuts(dict(segments=segs, pairs=[(9, 0)], generated=9), cfg, "bf16", [len(s) for s in segs], 1)["gen"] == [1] * 4
-    assert P.check_cuts(dict(segments=segs, pairs=[(9, 0)], generated=[9, 0, 255, 9]), cfg, "bf16", [len(s) for s in segs], 1)["gen"] == [1, 0, 0, 1]
-    assert P.check_cuts(dict(segments=segs, pairs=[(9, 20)], generated=9), cfg, "bf16", [len(s) for s in segs], 1) is None
+    assert check(dict(segments=segs, pairs=pairs, generated=255))["gen"] == [0] * 4
+    assert check(dict(segments=segs, pairs=[(9, 0)], generated=9))["gen"] == [1] * 4
+    assert check(dict(segments=segs, pairs=[(9, 0)], generated=[9, 0, 255, 9]))["gen"] == [1, 0, 0, 1]
+    assert check(dict(segments=segs, pairs=[(9, 20)], generated=9)) is None
     # a validated dict is itself a valid argument, with the same result (overlong="drop" hands it on)
-    again = P.check_cuts({k: v[k] for k in P.CUT_KEYS}, cfg, "bf16", [len(s) for s in segs], 1)
+    again = check({k: v[k] for k in P.CUT_KEYS})
     assert _pairs_of(again["entries"]) == _pairs_of(v["entries"]) and {k: again[k] for k in again if k not in ("entries", "segments")} == {k: v[k] for k in v if k not in ("entries", "segments")}
     assert [sg.tolist() for sg in again["segments"]] == segs
-    kept = P.check_cuts(P.keep_cut_rows(v, [1, 3]), cfg, "bf16", [len(segs[1]), len(segs[3])], 1)
+    kept = check(all_of.kept([1, 3]).cuts, [len(segs[1]), len(segs[3])])
     assert _pairs_of(kept["entries"]) == [_pairs_of(v["entries"])[1], _pairs_of(v["entries"])[3]] and kept["gen"] == [v["gen"][1], v["gen"][3]]
 
 

@@ -63,7 +63,7 @@ def gen_got():
 
 def test_generate_matrix_shape():
     cases = ["/".join(c) for c in lt.GEN_MATRIX]
-    assert len(cases) == len(set(cases)) == 71
+    assert len(cases) == len(set(cases)) == 101
     assert set(lt.load_fixture(lt.GEN_FIXTURE)) == set(cases)
 
 
@@ -79,11 +79,16 @@ def test_generate_trace_sees_the_modes(gen_got):
     names = ("greedy4", "chunk2", "sample_seeded", "repetition_penalty", "constrained", "beam3")
     assert len({gen_got[f"tiny_h4/bf16/{n}"] for n in names}) == len(names)
     assert gen_got["tiny_h4/bf16/chunk5"] == gen_got["tiny_h4/bf16/greedy4"]
-    # ... and so do the probes of the deciding rows: plain, readout, knockout, capture and patch, on every config that runs them
-    probes = ("greedy4", "prompt_attention", "knockout", "hidden", "patch_all_steps")
+    # ... and so do the probes: plain, readout, knockout, the residual and the head captures and patches, and cuts, on every
+    # config that runs them
+    probes = ("greedy4", "prompt_attention", "knockout", "hidden", "patch_all_steps", "heads", "head_patch_all_steps",
+              "heads_patch_shared", "cuts")
     for cname in ("tiny_h4", "7b_gqa8_bias"):
         assert len({gen_got[f"{cname}/bf16/{n}"] for n in probes}) == len(probes), cname
     assert len({gen_got[f"7b_lora/bf16/{n}"] for n in probes[1:]}) == len(probes) - 1
+    drops = ("drop_knockout", "drop_hidden_patch", "drop_cuts", "drop_head_patch")
+    for cname in ("tiny_h4", "7b_lora", "7b_gqa8_bias"):
+        assert len({gen_got[f"{cname}/bf16/{n}"] for n in drops}) == len(drops), cname
 
 
 @pytest.fixture

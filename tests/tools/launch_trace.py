@@ -9,7 +9,7 @@ the same device time by construction.  tests/test_launch_trace.py compares again
 
 A second matrix pins the generation driver one level up (runtime/salmonn.py: ``generate`` with every decode tail, chunked
 prefill, ``overlong="drop"`` and beam search, and the probes of the deciding rows — ``prompt_attention``, ``knockout``,
-``want_hidden`` and ``patch`` — chunked and not): one sha256 per case in tests/golden/generate_launch_trace.json.  Besides the
+``want_hidden``, ``patch``, ``want_heads``, ``head_patch`` and ``cuts`` — chunked and not): one sha256 per case in tests/golden/generate_launch_trace.json.  Besides the
 launches, a generate trace holds the torch plumbing between them (every in-place op or ``clone`` on a device tensor, host
 tables by value), where the three ``phase_marks`` are recorded, and the shape of the result.
 
@@ -389,6 +389,16 @@ _PROBES = {
     "patch_last_site": dict(patch=lambda cfg, lens: dict(site=cfg.n_layers, vectors=torch.zeros(5, cfg.hidden), rows=[0, 3])),   # no capture
     "hidden_patch_shared": dict(want_hidden=True,          # the shared vector, all rows: capture and patch in one launch
                                 patch=lambda cfg, lens: dict(site=cfg.n_layers, vectors=torch.zeros(1, cfg.hidden))),
+    "heads": dict(want_heads=True),
+    "head_patch_all_steps": dict(head_patch=lambda cfg, lens: dict(heads=[(1, 2), (0, 1), (1, 0)],       # two layers, out of order
+                                                                   vectors=torch.zeros(5, 3, cfg.head_dim), mode="add", alpha=0.5,
+                                                                   steps="all", rows=[0, 3])),
+    "heads_patch_shared": dict(want_heads=True,            # shared vectors, all rows: capture and patch in one launch
+                               head_patch=lambda cfg, lens: dict(heads=[(1, 2), (1, 0)], vectors=torch.zeros(1, 2, cfg.head_dim))),
+    # interior rows (segment 1) and the last rows (segment 3) are listed, two heads of four or more, both layers — the last one
+    # launches the last rows only — and the generated rows query as segment 1, so every decode step launches
+    "cuts": dict(cuts=lambda cfg, lens: dict(segments=segments_of(lens), pairs=[(1, 0), (3, 0)], layers=(0, cfg.n_layers),
+                                             heads=[0, 2], generated=1)),
 }
 PROBE_CASES = {}
 for _name, _kw in _PROBES.items():
@@ -401,6 +411,12 @@ PROBE_CASES["drop_knockout"] = ({}, _overlong_third, dict(max_new_tokens=4, over
 PROBE_CASES["drop_hidden_patch"] = ({}, _overlong_third, dict(max_new_tokens=4, overlong="drop", want_hidden=True,
                                                               patch=lambda cfg, lens: dict(site=1, vectors=torch.zeros(5, cfg.hidden),
                                                                                            rows=[2, 3])))
+# ... cuts with one pair list per prompt, the dropped one's too, and a head patch whose rows list the dropped row and one kept row
+PROBE_CASES["drop_cuts"] = ({}, _overlong_third, dict(max_new_tokens=4, overlong="drop", cuts=lambda cfg, lens: dict(
+    segments=segments_of(lens), pairs=[[(1, 0)], [(2, 1)], [(1, 0), (2, 0), (3, 0)], [(3, 1)], []], generated=[1, 3, 3, 3, 0])))
+PROBE_CASES["drop_head_patch"] = ({}, _overlong_third, dict(max_new_tokens=4, overlong="drop", want_heads=True,
+                                                            head_patch=lambda cfg, lens: dict(heads=[(1, 2), (0, 1)], rows=[2, 3],
+                                                                                              vectors=torch.zeros(5, 2, cfg.head_dim))))
 GEN_CASES.update(PROBE_CASES)
 # prompt_attention(): name -> (attributes set on the runtime, its keyword arguments besides the segments)
 PA_CASES = {
