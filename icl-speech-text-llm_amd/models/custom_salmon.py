@@ -628,14 +628,17 @@ class CustomSALMONN(BaseModel):
 
     MAX_PIECES = 32        # segments the readout kernel sums (runtime.probes.MAX_READOUT_SEGMENTS): 14 non-SQA exemplars
 
-    def prompt_attention(self, samples: Dict[str, Any]) -> Dict[str, Any]:
+    def prompt_attention(self, samples: Dict[str, Any], flow: bool = False) -> Dict[str, Any]:
         """Where the last prompt position (the query that decides the first generated token) looks, per piece of the wrapped
         prompt: ``{"mass": f32 [B, n_layers, n_heads, n_pieces] (CPU), "pieces": per row the list of (kind, i), "first_logits":
         f32 [B, V] (device)}``.  A piece is one entry of ``interleave_plan`` / ``interleave_plan_sqa`` that the prompt wrap emits —
         ``("text", i)``, ``("example", i)``, ``("speech", 0)`` or the SQA kinds; an empty text part emits nothing and gets no id —
         and piece p of a row has id p; n_pieces is the largest row's count, a row with fewer pieces has exact zeros behind them.
         ``first_logits`` are those of ``generate_ids(..., want_first_logits=True)``, bit for bit.  More than 32 pieces in a row
-        is a ``ValueError`` naming the row, raised before anything is launched on the decoder."""
+        is a ``ValueError`` naming the row, raised before anything is launched on the decoder.  ``flow``: the result also holds
+        ``"flow"``, f32 [B, n_layers, n_heads, n_pieces, n_pieces] (CPU) — the attention mass the positions of piece a send to
+        the positions of piece c, summed over a's positions — and ``"rows"``, int64 [B, n_pieces]: the positions of every piece
+        (``flow / rows`` is the mean mass); a row with fewer pieces has exact zeros behind them in both."""
         samples = self._host_counts(samples)
         speech_embeds, _, example_embeds, _ = self.get_speech_embeddings(samples)
         num_examples = samples.get("num_examples", torch.zeros(len(samples["prompt"]), dtype=torch.long))
@@ -643,8 +646,12 @@ class CustomSALMONN(BaseModel):
         for b, pc in enumerate(pieces):
             if len(pc) > self.MAX_PIECES:
                 raise ValueError(f"row {b}: {len(pc)} pieces in the wrapped prompt, the attention readout sums at most {self.MAX_PIECES}")
-        res = self.runtime.prompt_attention(segs, speech, [self.piece_ids(s) for s in segs], n_seg=max(len(pc) for pc in pieces))
-        return {"mass": res.mass, "pieces": pieces, "first_logits": res.first_logits}
+        res = self.runtime.prompt_attention(segs, speech, [self.piece_ids(s) for s in segs], n_seg=max(len(pc) for pc in pieces),
+                                            **(dict(want_flow=True) if flow else {}))
+        out = {"mass": res.mass, "pieces": pieces, "first_logits": res.first_logits}
+        if flow:
+            out.update(flow=res.flow, rows=res.rows)
+        return out
 
     def _wrapped_pieces(self, samples: Dict[str, Any], limit: str):
         """What ``generate_knockout`` and ``generate_cut`` start from: ``(the batch with its counts on the host, the label

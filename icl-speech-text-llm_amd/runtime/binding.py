@@ -71,6 +71,8 @@ _SIGNATURES = {
                                          c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
     "icl_attn_segmass_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
                                       c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "icl_attn_segflow_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32,
+                                      c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
     "icl_attn_decode_masked_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                             c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float,
                                             c_void_p]),
@@ -451,6 +453,25 @@ def attn_segmass(q, kcache, lens, seg, mass, n_heads: int, head_dim: int, max_le
                                                 probs.stride(1) if probs is not None else 0, n_seqs, n_heads, n_kv_heads,
                                                 head_dim, max_len, scale, _stream()), "icl_attn_segmass_bf16")
     return mass
+
+
+def attn_segflow(q, cu, kcache, seg, flow, n_heads: int, head_dim: int, max_len: int, max_seqlen: int, scale: float, *,
+                 n_kv_heads: int = 0):
+    """The segment-to-segment attention flow (icl_attn_segflow_bf16): the causal softmax weights of every prompt row over the K
+    cache [n_seqs, n_kv_heads, max_len, head_dim], summed by (segment of the query row, segment of the key).  q: bf16 packed rows,
+    already rotated — row ``cu[b] + i`` is position i of sequence b; cu: int32 [n_seqs + 1]; seg: uint8 [n_seqs, >= max_len], the
+    segment of every position (>= n_seg: summed nowhere as a query, counted in no segment as a key); flow: f32 [n_seqs, n_heads,
+    n_seg, n_seg], contiguous (every element written); ``max_seqlen``: the longest sequence, at most ``max_len``."""
+    _require_gpu(q, cu, kcache, seg, flow)
+    assert cu.dtype == torch.int32 and seg.dtype == torch.uint8 and flow.dtype == torch.float32 and q.dtype == torch.bfloat16
+    assert kcache.dtype == torch.bfloat16 and q.stride(-1) == 1 and cu.is_contiguous()
+    n_seqs = cu.numel() - 1
+    assert seg.dim() == 2 and seg.shape[0] == n_seqs and seg.stride(1) == 1 and kcache.shape[0] == n_seqs
+    assert flow.is_contiguous() and flow.dim() == 4 and tuple(flow.shape[:2]) == (n_seqs, n_heads) and flow.shape[2] == flow.shape[3]
+    _check(load_library().icl_attn_segflow_bf16(q.data_ptr(), q.stride(0), cu.data_ptr(), kcache.data_ptr(), seg.data_ptr(),
+                                                seg.stride(0), flow.shape[2], flow.data_ptr(), n_seqs, n_heads, n_kv_heads, head_dim,
+                                                max_len, max_seqlen, scale, _stream()), "icl_attn_segflow_bf16")
+    return flow
 
 
 def attn_decode_masked(q, kcache, vcache, out, lens, seg, blocked, row_seq, row_q, n_heads: int, head_dim: int, max_len: int,

@@ -648,7 +648,7 @@ class LlamaHIP:
         # the trimmed last layer is built on the 256-tile's fused RoPE epilogue (head_dim 128) and a bf16 cache; other models
         # and the FP8 KV mode (whose prefill attends to unrounded packed k / v) keep the full-height layer and gather after it
         trim = (last_rows_only and self.prefill_last_rows and not fp8 and not gqa and not qkn
-                and B.rope_epilogue_ok(H, D, w.k_aug))
+                and B.rope_epilogue_ok(H, D, w.k_aug) and not (probes is not None and probes.reads_every_row))
         last_idx = out = None
         if last_rows_only:
             last_idx = _i32([e - 1 for e in cu_h[1:]], dev)

@@ -1,6 +1,7 @@
 """Probes of the deciding rows of the LLM decoder — the last prompt row of every sequence and the rows generated after it:
 
   the prompt-attention readout   ``AttnReadout``          icl_attn_segmass_bf16         where the row looks, per prompt segment
+                                                          icl_attn_segflow_bf16         (``flow``) where EVERY prompt row looks, per segment pair
   attention knockout             ``Knockout``             icl_attn_decode_masked_bf16   the row attends as if segments were absent
   residual capture / patching    a tensor, ``ResidPatch`` icl_resid_rows_f32            the row's residual stream, read and written
   head-output capture / patching a tensor, ``HeadPatch``  icl_head_rows_bf16            what single heads hand to o_proj, read and written
@@ -41,16 +42,33 @@ HEAD_PATCH_KEYS = ("heads", "vectors", "mode", "alpha", "rows", "steps")
 class AttnReadout:
     """Where a prefill leaves the prompt-attention readout of its sequences, all on the device: ``seg`` uint8 [n_seqs, >= cache
     max_len] the segment of every prompt position (>= n_seg: counted nowhere), ``lens`` int32 [n_seqs] the prompt lengths,
-    ``mass`` f32 [n_layers, n_seqs, n_heads, n_seg] and ``probs`` None or f32 [n_layers, n_seqs, n_heads, >= max_len] (written)."""
+    ``mass`` f32 [n_layers, n_seqs, n_heads, n_seg] and ``probs`` None or f32 [n_layers, n_seqs, n_heads, >= max_len] (written).
+    ``flow``: None, or f32 [n_layers, n_seqs, n_heads, n_seg, n_seg] (written) — the segment-to-segment flow of ALL prompt rows
+    (icl_attn_segflow_bf16), which needs every query of every layer: a prefill does not trim its last layer for such a readout
+    (``Probes.reads_every_row``).  ``cu`` / ``max_seqlen``: what the flow launch needs of the prefill in progress
+    (``start_prefill``): int32 [n_seqs + 1] the first packed row of every sequence, and the longest sequence."""
     seg: torch.Tensor
     lens: torch.Tensor
     mass: torch.Tensor
     probs: Optional[torch.Tensor] = None
+    flow: Optional[torch.Tensor] = None
+    cu: Optional[torch.Tensor] = None
+    max_seqlen: int = 0
 
     def rows(self, b0: int, b1: int) -> "AttnReadout":
         """The readout of sequences b0 .. b1-1 (views), for a prefill over that chunk of the batch (``KVCache.rows``)."""
         return AttnReadout(self.seg[b0:b1], self.lens[b0:b1], self.mass[:, b0:b1],
-                           None if self.probs is None else self.probs[:, b0:b1])
+                           None if self.probs is None else self.probs[:, b0:b1],
+                           None if self.flow is None else self.flow[:, b0:b1])
+
+    def start_prefill(self, seq_lens: List[int], cu_h: List[int]) -> None:
+        if self.flow is not None:
+            self.cu, self.max_seqlen = _i32(cu_h, self.flow.device), max(seq_lens)
+
+    def launch_flow(self, layer: int, q: torch.Tensor, kc: torch.Tensor, cfg, max_len: int) -> None:
+        """``q``: the packed rotated query rows of the prefill in progress, all of them."""
+        B.attn_segflow(q, self.cu, kc, self.seg, self.flow[layer], cfg.n_heads, cfg.head_dim, max_len, self.max_seqlen,
+                       cfg.head_dim ** -0.5, n_kv_heads=cfg.kv_heads)
 
     def launch(self, layer: int, q: torch.Tensor, q_rows: Optional[torch.Tensor], kc: torch.Tensor, cfg, max_len: int) -> None:
         B.attn_segmass(q, kc, self.lens, self.seg, self.mass[layer], cfg.n_heads, cfg.head_dim, max_len, cfg.head_dim ** -0.5,
@@ -315,6 +333,13 @@ class Probes:
         bundle with nothing left is None: the chunk then launches what it launches without probes."""
         return Probes(**{k: p[b0:b1] if isinstance(p, torch.Tensor) else p.rows(b0, b1) for k, p in self._parts().items()})._or_none()
 
+    @property
+    def reads_every_row(self) -> bool:
+        """Does a probe read the queries of EVERY prompt row in every layer (the readout's ``flow``)?  ``LlamaHIP.prefill`` then
+        keeps its last layer at full height and gathers the last rows after it — bit-identical for those rows, the trim's own
+        contract."""
+        return self.readout is not None and self.readout.flow is not None
+
     def _every_step(self) -> dict:
         """The probes that launch in every decode step: the knockout, a patch and a head patch of every step, and cuts whose
         generated rows cut something."""
@@ -340,6 +365,8 @@ class Probes:
         self._ct_prefill, self._ct_tables = (list(seq_lens), list(cu_h)), {}
         self._last = last_idx
         self._key_counts = None if self.knockout is None else _i32(seq_lens, last_idx.device)
+        if self.readout is not None:
+            self.readout.start_prefill(seq_lens, cu_h)
         for p in self._parts().values():
             if isinstance(p, _ListedRows):
                 p.listed.start_prefill(cu_h)
@@ -371,9 +398,13 @@ class Probes:
             lambda rows, cap, pt: B.resid_rows(h, rows, capture=cap, **({} if pt is None else pt.operands())))
 
     def keys_appended(self, layer: int, q: torch.Tensor, kc: torch.Tensor, cfg, max_len: int, packed: bool = False) -> None:
-        """q is rotated and the layer's k is in the bf16 cache ``kc``: the readout of the deciding rows' attention."""
+        """q is rotated and the layer's k is in the bf16 cache ``kc``: the readout of the deciding rows' attention, and then —
+        the cache holds every prompt position here — of all rows' (``flow``)."""
         if self.readout is not None:
             self.readout.launch(layer, q, self._last if packed else None, kc, cfg, max_len)
+            if self.readout.flow is not None:
+                assert packed, "the flow readout reads every packed query row: its prefill does not trim the last layer"
+                self.readout.launch_flow(layer, q, kc, cfg, max_len)
 
     def attention_written(self, layer: int, q: torch.Tensor, att: torch.Tensor, kc, vc, cfg, max_len: int,
                           lens: Optional[torch.Tensor] = None, packed: bool = False) -> None:
@@ -543,16 +574,18 @@ def check_readout(segments, n_seg: Optional[int], kv_dtype: str, plens: List[int
 
 
 def readout_state(ws: Workspace, cfg, segs: List[torch.Tensor], n_seg: int, lens: List[int], max_len: int, want_probs: bool,
-                  device) -> AttnReadout:
+                  device, want_flow: bool = False) -> AttnReadout:
     """The validated readout on the device: the segment table padded to the cache length, the prompt lengths, and where the
-    launches leave the mass (and the full weights, ``want_probs``: zeroed — the kernel leaves a row's tail untouched)."""
+    launches leave the mass (and the full weights, ``want_probs``: zeroed — the kernel leaves a row's tail untouched; and the
+    segment-to-segment flow, ``want_flow``: every element is written)."""
     Bn = len(segs)
     seg_d = _segment_table(ws, "pa_seg", segs, max_len)
     mass = ws.get("pa_mass", (cfg.n_layers, Bn, cfg.n_heads, n_seg), F32)
     probs = ws.get("pa_probs", (cfg.n_layers, Bn, cfg.n_heads, max_len), F32) if want_probs else None
     if probs is not None:
         probs.zero_()
-    return AttnReadout(seg_d, _i32(lens, device), mass, probs)
+    flow = ws.get("pa_flow", (cfg.n_layers, Bn, cfg.n_heads, n_seg, n_seg), F32) if want_flow else None
+    return AttnReadout(seg_d, _i32(lens, device), mass, probs, flow)
 
 
 # ================================================================================================

@@ -52,6 +52,10 @@ class PromptAttention:
     probs: Optional[torch.Tensor]       # None, or f32 [B, n_layers, n_heads, max_len] (device); row b is valid up to lens[b]
     first_logits: torch.Tensor          # f32 [B, V] (device): generate(..., want_first_logits=True).first_logits, bit for bit
     lens: List[int]                     # prompt lengths (positions)
+    flow = None      # or f32 [B, n_layers, n_heads, n_seg, n_seg] on CPU, with ``want_flow``: the attention mass EVERY query row of
+    #                  segment a sends to the keys of segment c, summed over the rows (``flow / rows[:, None, None, :, None]``: the mean)
+    rows = None      # or int64 [B, n_seg] on CPU, with ``want_flow``: the positions of every segment.  Both are attributes set after
+    #                  construction, not dataclass fields: the fields are what a result of a plain call consists of (pinned trace)
 
 
 def _undrop(sub: GenerateResult, keep: List[int], bad: List[int], n: int, pad: int) -> GenerateResult:
@@ -498,7 +502,8 @@ class CausalLMRuntimeMixin:
 
     # ---- the prompt-attention readout: generate()'s prefill plus one launch per layer ----
     def prompt_attention(self, prompts, speech: Optional[torch.Tensor], segments: Sequence[Sequence[int]],
-                         want_probs: bool = False, n_seg: Optional[int] = None, cache_len_multiple: int = 64) -> PromptAttention:
+                         want_probs: bool = False, n_seg: Optional[int] = None, cache_len_multiple: int = 64,
+                         want_flow: bool = False) -> PromptAttention:
         """Where the last prompt row (the query that decides the first generated token) looks: its attention mass in every
         layer and head, summed over each segment of the prompt — what ``output_attentions=True`` of a transformers decoder gives
         for that row, reduced per segment (``[B, n_layers, n_heads, n_seg]`` floats; the full last-row weights with
@@ -507,6 +512,13 @@ class CausalLMRuntimeMixin:
         ``segments``: one sequence of ints per prompt, as long as the prompt's positions: the segment (0 .. n_seg - 1) of every
         position; an id >= n_seg (``IGNORE_SEGMENT``) is counted nowhere.  ``n_seg`` defaults to 1 + the largest id below
         ``IGNORE_SEGMENT``; at most 32.
+
+        ``want_flow``: also ``flow`` f32 [B, n_layers, n_heads, n_seg, n_seg] and ``rows`` int64 [B, n_seg], both on the CPU — the
+        descriptive side of ``generate(cuts=...)``: ``flow[b, l, h, a, c]`` is the attention mass the query rows of segment a
+        send to the keys of segment c (causal softmax of every row, summed over the rows; ``rows[b, a]`` of them), one more
+        launch per layer (icl_attn_segflow_bf16).  It reads every query of every layer, so the last layer runs at full height
+        and its last rows are gathered: the same bits for ``first_logits`` and ``mass``.  An ignored id on a query row: the row is
+        summed nowhere.
 
         Runs the prefill ``generate`` runs (same kernels, same KV cache, last rows only, same chunks), with one more launch per
         layer (icl_attn_segmass_bf16) between the K append and the attention, so ``first_logits`` are ``generate``'s bit for bit.
@@ -522,11 +534,15 @@ class CausalLMRuntimeMixin:
         h, lens = self.embed_prompts(prompts, speech)
         max_len = self._cache_len(lens, 1, cache_len_multiple)
         cache = self._cache(len(lens), max_len)
-        readout = P.readout_state(ws, c, segs, n_seg, lens, max_len, want_probs, self.device)
+        readout = P.readout_state(ws, c, segs, n_seg, lens, max_len, want_probs, self.device, want_flow=want_flow)
         logits = self._prefill_logits(h, lens, cache, ws.get("gen_last", (len(lens), c.hidden), F32), probes=P.Probes(readout=readout))
-        return PromptAttention(mass=readout.mass.cpu().transpose(0, 1).contiguous(),
-                               probs=None if readout.probs is None else readout.probs.transpose(0, 1).clone(),
-                               first_logits=logits.clone(), lens=list(lens))
+        res = PromptAttention(mass=readout.mass.cpu().transpose(0, 1).contiguous(),
+                              probs=None if readout.probs is None else readout.probs.transpose(0, 1).clone(),
+                              first_logits=logits.clone(), lens=list(lens))
+        if readout.flow is not None:
+            res.flow = readout.flow.cpu().transpose(0, 1).contiguous()
+            res.rows = torch.stack([torch.bincount(sg[sg < n_seg], minlength=n_seg) for sg in segs])
+        return res
 
     def _check_constraint(self, constraint, n_rows: int, max_new_tokens: int, eos_id, do_sample: bool, repetition_penalty: float,
                           num_beams: int, suppress_eos: bool):

@@ -246,6 +246,33 @@ int icl_attn_segmass_bf16(const void* Q, int64_t ldq, const int32_t* q_rows, con
                           int32_t n_seqs, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int32_t max_len, float scale,
                           void* stream);
 
+/* ---- segment-to-segment attention flow: the causal softmax weights of EVERY prompt row, summed by (query segment, key segment) ----
+ * The descriptive side of the cuts below, and the readout above for all rows at once: what output_attentions=True of a transformers
+ * decoder (eager attention) gives as an S x S matrix per layer and head, summed by (seg[i], seg[j]).  Replaces that matrix and the
+ * loop of one-row icl_attn_segmass_bf16 launches it would otherwise take.  V is never read.
+ *   Q      bf16, packed rotated query rows (normalised, for a QK-norm decoder): row cu[b] + i is position i of sequence b, head h at
+ *          column h * head_dim.  ldq % 8 == 0, ldq >= n_heads * head_dim.
+ *   cu     int32 [n_seqs + 1], ascending: sequence b has len = cu[b + 1] - cu[b] positions, 1 <= len <= max_seqlen <= max_len.
+ *   Kc     the bf16 K cache of the decode kernels, [n_seqs][n_kv_heads][max_len][head_dim], holding positions 0 .. len - 1; query
+ *          head h reads K head h / (n_heads / n_kv_heads); n_kv_heads 0 = n_heads.  Rows at or past len are never read.
+ *   seg    seg[b * ld_seg + i] = the segment of position i, as a query row and as a key; entries at or past len are never read.
+ *   p(i, j) = softmax over j <= i of scale * sum_d q_id k_jd,
+ *   flow[b][h][a][c] = sum_{i < len, seg_i = a} sum_{j <= i, seg_j = c} p(i, j)    (f32 [n_seqs][n_heads][n_seg][n_seg], compact).
+ * An id >= n_seg on a query row: the row is summed nowhere; on a key: it counts in no segment but stays in the row's softmax.
+ * Every element of flow is written (no zero-fill contract); a pair (a, c) with no (i, j) to count is exactly 0.0f.
+ * Flash-shaped: S^T = K Q^T on MFMA with the query on the lane, keys in tiles of 64 through LDS, an online (m, l) per lane; the
+ * P V product is P E with E the one-hot [key][segment] matrix built in registers, P as a two-term bf16 split (hi + lo).  One
+ * workgroup per (sequence, query head) walks the 128-query blocks in order.  No atomics, every sum in a fixed order that depends on
+ * the sequence's own length and ids only: a sequence's flow is bit-identical alone and in any batch.
+ * head_dim 64 or 128 multi-head; grouped (2 <= G <= 8 query heads per K/V head) at head_dim 128.
+ * ICL_EINVAL (before any launch, naming the argument): a NULL Q / cu / Kc / seg / flow, n_seg outside 1..32, head_dim not 64 / 128,
+ * n_kv_heads not dividing n_heads, G > 8, G > 1 at head_dim 64, n_seqs outside 1..65535, max_seqlen outside 1..max_len,
+ * ld_seg < max_len, ldq % 8 or ldq < n_heads * head_dim, misaligned Q / Kc (16 B) or flow (4 B), a scale that is not finite.
+ */
+int icl_attn_segflow_bf16(const void* Q, int64_t ldq, const int32_t* cu, const void* Kc, const uint8_t* seg, int64_t ld_seg,
+                          int32_t n_seg, float* flow, int32_t n_seqs, int32_t n_heads, int32_t n_kv_heads /* 0 = n_heads */,
+                          int32_t head_dim, int32_t max_len, int32_t max_seqlen, float scale, void* stream);
+
 /* ---- attention knockout: icl_attn_decode_bf16 / icl_attn_decode_gqa_bf16 over a row LIST, under a per-key segment mask ----
  * The causal companion of the readout above: the deciding query attends as if chosen pieces of the prompt were not there.
  * List entry r (0 <= r < n_rows) works on cache sequence row_seq[r]: it reads the query (bf16, already rotated) at row row_q[r]
