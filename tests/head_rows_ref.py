@@ -21,7 +21,7 @@ import torch
 
 import far_layout as fl
 from fp64_bounds import bf16_interval, bf16_rne, in_interval, interval_ratio
-from resid_patch_ref import _fma32, _rng
+from resid_patch_ref import fma32, keyed_rng
 
 SHAPES = ((64, 3), (128, 4), (128, 40))    # (head_dim, n_heads): 8 and 16 lanes per head row; one block, part of one, two and a half
 N_ROWS = (1, 3, 65)
@@ -64,7 +64,7 @@ def heads_of(c: Launch) -> np.ndarray:
         return np.array([c.H - 2], dtype=np.int32)
     if c.sel == "two":
         return np.array([2, 0], dtype=np.int32)             # unsorted
-    return _rng("heads", c.H).permutation(c.H).astype(np.int32)
+    return keyed_rng("heads", c.H).permutation(c.H).astype(np.int32)
 
 
 def launch_cases(D, H, n_rows):
@@ -84,7 +84,7 @@ def launch_cases(D, H, n_rows):
 
 def rows_of(c: Launch):
     """Distinct rows of the 70, never the last one (a row + 1 mutant stays inside), in no particular order."""
-    rows = _rng("rows", c.n_rows).permutation(ROWS_TOTAL - 1)[:c.n_rows].astype(np.int32)
+    rows = keyed_rng("rows", c.n_rows).permutation(ROWS_TOTAL - 1)[:c.n_rows].astype(np.int32)
     return rows[::-1].copy() if c.reverse else rows
 
 
@@ -101,7 +101,7 @@ def widen(bits: np.ndarray) -> np.ndarray:
 def inputs(c: Launch):
     """(att uint16 [70, width + PAD] bf16 bits with the sentinel in the PAD columns, rows int32 [n], heads int32 [n_sel] | None,
     vec f32 [n or 1, n_sel, D] | None)."""
-    g = _rng("data", c.D, c.H, c.n_rows, c.sel, c.data, c.shared)
+    g = keyed_rng("data", c.D, c.H, c.n_rows, c.sel, c.data, c.shared)
     heads = heads_of(c)
     nv, ns = (1 if c.shared else c.n_rows), len(heads)
     if c.data == "bits":
@@ -226,7 +226,7 @@ def emulate(c: Launch, att, rows, heads, vec, mutant=None):
                 elif mutant == "mul_then_add":
                     new[sl] = _bf16_bits((al * v).astype(np.float32) + widen(x[sl]))
                 else:
-                    new[sl] = _bf16_bits(_fma32(np.full_like(v, al), v, widen(x[sl])))
+                    new[sl] = _bf16_bits(fma32(np.full_like(v, al), v, widen(x[sl])))
             out[row, :c.width] = new
         if c.capture:
             cap[r] = new if mutant == "capture_after" else x

@@ -1,4 +1,4 @@
-"""Support for the residual-stream tests (tests/test_resid_patch_ref.py on the CPU, tests/test_gpu_resid_patch*.py on the GPU): not
+"""Support for the residual-stream tests (tests/test_resid_patch_ref.py on the CPU, tests/test_gpu_resid_patch.py on the GPU): not
 a test module.
 
 1. icl_resid_rows_f32 (include/icl_hip.h): a float64 reference of one launch (``expect``), the assertions every test applies to a
@@ -14,15 +14,11 @@ a test module.
    exactly (non-zero wherever the product was inexact); multiply-then-add returns 0, which misses ref by |ref| — refused.
 
 2. The far-offset case (tests/far_layout.py): ldh = 2^32 + 64, rows 0 and 1.
-
-3. The small decoders of the runtime tests and the same weights as a transformers model on the CPU (``Env``), in the style of
-   tests/test_gpu_attn_knockout.py, with hooks that read and patch HF's residual stream at a site.
 """
-from dataclasses import dataclass, replace
+from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
-import torch
 
 import far_layout as fl
 
@@ -69,20 +65,20 @@ def launch_cases(hidden, n_rows):
     return out
 
 
-def _rng(*key):
+def keyed_rng(*key):
     import zlib
     return np.random.default_rng(zlib.crc32("/".join(str(k) for k in key).encode()))
 
 
 def rows_of(c: Launch):
     """Distinct rows of the 70, never the last one (a row + 1 mutant stays inside), in no particular order."""
-    rows = _rng("rows", c.n_rows).permutation(ROWS_TOTAL - 1)[:c.n_rows].astype(np.int32)
+    rows = keyed_rng("rows", c.n_rows).permutation(ROWS_TOTAL - 1)[:c.n_rows].astype(np.int32)
     return rows[::-1].copy() if c.reverse else rows
 
 
 def inputs(c: Launch):
     """(h f32 [70, hidden + PAD] with the sentinel in the PAD columns, rows int32 [n], vec f32 [n or 1, hidden] | None)."""
-    g = _rng("data", c.hidden, c.n_rows, c.data, c.shared)
+    g = keyed_rng("data", c.hidden, c.n_rows, c.data, c.shared)
     nv = 1 if c.shared else c.n_rows
     if c.data == "bits":
         h = g.standard_normal((ROWS_TOTAL, c.hidden)).astype(np.float32).view(np.uint32)
@@ -157,7 +153,7 @@ def check(c: Launch, e: Expect, h_out, cap_out) -> list:
     return fails, worst
 
 
-def _fma32(a, v, h):
+def fma32(a, v, h):
     """fl32(a * v + h) with ONE rounding, for finite f32 arrays: the product is exact in f64; the f64 sum is taken with round-to-odd
     (TwoSum gives its exact error), which a second rounding to 24 bits cannot turn into a double rounding."""
     p = a.astype(np.float64) * v.astype(np.float64)
@@ -194,7 +190,7 @@ def emulate(c: Launch, h, rows, vec, mutant=None):
             elif mutant == "mul_then_add":
                 new = (a * v).astype(np.float32) + x
             else:
-                new = _fma32(np.full_like(v, a), v, x)
+                new = fma32(np.full_like(v, a), v, x)
             out[row, :c.hidden] = new
         if c.capture:
             cap[r] = new if (mutant == "capture_after" and new is not None) else x
@@ -228,106 +224,3 @@ def far_case():
     n = FAR_HIDDEN
     ops = [fl.stride_op("h", "f32", "inout", n), fl.plain_op("capture", "f32", "out", n, 2), fl.plain_op("vec", "f32", "in", n, 2)]
     return fl.place(fl.Case("resid_rows", "resid", "stride", ops, dict(hidden=n)))
-
-
-# ------------------------------------------------------------------------------------------------------------------
-# 3. the runtime's decoders and their transformers twins
-# ------------------------------------------------------------------------------------------------------------------
-PROMPT_LENS = [33, 90, 61, 12, 130]
-SPEECH_ROW, SPEECH_AT, SPEECH_N = 1, 20, 17          # prompt 1 carries 17 speech rows after its 20th token
-NEW = 4
-N_LAYERS = 3                                         # a first, a middle and a (trimmed, for the multi-head form) last layer
-FORMS = {"mha": (None, False), "gqa-qknorm": (2, True)}
-WEIGHT_SEED = 10_005
-
-
-class Env:
-    """A 3-layer decoder (hidden 512, 4 heads of 128, ``kv`` K/V heads, no LoRA: the HF model holds the same tensors): the state
-    dict, five ragged prompts (one with a speech segment) and the transformers model on the CPU; layer projections small next to
-    the embeddings and the LM head.  ``runtime(device)`` builds the GPU side."""
-
-    def __init__(self, kv, qk_norm, seed=WEIGHT_SEED):
-        from icl_speech_text_llm_amd.runtime import synth
-        from icl_speech_text_llm_amd.runtime.config import SalmonnCfg
-        from icl_speech_text_llm_amd.runtime.salmonn import speech_segment
-        tiny = SalmonnCfg.tiny(use_beats=False, lora=False)
-        self.cfg = replace(tiny, llama=replace(tiny.llama, hidden=512, n_layers=N_LAYERS, n_heads=4, n_kv_heads=kv, ffn=1024,
-                                               qk_norm=qk_norm))
-        g = torch.Generator().manual_seed(seed)
-        self.sd = {}
-        for k, v in synth.salmonn_state(self.cfg, seed=0, jitter=True, parts=("llama",)).items():
-            if v.dim() > 1:
-                v = (torch.randn(v.shape, generator=g) * (0.03 if "_proj" in k else 0.3)).to(torch.bfloat16).float()
-            self.sd[k] = v
-        c = self.cfg.llama
-        g = torch.Generator().manual_seed(17)
-        self.speech = torch.randn(SPEECH_N + 3, c.hidden, generator=g) * 0.3
-        self.prompts = []
-        for b, n in enumerate(PROMPT_LENS):
-            ids = torch.randint(3, c.vocab - 1, (n,), generator=g).tolist()
-            self.prompts.append([ids[:SPEECH_AT], speech_segment(2, SPEECH_N), ids[SPEECH_AT:]] if b == SPEECH_ROW else [ids])
-        self.lens = [n + (SPEECH_N if b == SPEECH_ROW else 0) for b, n in enumerate(PROMPT_LENS)]
-        self.other = [[torch.randint(3, c.vocab - 1, (n,), generator=g).tolist()] for n in (40, 17, 77, 25, 101)]   # a second batch
-
-    def runtime(self, device, **kw):
-        from icl_speech_text_llm_amd.runtime.salmonn import SalmonnRuntime
-        return SalmonnRuntime(self.cfg, dict(self.sd), device=device, parts=("llama",), **kw)
-
-    def hf(self):
-        import transformers as tf
-        c = self.cfg.llama
-        assert c.rope_theta == 10000.0                     # the default of both configurations
-        kw = dict(hidden_size=c.hidden, num_hidden_layers=c.n_layers, num_attention_heads=c.n_heads, num_key_value_heads=c.kv_heads,
-                  intermediate_size=c.ffn, vocab_size=c.vocab, rms_norm_eps=c.rms_eps, max_position_embeddings=c.max_pos,
-                  tie_word_embeddings=False, attention_bias=False, head_dim=c.head_dim, attn_implementation="eager")
-        m = (tf.Qwen3ForCausalLM(tf.Qwen3Config(**kw)) if c.qk_norm else tf.LlamaForCausalLM(tf.LlamaConfig(**kw))).eval()
-        m.load_state_dict({k[len("llama_model."):]: v for k, v in self.sd.items()}, strict=True)
-        return m
-
-    def hf_run(self, m, dtype, tokens, patch=None):
-        """transformers on prompt + the first NEW - 1 tokens of ``tokens`` (teacher-forced), eager attention, in ``dtype``.
-        Forward pre-hooks on the decoder layers and on ``model.norm`` read the residual stream at every site and, with ``patch``
-        = dict(site, vectors f32 [B, hidden] | [1, hidden], mode, alpha, steps, rows | None), rewrite it at one: the last prompt
-        row (``steps="all"``: and every later row) of a listed prompt is replaced by, or gets alpha times, its vector.
-        -> (step logits f64 [NEW, B, V], hidden f64 [B, n_layers + 1, hidden]: the last prompt row at every site, pre-patch,
-        lens logits f64 [B, n_layers + 1, V]: model.norm + lm_head on those rows)."""
-        m, c = m.to(dtype), self.cfg.llama
-        emb = m.get_input_embeddings().weight.detach().float()
-        Bn = len(self.prompts)
-        logits = torch.zeros(NEW, Bn, c.vocab, dtype=torch.float64)
-        hidden = torch.zeros(Bn, c.n_layers + 1, c.hidden, dtype=torch.float64)
-        lens_logits = torch.zeros(Bn, c.n_layers + 1, c.vocab, dtype=torch.float64)
-        mods = list(m.model.layers) + [m.model.norm]
-        for b, segs in enumerate(self.prompts):
-            x = torch.cat([self.speech[s[1]:s[1] + s[2]] if isinstance(s, tuple) else emb[torch.tensor(s)] for s in segs]
-                          + [emb[tokens[b, :NEW - 1]]])
-            n = self.lens[b]
-            seen, kept = [], {}
-
-            def hook(mod, args, kwargs, site=None, b=b, n=n, seen=seen, kept=kept):
-                hs = args[0] if args else kwargs["hidden_states"]
-                seen.append(site)
-                kept[site] = hs[:, n - 1:n].clone()
-                if patch is None or patch["site"] != site or (patch.get("rows") is not None and b not in patch["rows"]):
-                    return None
-                v = patch["vectors"]
-                v = (v[0] if v.shape[0] == 1 else v[b]).to(hs.dtype)
-                hs = hs.clone()
-                sl = slice(n - 1, None) if patch.get("steps", "prompt") == "all" else slice(n - 1, n)
-                hs[0, sl] = v if patch.get("mode", "replace") == "replace" else hs[0, sl] + patch.get("alpha", 1.0) * v
-                return ((hs,) + tuple(args[1:]), kwargs) if args else (args, dict(kwargs, hidden_states=hs))
-            hooks = [mod.register_forward_pre_hook(lambda mo, a, k, s=s: hook(mo, a, k, site=s), with_kwargs=True)
-                     for s, mod in enumerate(mods)]
-            try:
-                with torch.no_grad():
-                    lg = m(inputs_embeds=x[None].to(dtype)).logits[0]
-            finally:
-                for h in hooks:
-                    h.remove()
-            assert seen == list(range(c.n_layers + 1)), seen
-            with torch.no_grad():                           # the hooks are gone: model.norm can be used for the lens
-                for site, row in kept.items():
-                    hidden[b, site] = row[0, 0].double()
-                    lens_logits[b, site] = m.lm_head(m.model.norm(row))[0, 0].double()
-            logits[:, b] = lg[n - 1:].double()
-        return logits, hidden, lens_logits

@@ -15,10 +15,10 @@ Which test reaches which instantiation (attn_decode_kernel<D, UNR, false, false,
 Tests (a) - (g) of a form: test_bound (a), test_count_probe (b), test_blocked_peak_probe (c), test_all_masks_zero (d),
 test_unlisted_rows_untouched (e), test_batch_invariance (f), test_binding_refuses_what_the_entry_point_refuses (g).
 
-Runtime: 2-layer decoders of hidden 512 (multi-head with the trimmed last layer, grouped 4/2, grouped 4/2 QK-norm), five ragged
-prompts, one with a speech segment, weights in the style of tests/golden/e2e_weights.py (layer projections small next to the
-embeddings and the LM head).  Per step: rel-L2 of the logits against the same transformers model in fp32
-on the CPU, on prompt + generated tokens under the 4-D mask of the knockout (rows >= len - 1, blocked columns at -inf, swapped in
+Runtime (the harness of tests/probe_harness.py): 2-layer decoders of hidden 512 (multi-head with the trimmed last layer, grouped
+4/2, grouped 4/2 QK-norm), five ragged prompts, one with a speech segment, weights in the style of tests/golden/e2e_weights.py
+(layer projections small next to the embeddings and the LM head).  Per step: rel-L2 of the logits against the same transformers
+model in fp32 on the CPU, on prompt + generated tokens under the 4-D mask of the knockout (rows >= len - 1, blocked columns at -inf, swapped in
 per decoder layer by a forward pre-hook); allowed: 1.25 x the rel-L2 of that model in bf16 against itself in fp32 under the same mask
 (the project's ratio criterion).  Both figures are printed.
 
@@ -28,20 +28,18 @@ and at most 1 bf16 ulp from the unmasked kernels (D64-H3: 99.98 % of the element
 HF fp32 next to HF bf16 against HF fp32, rel-L2, largest ratio of the four steps: multi-head 0.47 (all layers) / 0.46 (window
 (1, 2)), grouped 0.45 / 0.47, grouped QK-norm 0.48 / 0.44.
 """
-from dataclasses import replace
 from functools import lru_cache
 
 import pytest
 import torch
 
 import attn_knockout_ref as kr
-from decoder_support import salmonn_batch
+import probe_harness as ph
 from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
 from oracle import attention as oa
 
 pytestmark = pytest.mark.gpu
 
-PARITY_RATIO = 1.25
 SENTINEL = 0x7FA5                   # a NaN bit pattern no kernel writes (int16 view of bf16)
 LENS = list(kr.LENS)
 SIZES = ("few", "many")
@@ -277,89 +275,28 @@ def test_binding_refuses_what_the_entry_point_refuses(B):
 # ------------------------------------------------------------------------------------------------------------------
 # the runtime
 # ------------------------------------------------------------------------------------------------------------------
-PROMPT_LENS = [33, 90, 61, 12, 130]
-SPEECH_ROW, SPEECH_AT, SPEECH_N = 1, 20, 17          # prompt 1 carries 17 speech rows after its 20th token
-NEW = 4
-WEIGHT_SEED = 10_005       # of 40 seeds, the one with the widest smallest fp32 greedy margin of transformers on the CPU
+NEW = ph.NEW
 BLOCKED = [[1], [1, 2], [0, 3], [2], [0, 1]]        # per prompt; row 1 blocks its speech segment (1) and the text after it
 
 
-class _Env:
-    """A 2-layer decoder (hidden 512, 4 heads of 128, ``kv`` K/V heads, no LoRA: the HF model holds the same tensors) on the GPU and
-    the same weights as a transformers model on the CPU; layer projections small next to the embeddings and the LM head."""
+class _Env(ph.Decoder):
+    """The 2-layer decoder of tests/probe_harness.py on the GPU, weights drawn from its ``WEIGHT_SEED``."""
 
     def __init__(self, kv, qk_norm):
-        from icl_speech_text_llm_amd.runtime import synth
-        from icl_speech_text_llm_amd.runtime.config import SalmonnCfg
-        from icl_speech_text_llm_amd.runtime.salmonn import SalmonnRuntime, speech_segment
-        tiny = SalmonnCfg.tiny(use_beats=False, lora=False)
-        self.cfg = replace(tiny, llama=replace(tiny.llama, hidden=512, n_layers=2, n_heads=4, n_kv_heads=kv, ffn=1024, qk_norm=qk_norm))
-        g = torch.Generator().manual_seed(WEIGHT_SEED)
-        self.sd = {}
-        for k, v in synth.salmonn_state(self.cfg, seed=0, jitter=True, parts=("llama",)).items():
-            if v.dim() > 1:
-                v = (torch.randn(v.shape, generator=g) * (0.03 if "_proj" in k else 0.3)).to(torch.bfloat16).float()
-            self.sd[k] = v
-        self.rt = SalmonnRuntime(self.cfg, dict(self.sd), device=DEV, parts=("llama",))
-        c = self.cfg.llama
-        g = torch.Generator().manual_seed(17)
-        self.speech = torch.randn(SPEECH_N + 3, c.hidden, generator=g) * 0.3
-        self.prompts, self.segments = [], []
-        for b, n in enumerate(PROMPT_LENS):
-            ids = torch.randint(3, c.vocab - 1, (n,), generator=g).tolist()
-            if b == SPEECH_ROW:
-                self.prompts.append([ids[:SPEECH_AT], speech_segment(2, SPEECH_N), ids[SPEECH_AT:]])
-                sg = [0] * SPEECH_AT + [1] * SPEECH_N + [2] * (n - SPEECH_AT)
-            else:
-                sg = [min(j * 4 // n, 3) for j in range(n)]              # four runs ...
-                sg[n // 2] = 255                                          # ... with one position that can never be blocked
-                sg[n - 1] = 40                                            # ... and the last one under an id >= 32
-                self.prompts.append([ids])
-            self.segments.append(sg)
-        self.lens = [len(s) for s in self.segments]
-
-    def hf(self):
-        import transformers as tf
-        c = self.cfg.llama
-        assert c.rope_theta == 10000.0                     # the default of both configurations
-        kw = dict(hidden_size=c.hidden, num_hidden_layers=c.n_layers, num_attention_heads=c.n_heads, num_key_value_heads=c.kv_heads,
-                  intermediate_size=c.ffn, vocab_size=c.vocab, rms_norm_eps=c.rms_eps, max_position_embeddings=c.max_pos,
-                  tie_word_embeddings=False, attention_bias=False, head_dim=c.head_dim, attn_implementation="eager")
-        m = (tf.Qwen3ForCausalLM(tf.Qwen3Config(**kw)) if c.qk_norm else tf.LlamaForCausalLM(tf.LlamaConfig(**kw))).eval()
-        m.load_state_dict({k[len("llama_model."):]: v for k, v in self.sd.items()}, strict=True)
-        return m
+        super().__init__(kv, qk_norm, n_layers=2)
+        self.rt = self.runtime(DEV)
+        # four runs with one position that can never be blocked and the last one under an id >= 32
+        self.segments = [ph.four_runs(n, {n // 2: 255, n - 1: 40}) for n in ph.PROMPT_LENS]
+        self.segments[ph.SPEECH_ROW] = ph.speech_row_runs()
 
     def hf_step_logits(self, m, dtype, tokens, blocked, layers):
-        """f64 [NEW, B, V]: transformers' eager attention on prompt + the first NEW - 1 tokens of ``tokens``, the knockout's 4-D
-        additive mask given to the decoder layers of the window by a forward pre-hook (the others keep the causal mask); the
-        logits at positions len - 1 .. len + NEW - 2."""
-        m, c = m.to(dtype), self.cfg.llama
-        emb = m.get_input_embeddings().weight.detach().float()
-        out = torch.zeros(NEW, len(self.prompts), c.vocab, dtype=torch.float64)
-        for b, segs in enumerate(self.prompts):
-            x = torch.cat([self.speech[s[1]:s[1] + s[2]] if isinstance(s, tuple) else emb[torch.tensor(s)] for s in segs]
-                          + [emb[tokens[b, :NEW - 1]]])
-            n, T = self.lens[b], self.lens[b] + NEW - 1
+        """f64 [NEW, B, V]: transformers, teacher-forced, under the knockout's mask in the decoder layers of the window: rows
+        >= len - 1, blocked columns (generated keys are 255) at -inf."""
+        def fill_dead(b, n, dead):
             ids = torch.tensor(self.segments[b] + [255] * (NEW - 1))
-            dead = torch.triu(torch.ones(T, T, dtype=torch.bool), 1)
-            cols = torch.isin(ids, torch.tensor(blocked[b], dtype=torch.long)) & (ids < 32)
-            dead[n - 1:] |= cols[None]
-            mask = torch.zeros(T, T, dtype=dtype).masked_fill(dead, float("-inf"))[None, None]
-            seen = []
-
-            def hook(mod, args, kwargs, mask=mask, seen=seen):
-                assert "attention_mask" in kwargs, "the decoder layers do not take the mask as a keyword"
-                seen.append(1)
-                return args, dict(kwargs, attention_mask=mask)
-            hooks = [m.model.layers[i].register_forward_pre_hook(hook, with_kwargs=True) for i in range(*layers)]
-            try:
-                with torch.no_grad():
-                    lg = m(inputs_embeds=x[None].to(dtype)).logits[0]
-            finally:
-                for h in hooks:
-                    h.remove()
-            assert len(seen) == layers[1] - layers[0]
-            out[:, b] = lg[n - 1:].double()
+            dead[n - 1:] |= (torch.isin(ids, torch.tensor(blocked[b], dtype=torch.long)) & (ids < 32))[None]
+        out, fired = ph.masked_run(self, m, dtype, tokens, fill_dead, layers)
+        assert fired == [layers[1] - layers[0]] * len(self.prompts)
         return out
 
 
@@ -386,24 +323,8 @@ def test_runtime_against_transformers(env, layers):
     want32 = env.hf_step_logits(hf, torch.float32, res.tokens, BLOCKED, window)
     want16 = env.hf_step_logits(hf, torch.bfloat16, res.tokens, BLOCKED, window)
     free32 = env.hf_step_logits(hf, torch.float32, res.tokens, [[]] * len(BLOCKED), window)
-    rel = lambda a, b: float((a - b).norm() / b.norm())
-    for t in range(NEW):
-        own, mine, effect = rel(want16[t], want32[t]), rel(got[t], want32[t]), rel(free32[t], want32[t])
-        print(f"knockout kv={c.n_kv_heads} qk_norm={c.qk_norm} layers={window} step {t}: rel-L2 vs HF fp32 {mine:.3e}; HF bf16 vs HF fp32 "
-              f"{own:.3e}; ratio {mine / own:.3f} (allowed {PARITY_RATIO}); the knockout moves HF's logits by {effect:.3e}")
-        assert effect > 4 * own, "the mask does not reach transformers' attention: the reference would prove nothing"
-        assert mine <= PARITY_RATIO * own, f"step {t}"
-    # greedy tokens: HF fp32's (teacher-forced on the same tokens) wherever its margin is decisive.  With 20 decisions per run over a
-    # vocabulary of random logits some top-1 / top-2 gaps are always next to nothing, so "decisive" is decided on the reference
-    # alone: a gap above 2 x 1.25 x the largest |HF bf16 - HF fp32| logit error (both sides of the gap may move by the allowed error)
-    top2 = want32.topk(2, dim=-1).values
-    margin = (top2[..., 0] - top2[..., 1]).t()                                   # [B, NEW]
-    noise = float((want16 - want32).abs().max())
-    decisive = margin > 2 * PARITY_RATIO * noise
-    print(f"top-1 / top-2 margins of HF fp32: {int(decisive.sum())} of {decisive.numel()} above {2 * PARITY_RATIO * noise:.3f} (smallest "
-          f"{float(margin.min()):.3f}); largest |logit difference| to HF fp32 {float((got - want32).abs().max()):.3e}")
-    assert int(decisive.sum()) >= decisive.numel() // 3
-    assert torch.equal(res.tokens[decisive], want32.argmax(-1).t()[decisive])
+    ph.parity_check(got, want32, want16, free32, res.tokens, f"knockout kv={c.n_kv_heads} qk_norm={c.qk_norm} layers={window}",
+                    effect_floor=4, min_decisive=res.tokens.numel() // 3, moves="the knockout moves")
     assert not torch.equal(res.step_logits, plain.step_logits)
 
 
@@ -424,11 +345,8 @@ def test_runtime_mixed_batch_and_empty_sets(env):
         else:
             assert torch.equal(mixed.step_logits[:, b], plain.step_logits[:, b]) and torch.equal(mixed.tokens[b], plain.tokens[b]), b
             assert torch.equal(mixed.first_logits[b], plain.first_logits[b]), b
-    try:
-        rt.prefill_chunk = 2
+    with ph.prefill_chunks(rt, 2):
         chunked = rt.generate(env.prompts, sp, knockout=_knockout(env, blocked=mixed_sets), **kw)
-    finally:
-        del rt.prefill_chunk
     assert torch.equal(chunked.step_logits, mixed.step_logits) and torch.equal(chunked.tokens, mixed.tokens)
     # twice more: the second call captures the decode graph, the third replays it
     for _ in range(2):
@@ -467,7 +385,6 @@ def test_runtime_other_tails(env):
 
 
 def test_runtime_refusals(env):
-    from icl_speech_text_llm_amd.runtime.salmonn import SalmonnRuntime
     rt, c = env.rt, env.cfg.llama
     sp = env.speech.to(DEV)
     gen = lambda ko, **kw: rt.generate(env.prompts, sp, max_new_tokens=2, knockout=ko, **kw)
@@ -504,7 +421,7 @@ def test_runtime_refusals(env):
     want = rt.generate(env.prompts, sp, max_new_tokens=NEW, suppress_eos=True, want_step_logits=True, knockout=_knockout(env))
     assert res.dropped == (5,) and torch.equal(res.step_logits[:, :5], want.step_logits) and torch.equal(res.tokens[:5], want.tokens)
     if c.group == 1 and not c.qk_norm:                                       # the FP8 KV cache exists for this form only
-        r8 = SalmonnRuntime(env.cfg, dict(env.sd), device=DEV, parts=("llama",), llm_kv_dtype="fp8")
+        r8 = env.runtime(DEV, llm_kv_dtype="fp8")
         with pytest.raises(ValueError, match="bf16 KV cache"):
             r8.generate(env.prompts, sp, max_new_tokens=2, knockout=_knockout(env))
 
@@ -556,27 +473,15 @@ def test_launch_trace():
 # the plugin
 # ------------------------------------------------------------------------------------------------------------------
 def test_plugin():
-    from icl_speech_text_llm_amd.models.model_factory import ModelFactory
-    model = ModelFactory.create_model("salmonn", device="cuda", arch="tiny", low_resource=True, llama_path="none", lora_alpha=32).eval()
-    b = salmonn_batch(model, "speech", n=2, bs=2, num_examples=2)
-    b = {k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
-    seen = {}
-    real = model.runtime.generate
-
-    def generate(segs, speech, **kw):
-        seen.update(kw)
-        return real(segs, speech, **kw)
-    model.runtime.generate = generate
-    try:
+    model, b = ph.tiny_plugin_batches(2)
+    with ph.spy_generate(model) as seen:
         out = model.generate_knockout(dict(b), [("example", 1)])
-    finally:
-        del model.runtime.generate
     assert set(out) == {"texts", "tokens", "first_logits", "pieces"}
     c = model.cfg.llama
     assert len(out["texts"]) == 2 and out["tokens"].shape[0] == 2 and out["first_logits"].shape == (2, c.vocab)
     att = model.prompt_attention(dict(b))
     assert out["pieces"] == att["pieces"]
-    segments, blocked, layers, heads = seen["knockout"]
+    segments, blocked, layers, heads = seen["kw"]["knockout"]
     assert layers is None and heads is None
     assert blocked == [[pc.index(("example", 1))] for pc in out["pieces"]]
     for sg, pc in zip(segments, out["pieces"]):                                  # the ids of prompt_attention's pieces

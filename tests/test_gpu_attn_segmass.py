@@ -20,18 +20,15 @@ Measured on MI355X (printed by the tests, recorded in README.md): largest err / 
 absolute term.  Mass against HF fp32, rel-L2, next to HF bf16 against HF fp32: multi-head 6.08e-4 / 1.07e-3 (ratio 0.57), grouped
 6.50e-4 / 1.02e-3 (0.64), grouped QK-norm 3.42e-3 / 6.26e-3 (0.55), multi-head QK-norm 3.37e-3 / 6.40e-3 (0.53).
 """
-from dataclasses import replace
-
 import pytest
 import torch
 
 import attn_segmass_ref as sr
-from decoder_support import salmonn_batch
+import probe_harness as ph
 from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-PARITY_RATIO = 1.25
 NAN = float("nan")
 
 
@@ -145,48 +142,15 @@ def test_binding_refuses_what_the_entry_point_refuses(B):
 # ------------------------------------------------------------------------------------------------------------------
 # the runtime
 # ------------------------------------------------------------------------------------------------------------------
-PROMPT_LENS = [33, 90, 61, 12, 130]
-SPEECH_ROW, SPEECH_AT, SPEECH_N = 1, 20, 17          # prompt 1 carries 17 speech rows after its 20th token
-
-
-class _Env:
-    """A 2-layer decoder (hidden 512, 4 heads of 128, ``kv`` K/V heads, no LoRA: the HF model holds the same tensors) on the GPU and
-    the same weights as a transformers model on the CPU."""
+class _Env(ph.Decoder):
+    """The 2-layer decoder of tests/probe_harness.py on the GPU, with the ``synth.salmonn_state`` weights as they are."""
 
     def __init__(self, kv, qk_norm):
-        from icl_speech_text_llm_amd.runtime import synth
-        from icl_speech_text_llm_amd.runtime.config import SalmonnCfg
-        from icl_speech_text_llm_amd.runtime.salmonn import SalmonnRuntime, speech_segment
-        tiny = SalmonnCfg.tiny(use_beats=False, lora=False)
-        self.cfg = replace(tiny, llama=replace(tiny.llama, hidden=512, n_layers=2, n_heads=4, n_kv_heads=kv, ffn=1024, qk_norm=qk_norm))
-        self.sd = synth.salmonn_state(self.cfg, seed=0, jitter=True, parts=("llama",))
-        self.rt = SalmonnRuntime(self.cfg, dict(self.sd), device=DEV, parts=("llama",))
-        c = self.cfg.llama
-        g = torch.Generator().manual_seed(17)
-        self.speech = torch.randn(SPEECH_N + 3, c.hidden, generator=g) * 0.05
-        self.prompts, self.segments = [], []
-        for b, n in enumerate(PROMPT_LENS):
-            ids = torch.randint(3, c.vocab - 1, (n,), generator=g).tolist()
-            if b == SPEECH_ROW:
-                self.prompts.append([ids[:SPEECH_AT], speech_segment(2, SPEECH_N), ids[SPEECH_AT:]])
-                sg = [0] * SPEECH_AT + [1] * SPEECH_N + [2] * (n - SPEECH_AT)
-            else:
-                sg = [min(j * 4 // n, 3) for j in range(n)]              # four runs ...
-                sg[n // 2] = 255                                          # ... with one position ignored
-                self.prompts.append([ids])
-            self.segments.append(sg)
+        super().__init__(kv, qk_norm, n_layers=2, redraw=False, speech_scale=0.05)
+        self.rt = self.runtime(DEV)
+        self.segments = [ph.four_runs(n, {n // 2: 255}) for n in ph.PROMPT_LENS]        # four runs with one position ignored
+        self.segments[ph.SPEECH_ROW] = ph.speech_row_runs()
         self.n_seg = 4
-
-    def hf(self):
-        import transformers as tf
-        c = self.cfg.llama
-        assert c.rope_theta == 10000.0                     # the default of both configurations
-        kw = dict(hidden_size=c.hidden, num_hidden_layers=c.n_layers, num_attention_heads=c.n_heads, num_key_value_heads=c.kv_heads,
-                  intermediate_size=c.ffn, vocab_size=c.vocab, rms_norm_eps=c.rms_eps, max_position_embeddings=c.max_pos,
-                  tie_word_embeddings=False, attention_bias=False, head_dim=c.head_dim, attn_implementation="eager")
-        m = (tf.Qwen3ForCausalLM(tf.Qwen3Config(**kw)) if c.qk_norm else tf.LlamaForCausalLM(tf.LlamaConfig(**kw))).eval()
-        m.load_state_dict({k[len("llama_model."):]: v for k, v in self.sd.items()}, strict=True)
-        return m
 
     def hf_mass(self, m, dtype):
         """[B, n_layers, n_heads, n_seg] float64: the last query row of transformers' eager attention, summed per segment."""
@@ -215,7 +179,7 @@ def test_runtime(env):
     sp = env.speech.to(DEV)
     res = rt.prompt_attention(env.prompts, sp, env.segments, want_probs=True)
     lens = res.lens
-    assert lens == [n + (SPEECH_N if b == SPEECH_ROW else 0) for b, n in enumerate(PROMPT_LENS)]
+    assert lens == env.lens
     assert res.mass.shape == (len(lens), c.n_layers, c.n_heads, env.n_seg) and res.mass.device.type == "cpu"
     assert res.probs.shape[:3] == (len(lens), c.n_layers, c.n_heads) and res.probs.shape[3] >= max(lens)
     # first logits: generate's, bit for bit (and again after the readout: the default path is undisturbed)
@@ -225,11 +189,8 @@ def test_runtime(env):
                        gen.first_logits)
     # without probs, and in chunks of two sequences: the same mass bits
     assert torch.equal(rt.prompt_attention(env.prompts, sp, env.segments).mass, res.mass)
-    try:
-        rt.prefill_chunk = 2
+    with ph.prefill_chunks(rt, 2):
         chunked = rt.prompt_attention(env.prompts, sp, env.segments, want_probs=True)
-    finally:
-        del rt.prefill_chunk
     assert torch.equal(chunked.mass, res.mass) and torch.equal(chunked.probs, res.probs) and torch.equal(chunked.first_logits, res.first_logits)
     # every layer's mass is the segmented sum of its probs: float64 recomputation, the f32 sum bound c2 * n_g * u of the reference module
     probs = res.probs.double().cpu()
@@ -244,15 +205,13 @@ def test_runtime(env):
     hf = env.hf()
     want32 = env.hf_mass(hf, torch.float32)
     want16 = env.hf_mass(hf, torch.bfloat16)
-    rel = lambda a, b: float((a - b).norm() / b.norm())
-    own, got = rel(want16, want32), rel(res.mass.double(), want32)
+    own, got = ph.rel(want16, want32), ph.rel(res.mass.double(), want32)
     print(f"prompt_attention kv={c.n_kv_heads} qk_norm={c.qk_norm}: rel-L2 of mass vs HF fp32 {got:.3e}; HF bf16 vs HF fp32 {own:.3e}; "
-          f"ratio {got / own:.3f} (allowed {PARITY_RATIO})")
-    assert got <= PARITY_RATIO * own
+          f"ratio {got / own:.3f} (allowed {ph.PARITY_RATIO})")
+    assert got <= ph.PARITY_RATIO * own
 
 
 def test_runtime_refusals(env):
-    from icl_speech_text_llm_amd.runtime.salmonn import SalmonnRuntime
     rt, c = env.rt, env.cfg.llama
     sp = env.speech.to(DEV)
     before = rt.ws.nbytes()
@@ -266,7 +225,7 @@ def test_runtime_refusals(env):
         rt.prompt_attention([[[5] * (c.max_pos + 1)]], None, [[0] * (c.max_pos + 1)])
     assert rt.ws.nbytes() == before                                          # nothing was sized, nothing launched
     if c.group == 1 and not c.qk_norm:                                       # the FP8 KV cache exists for this form only
-        r8 = SalmonnRuntime(env.cfg, dict(env.sd), device=DEV, parts=("llama",), llm_kv_dtype="fp8")
+        r8 = env.runtime(DEV, llm_kv_dtype="fp8")
         with pytest.raises(ValueError, match="bf16 KV cache"):
             r8.prompt_attention(env.prompts, sp, env.segments)
 
@@ -275,10 +234,7 @@ def test_runtime_refusals(env):
 # the plugin
 # ------------------------------------------------------------------------------------------------------------------
 def test_plugin():
-    from icl_speech_text_llm_amd.models.model_factory import ModelFactory
-    model = ModelFactory.create_model("salmonn", device="cuda", arch="tiny", low_resource=True, llama_path="none", lora_alpha=32).eval()
-    b = salmonn_batch(model, "speech", n=2, bs=2, num_examples=2)
-    b = {k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
+    model, b = ph.tiny_plugin_batches(2)
     out = model.prompt_attention(dict(b))
     assert set(out) == {"mass", "pieces", "first_logits"}
     c = model.cfg.llama

@@ -1,7 +1,7 @@
 """`-m gpu`: ``generate(cuts=...)`` — attention cuts between prompt segments, edges whose QUERY is an interior prompt row — on the
-harness of tests/test_gpu_attn_knockout.py (its ``_Env``, restated: no test module imports another) at THREE layers (hidden 512, 4 heads of 128: multi-head with the trimmed last
-layer, and grouped 4 / 2 with QK-norm), five ragged prompts of 33 / 90 / 61 / 12 / 130 positions in four equal segment runs, one with
-a speech segment, four new tokens.
+harness of tests/probe_harness.py, which tests/test_gpu_attn_knockout.py uses at two layers, at THREE (hidden 512, 4 heads of 128:
+multi-head with the trimmed last layer, and grouped 4 / 2 with QK-norm), five ragged prompts of 33 / 90 / 61 / 12 / 130 positions in
+four equal segment runs, one with a speech segment, four new tokens.
 
 Bit for bit: cuts on interior rows in the last layer alone are the plain run (no other row of that layer can influence anything);
 prefill chunks of two are one chunk; a replayed decode graph is the eager run; in a mixed batch the prompts without pairs are the
@@ -15,107 +15,45 @@ fp32); the cut moves HF's logits by more than 4 x HF's bf16 error; the GPU's gre
 
 Measured on MI355X: see README.md ("Attention cuts").
 """
-from dataclasses import replace
-
 import pytest
 import torch
 
-from decoder_support import salmonn_batch
+import probe_harness as ph
 from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
+from probe_harness import same_result as _same
 
 pytestmark = pytest.mark.gpu
 
-PARITY_RATIO = 1.25
-PROMPT_LENS = [33, 90, 61, 12, 130]
-SPEECH_ROW, SPEECH_AT, SPEECH_N = 1, 20, 17          # prompt 1 carries 17 speech rows after its 20th token
-NEW = 4
-WEIGHT_SEED = 10_005       # the knockout harness's; the two conditions on the reference alone were re-checked on the CPU at 3 layers
-
+NEW = ph.NEW
 N_LAYERS = 3
 INTERIOR = dict(pairs=[(1, 0), (2, 1)], generated=255)        # no last row (segment 3) and no generated row is touched
 DECIDING = dict(pairs=[(1, 0), (3, 1)], generated=3)          # the last rows and the generated rows do not read segment 1
 CASES = {"interior-layers-0-2": (INTERIOR, (0, 2)), "interior-layer-0": (INTERIOR, (0, 1)), "interior-and-deciding-all-layers": (DECIDING, None)}
 
 
-class _Env3:
-    """A 3-layer decoder (hidden 512, 4 heads of 128, ``kv`` K/V heads, no LoRA: the HF model holds the same tensors) on the GPU and
-    the same weights as a transformers model on the CPU; layer projections small next to the embeddings and the LM head; four equal
-    segment runs per prompt (the speech rows of prompt 1 fall where they fall)."""
+class _Env3(ph.Decoder):
+    """The harness's decoder at 3 layers on the GPU; four equal segment runs per prompt (the speech rows of prompt 1 fall where
+    they fall)."""
 
     def __init__(self, kv, qk_norm):
-        from icl_speech_text_llm_amd.runtime import synth
-        from icl_speech_text_llm_amd.runtime.config import SalmonnCfg
-        from icl_speech_text_llm_amd.runtime.salmonn import SalmonnRuntime, speech_segment
-        tiny = SalmonnCfg.tiny(use_beats=False, lora=False)
-        self.cfg = replace(tiny, llama=replace(tiny.llama, hidden=512, n_layers=N_LAYERS, n_heads=4, n_kv_heads=kv, ffn=1024, qk_norm=qk_norm))
-        g = torch.Generator().manual_seed(WEIGHT_SEED)
-        self.sd = {}
-        for k, v in synth.salmonn_state(self.cfg, seed=0, jitter=True, parts=("llama",)).items():
-            if v.dim() > 1:
-                v = (torch.randn(v.shape, generator=g) * (0.03 if "_proj" in k else 0.3)).to(torch.bfloat16).float()
-            self.sd[k] = v
-        self.rt = SalmonnRuntime(self.cfg, dict(self.sd), device=DEV, parts=("llama",))
-        c = self.cfg.llama
-        g = torch.Generator().manual_seed(17)
-        self.speech = torch.randn(SPEECH_N + 3, c.hidden, generator=g) * 0.3
-        self.prompts, self.segments = [], []
-        for b, n in enumerate(PROMPT_LENS):
-            ids = torch.randint(3, c.vocab - 1, (n,), generator=g).tolist()
-            if b == SPEECH_ROW:
-                self.prompts.append([ids[:SPEECH_AT], speech_segment(2, SPEECH_N), ids[SPEECH_AT:]])
-                n += SPEECH_N
-            else:
-                self.prompts.append([ids])
-            self.segments.append([j * 4 // n for j in range(n)])
-        self.lens = [len(s) for s in self.segments]
-
-    def hf(self):
-        import transformers as tf
-        c = self.cfg.llama
-        assert c.rope_theta == 10000.0                     # the default of both configurations
-        kw = dict(hidden_size=c.hidden, num_hidden_layers=c.n_layers, num_attention_heads=c.n_heads, num_key_value_heads=c.kv_heads,
-                  intermediate_size=c.ffn, vocab_size=c.vocab, rms_norm_eps=c.rms_eps, max_position_embeddings=c.max_pos,
-                  tie_word_embeddings=False, attention_bias=False, head_dim=c.head_dim, attn_implementation="eager")
-        m = (tf.Qwen3ForCausalLM(tf.Qwen3Config(**kw)) if c.qk_norm else tf.LlamaForCausalLM(tf.LlamaConfig(**kw))).eval()
-        m.load_state_dict({k[len("llama_model."):]: v for k, v in self.sd.items()}, strict=True)
-        return m
+        super().__init__(kv, qk_norm, n_layers=N_LAYERS)
+        self.rt = self.runtime(DEV)
+        self.segments = [ph.four_runs(n) for n in self.lens]
 
     def cuts(self, case, layers=None, **kw):
         return dict(segments=self.segments, layers=layers, **{**case, **kw})
 
     def hf_cut_logits(self, m, dtype, tokens, pairs, generated, layers):
-        """f64 [NEW, B, V]: transformers' eager attention on prompt + the first NEW - 1 tokens of ``tokens`` under the cuts' 4-D
-        additive mask, given to the decoder layers of the window by a forward pre-hook (the others keep the causal mask); the
-        logits at positions len - 1 .. len + NEW - 2.  ``pairs``: one list for all prompts."""
-        m, c = m.to(dtype), self.cfg.llama
-        emb = m.get_input_embeddings().weight.detach().float()
-        out = torch.zeros(NEW, len(self.prompts), c.vocab, dtype=torch.float64)
-        for b, segs in enumerate(self.prompts):
-            x = torch.cat([self.speech[s[1]:s[1] + s[2]] if isinstance(s, tuple) else emb[torch.tensor(s)] for s in segs]
-                          + [emb[tokens[b, :NEW - 1]]])
-            n, T = self.lens[b], self.lens[b] + NEW - 1
+        """f64 [NEW, B, V]: transformers, teacher-forced, under the cuts' mask in the decoder layers of the window.  ``pairs``: one
+        list for all prompts."""
+        def fill_dead(b, n, dead):
             key_ids = torch.tensor(self.segments[b] + [255] * (NEW - 1))
             query_ids = torch.tensor(self.segments[b] + [generated] * (NEW - 1))
-            dead = torch.triu(torch.ones(T, T, dtype=torch.bool), 1)
             for qs, ks in pairs:
                 dead |= (query_ids == qs)[:, None] & (key_ids == ks)[None]
             assert not bool(dead.all(1).any())
-            mask = torch.zeros(T, T, dtype=dtype).masked_fill(dead, float("-inf"))[None, None]
-            seen = []
-
-            def hook(mod, args, kwargs, mask=mask, seen=seen):
-                assert "attention_mask" in kwargs, "the decoder layers do not take the mask as a keyword"
-                seen.append(1)
-                return args, dict(kwargs, attention_mask=mask)
-            hooks = [m.model.layers[i].register_forward_pre_hook(hook, with_kwargs=True) for i in range(*layers)]
-            try:
-                with torch.no_grad():
-                    lg = m(inputs_embeds=x[None].to(dtype)).logits[0]
-            finally:
-                for h in hooks:
-                    h.remove()
-            assert len(seen) == layers[1] - layers[0]
-            out[:, b] = lg[n - 1:].double()
+        out, fired = ph.masked_run(self, m, dtype, tokens, fill_dead, layers)
+        assert fired == [layers[1] - layers[0]] * len(self.prompts)
         return out
 
 
@@ -132,10 +70,6 @@ def plain(env):
     return env.rt.generate(env.prompts, env.speech.to(DEV), **KW)
 
 
-def _same(a, b):
-    return torch.equal(a.step_logits, b.step_logits) and torch.equal(a.tokens, b.tokens) and torch.equal(a.first_logits, b.first_logits)
-
-
 @pytest.mark.parametrize("name", list(CASES))
 def test_runtime_against_transformers(env, plain, name):
     case, layers = CASES[name]
@@ -148,21 +82,8 @@ def test_runtime_against_transformers(env, plain, name):
     want32 = env.hf_cut_logits(hf, torch.float32, res.tokens, case["pairs"], case["generated"], window)
     want16 = env.hf_cut_logits(hf, torch.bfloat16, res.tokens, case["pairs"], case["generated"], window)
     free32 = env.hf_cut_logits(hf, torch.float32, res.tokens, [], 255, window)
-    rel = lambda a, b: float((a - b).norm() / b.norm())
-    for t in range(NEW):
-        own, mine, effect = rel(want16[t], want32[t]), rel(got[t], want32[t]), rel(free32[t], want32[t])
-        print(f"cuts {name} kv={c.n_kv_heads} qk_norm={c.qk_norm} step {t}: rel-L2 vs HF fp32 {mine:.3e}; HF bf16 vs HF fp32 {own:.3e}; "
-              f"ratio {mine / own:.3f} (allowed {PARITY_RATIO}); the cuts move HF's logits by {effect:.3e} ({effect / own:.1f} x)")
-        assert effect > 4 * own, "the mask does not reach transformers' attention: the reference would prove nothing"
-        assert mine <= PARITY_RATIO * own, f"step {t}"
-    top2 = want32.topk(2, dim=-1).values
-    margin = (top2[..., 0] - top2[..., 1]).t()                                   # [B, NEW]
-    noise = float((want16 - want32).abs().max())
-    decisive = margin > 2 * PARITY_RATIO * noise
-    print(f"cuts {name}: top-1 / top-2 margins of HF fp32: {int(decisive.sum())} of {decisive.numel()} above {2 * PARITY_RATIO * noise:.3f}; "
-          f"largest |logit difference| to HF fp32 {float((got - want32).abs().max()):.3e}")
-    assert int(decisive.sum()) >= decisive.numel() // 3 + 1
-    assert torch.equal(res.tokens[decisive], want32.argmax(-1).t()[decisive])
+    ph.parity_check(got, want32, want16, free32, res.tokens, f"cuts {name} kv={c.n_kv_heads} qk_norm={c.qk_norm}",
+                    effect_floor=4, min_decisive=res.tokens.numel() // 3 + 1, moves="the cuts move")
     assert not torch.equal(res.step_logits, plain.step_logits)
 
 
@@ -179,11 +100,8 @@ def test_chunks_graph_replay_and_captures_change_nothing(env):
     rt, sp = env.rt, env.speech.to(DEV)
     for case, layers in ((INTERIOR, (0, 2)), (DECIDING, None)):
         first = rt.generate(env.prompts, sp, cuts=env.cuts(case, layers), **KW)
-        try:
-            rt.prefill_chunk = 2
+        with ph.prefill_chunks(rt, 2):
             assert _same(rt.generate(env.prompts, sp, cuts=env.cuts(case, layers), **KW), first), "prefill chunks of two"
-        finally:
-            del rt.prefill_chunk
         for what in ("captures the decode graph", "replays it"):        # the first call of the key ran eagerly
             assert _same(rt.generate(env.prompts, sp, cuts=env.cuts(case, layers), **KW), first), what
         both = rt.generate(env.prompts, sp, cuts=env.cuts(case, layers), want_hidden=True, want_heads=True, **KW)
@@ -240,27 +158,14 @@ def test_refusals_launch_nothing(env):
 
 
 def test_plugin():
-    from icl_speech_text_llm_amd.models.model_factory import ModelFactory
-    model = ModelFactory.create_model("salmonn", device="cuda", arch="tiny", low_resource=True, llama_path="none", lora_alpha=32).eval()
-    b = salmonn_batch(model, "speech", n=2, bs=2, num_examples=2)
-    b = {k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
-    seen = {}
-    real = model.runtime.generate
-
-    def generate(segs, speech, **kw):
-        seen.update(kw)
-        seen["result"] = real(segs, speech, **kw)
-        return seen["result"]
-    model.runtime.generate = generate
-    try:
+    model, b = ph.tiny_plugin_batches(2)
+    with ph.spy_generate(model) as seen:
         out = model.generate_cut(dict(b), [(("example", 1), ("example", 0)), (("speech", 0), ("example", 1))], generated=("speech", 0))
-    finally:
-        del model.runtime.generate
     assert set(out) == {"texts", "tokens", "first_logits", "pieces"}
     c = model.cfg.llama
     assert len(out["texts"]) == 2 and out["tokens"].shape[0] == 2 and out["first_logits"].shape == (2, c.vocab)
     assert out["pieces"] == model.prompt_attention(dict(b))["pieces"]
-    ct = seen["cuts"]
+    ct = seen["kw"]["cuts"]
     ids = lambda pc, *ps: [pc.index(p) for p in ps]
     assert ct["layers"] is None and ct["heads"] is None and ct["generated"] == [pc.index(("speech", 0)) for pc in out["pieces"]]
     assert ct["pairs"] == [[tuple(ids(pc, ("example", 1), ("example", 0))), tuple(ids(pc, ("speech", 0), ("example", 1)))] for pc in out["pieces"]]

@@ -1,7 +1,7 @@
 """`-m gpu`: ``generate(want_heads=..., head_patch=...)`` and ``head_contrib`` of the runtime, then the plugin (the launch itself:
 tests/test_gpu_head_rows.py).
 
-The decoders of tests/test_gpu_resid_patch_runtime.py (tests/resid_patch_ref.py ``Env``: 3 layers of hidden 512, 4 heads of 128 —
+The decoders of tests/test_gpu_resid_patch_runtime.py (tests/probe_harness.py ``Decoder``: 3 layers of hidden 512, 4 heads of 128 —
 multi-head with the trimmed last layer, and grouped 4 / 2 with QK-norm), five ragged prompts, one with a speech segment, four new
 tokens.
 
@@ -22,21 +22,21 @@ import pytest
 import torch
 
 import fp64_bounds as fb
-import resid_patch_ref as rr
-from decoder_support import salmonn_batch
+import probe_harness as ph
 from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
+from probe_harness import PARITY_RATIO, rel as _rel, same_result as _same
 
 pytestmark = pytest.mark.gpu
 
-PARITY_RATIO = 1.25
-NEW, L = rr.NEW, rr.N_LAYERS
+NEW, L = ph.NEW, 3
+FORMS = {"mha": (None, False), "gqa-qknorm": (2, True)}
 KW = dict(max_new_tokens=NEW, suppress_eos=True, want_first_logits=True, want_step_logits=True)
 ALL = lambda c, layer: [(layer, h) for h in range(c.n_heads)]
 
 
-class _Env(rr.Env):
+class _Env(ph.Decoder):
     def __init__(self, kv, qk_norm):
-        super().__init__(kv, qk_norm)
+        super().__init__(kv, qk_norm, n_layers=L, other=True)
         self.rt = self.runtime(DEV)
         self.sp = self.speech.to(DEV)
         self.plain = self.gen()
@@ -54,59 +54,10 @@ class _Env(rr.Env):
     def vectors(self, pairs, rows=slice(None)):
         return torch.stack([self.vec[rows, l, h] for l, h in pairs], dim=1)
 
-    def hf_heads(self, m, dtype, tokens, hp=None):
-        """transformers on prompt + the first NEW - 1 tokens of ``tokens`` (teacher-forced), eager attention, in ``dtype``.  A
-        forward pre-hook on every layer's ``self_attn.o_proj`` reads its input's last prompt row and, with ``hp`` = dict(heads,
-        vectors f32 [B, n_pairs, D] | [1, n_pairs, D], mode, alpha, steps, rows | None), rewrites the selected heads of that row
-        (``steps="all"``: and of every later row).  -> (step logits f64 [NEW, B, V], head_out f64 [B, L, H, D], pre-patch)."""
-        m, c = m.to(dtype), self.cfg.llama
-        H, D = c.n_heads, c.head_dim
-        emb = m.get_input_embeddings().weight.detach().float()
-        Bn = len(self.prompts)
-        logits = torch.zeros(NEW, Bn, c.vocab, dtype=torch.float64)
-        head_out = torch.zeros(Bn, c.n_layers, H, D, dtype=torch.float64)
-        for b, segs in enumerate(self.prompts):
-            x = torch.cat([self.speech[s[1]:s[1] + s[2]] if isinstance(s, tuple) else emb[torch.tensor(s)] for s in segs]
-                          + [emb[tokens[b, :NEW - 1]]])
-            n = self.lens[b]
-            seen = []
 
-            def hook(mod, args, layer=None, b=b, n=n, seen=seen):
-                a = args[0]
-                seen.append(layer)
-                head_out[b, layer] = a[0, n - 1].double().view(H, D)
-                if hp is None or (hp.get("rows") is not None and b not in hp["rows"]):
-                    return None
-                mine = [(s, h) for s, (l, h) in enumerate(hp["heads"]) if l == layer]
-                if not mine:
-                    return None
-                a = a.clone()
-                sl = slice(n - 1, None) if hp.get("steps", "prompt") == "all" else slice(n - 1, n)
-                for s, h in mine:
-                    v = hp["vectors"]
-                    v = (v[0, s] if v.shape[0] == 1 else v[b, s]).to(a.dtype)
-                    cols = slice(h * D, (h + 1) * D)
-                    a[0, sl, cols] = v if hp.get("mode", "replace") == "replace" else a[0, sl, cols] + hp.get("alpha", 1.0) * v
-                return (a,) + tuple(args[1:])
-            hooks = [lay.self_attn.o_proj.register_forward_pre_hook(lambda mo, a, i=i: hook(mo, a, layer=i)) for i, lay in enumerate(m.model.layers)]
-            try:
-                with torch.no_grad():
-                    lg = m(inputs_embeds=x[None].to(dtype)).logits[0]
-            finally:
-                for h in hooks:
-                    h.remove()
-            assert seen == list(range(c.n_layers)), seen
-            logits[:, b] = lg[n - 1:].double()
-        return logits, head_out
-
-
-@pytest.fixture(scope="module", params=list(rr.FORMS), ids=list(rr.FORMS))
+@pytest.fixture(scope="module", params=list(FORMS), ids=list(FORMS))
 def env(request):
-    return _Env(*rr.FORMS[request.param])
-
-
-def _same(a, b):
-    return torch.equal(a.tokens, b.tokens) and torch.equal(a.first_logits, b.first_logits) and torch.equal(a.step_logits, b.step_logits)
+    return _Env(*FORMS[request.param])
 
 
 def _bits(t):
@@ -189,11 +140,8 @@ def test_prefill_chunks_give_the_same_bits(env, name):
     hp = _patch(env, name)
     one = env.gen(hp, want_heads=True)
     assert not _same(one, env.plain)
-    try:
-        env.rt.prefill_chunk = 2
+    with ph.prefill_chunks(env.rt, 2):
         two = env.gen(hp, want_heads=True)
-    finally:
-        del env.rt.prefill_chunk
     assert _same(one, two) and torch.equal(_bits(one.head_out), _bits(two.head_out))
     first = min(l for l, _ in hp["heads"])
     assert torch.equal(_bits(one.head_out[:, :first + 1]), _bits(env.cap.head_out[:, :first + 1]))   # pre-patch; nothing before it moves
@@ -315,10 +263,6 @@ def test_head_contrib_against_float64(env):
 # ------------------------------------------------------------------------------------------------------------------
 # against transformers
 # ------------------------------------------------------------------------------------------------------------------
-def _rel(a, b):
-    return float((a - b).norm() / b.norm()) if float(b.norm()) > 0 else float((a - b).norm())
-
-
 HF_PATCHES = {
     "zero-two-heads-prompt": dict(heads=[(1, 2), (0, 1)], mode="replace", steps="prompt", scale=0.0),
     "add-half-v-all": dict(heads=[(1, 2), (0, 1)], mode="add", alpha=0.5, steps="all", scale=1.0),
@@ -334,58 +278,32 @@ def test_patched_run_against_transformers(env, name):
     res = env.gen(hp, want_heads=True)
     got, heads = res.step_logits.double().cpu(), res.head_out.double().cpu()
     hf = env.hf()
-    want32, ho32 = env.hf_heads(hf, torch.float32, res.tokens, hp)
-    want16, ho16 = env.hf_heads(hf, torch.bfloat16, res.tokens, hp)
-    free32, _ = env.hf_heads(hf, torch.float32, res.tokens)
+    want32, ho32 = ph.heads_run(env, hf, torch.float32, res.tokens, hp)
+    want16, ho16 = ph.heads_run(env, hf, torch.bfloat16, res.tokens, hp)
+    free32, _ = ph.heads_run(env, hf, torch.float32, res.tokens)
     c = env.cfg.llama
     tag = f"{name} kv={c.n_kv_heads} qk_norm={c.qk_norm}"
     for layer in range(L):
         own, mine = _rel(ho16[:, layer], ho32[:, layer]), _rel(heads[:, layer], ho32[:, layer])
         print(f"{tag} layer {layer} head_out: rel-L2 vs HF fp32 {mine:.3e}; HF bf16 vs HF fp32 {own:.3e}; ratio {mine / own:.3f} (allowed {PARITY_RATIO})")
         assert mine <= PARITY_RATIO * own, f"layer {layer}"
-    for t in range(NEW):
-        own, mine, effect = _rel(want16[t], want32[t]), _rel(got[t], want32[t]), _rel(free32[t], want32[t])
-        print(f"{tag} step {t}: rel-L2 vs HF fp32 {mine:.3e}; HF bf16 vs HF fp32 {own:.3e}; ratio {mine / own:.3f} (allowed "
-              f"{PARITY_RATIO}); the patch moves HF's logits by {effect:.3e}")
-        assert effect > 0, "the patch does not reach transformers' attention output: the reference would prove nothing"
-        assert mine <= PARITY_RATIO * own, f"step {t}"
-    top2 = want32.topk(2, dim=-1).values
-    margin = (top2[..., 0] - top2[..., 1]).t()                                   # [B, NEW]
-    noise = float((want16 - want32).abs().max())
-    decisive = margin > 2 * PARITY_RATIO * noise
-    print(f"{tag}: top-1 / top-2 margins of HF fp32: {int(decisive.sum())} of {decisive.numel()} above {2 * PARITY_RATIO * noise:.3f}; "
-          f"largest |logit difference| to HF fp32 {float((got - want32).abs().max()):.3e}")
-    assert int(decisive.sum()) >= MIN_DECISIONS
-    assert torch.equal(res.tokens[decisive], want32.argmax(-1).t()[decisive])
+    ph.parity_check(got, want32, want16, free32, res.tokens, tag, effect_floor=0, min_decisive=MIN_DECISIONS)
 
 
 # ------------------------------------------------------------------------------------------------------------------
 # the plugin
 # ------------------------------------------------------------------------------------------------------------------
 def test_plugin():
-    from icl_speech_text_llm_amd.models.model_factory import ModelFactory
-    model = ModelFactory.create_model("salmonn", device="cuda", arch="tiny", low_resource=True, llama_path="none", lora_alpha=32).eval()
-    on_gpu = lambda b: {k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
-    few = on_gpu(salmonn_batch(model, "speech", n=2, bs=2, num_examples=2))
-    zero = on_gpu(salmonn_batch(model, "speech", n=2, bs=2, num_examples=0))
+    model, few, zero = ph.tiny_plugin_batches(2, 0)
     c = model.cfg.llama
     ho = model.head_outputs(dict(few))
     assert set(ho) == {"head_out", "first_logits", "tokens", "texts"} and ho["head_out"].shape == (2, c.n_layers, c.n_heads, c.head_dim)
     plain_few = model.generate_ids(dict(few), want_first_logits=True)
     assert torch.equal(ho["first_logits"], plain_few.first_logits) and torch.equal(ho["tokens"], plain_few.tokens)
-    seen = {}
-    real = model.runtime.generate
-
-    def generate(segs, speech, **kw):
-        seen.update(segs=segs, speech=speech, kw=kw)
-        return real(segs, speech, **kw)
     pairs = [(c.n_layers - 1, 1), (0, 0)]
     vec = torch.stack([ho["head_out"][:, l, h].float() for l, h in pairs], dim=1)
-    model.runtime.generate = generate
-    try:
+    with ph.spy_generate(model) as seen:
         out = model.generate_head_patched(dict(zero), pairs, vec)
-    finally:
-        del model.runtime.generate
     assert set(out) == {"texts", "tokens", "first_logits"} and len(out["texts"]) == 2 and out["first_logits"].shape == (2, c.vocab)
     hp = seen["kw"]["head_patch"]
     assert hp["heads"] == pairs and hp["mode"] == "replace" and hp["steps"] == "prompt" and hp["rows"] is None

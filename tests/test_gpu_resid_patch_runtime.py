@@ -1,7 +1,7 @@
 """`-m gpu`: ``generate(want_hidden=..., patch=...)`` and ``layer_logits`` of the runtime, then the plugin (the launch itself:
 tests/test_gpu_resid_patch.py).
 
-3-layer decoders of hidden 512 (tests/resid_patch_ref.py ``Env``: a first, a middle and a last layer — trimmed to the last rows in
+3-layer decoders of hidden 512 (tests/probe_harness.py ``Decoder``: a first, a middle and a last layer — trimmed to the last rows in
 the multi-head form; grouped 4 / 2 with QK-norm as the second form), five ragged prompts, one with a speech segment, four new tokens.
 
 Exact (bits): ``want_hidden`` changes nothing else; replacing a site by its own captured rows is the unpatched run, at every site
@@ -20,20 +20,20 @@ from functools import lru_cache
 import pytest
 import torch
 
-import resid_patch_ref as rr
-from decoder_support import salmonn_batch
+import probe_harness as ph
 from gpu_support import DEV, B, stop_after_a_device_fault  # noqa: F401  (fixtures)
+from probe_harness import PARITY_RATIO, rel as _rel, same_result as _same
 
 pytestmark = pytest.mark.gpu
 
-PARITY_RATIO = 1.25
-NEW, L = rr.NEW, rr.N_LAYERS
+NEW, L = ph.NEW, 3                                    # a first, a middle and a (trimmed, for the multi-head form) last layer
+FORMS = {"mha": (None, False), "gqa-qknorm": (2, True)}
 KW = dict(max_new_tokens=NEW, suppress_eos=True, want_first_logits=True, want_step_logits=True)
 
 
-class _Env(rr.Env):
+class _Env(ph.Decoder):
     def __init__(self, kv, qk_norm):
-        super().__init__(kv, qk_norm)
+        super().__init__(kv, qk_norm, n_layers=L, other=True)
         self.rt = self.runtime(DEV)
         self.sp = self.speech.to(DEV)
         self.plain = self.rt.generate(self.prompts, self.sp, **KW)
@@ -47,13 +47,9 @@ class _Env(rr.Env):
                                 **({} if patch is None else {"patch": patch}))
 
 
-@pytest.fixture(scope="module", params=list(rr.FORMS), ids=list(rr.FORMS))
+@pytest.fixture(scope="module", params=list(FORMS), ids=list(FORMS))
 def env(request):
-    return _Env(*rr.FORMS[request.param])
-
-
-def _same(a, b):
-    return torch.equal(a.tokens, b.tokens) and torch.equal(a.first_logits, b.first_logits) and torch.equal(a.step_logits, b.step_logits)
+    return _Env(*FORMS[request.param])
 
 
 def test_want_hidden_changes_nothing_and_the_last_site_is_the_first_logits(env):
@@ -105,11 +101,8 @@ def test_prefill_chunks_give_the_same_bits(env, name):
     patch = dict(PATCHES[name], vectors=env.vec)
     one = env.gen(patch, want_hidden=True)
     assert not _same(one, env.plain)
-    try:
-        env.rt.prefill_chunk = 2
+    with ph.prefill_chunks(env.rt, 2):
         two = env.gen(patch, want_hidden=True)
-    finally:
-        del env.rt.prefill_chunk
     assert _same(one, two) and torch.equal(one.hidden, two.hidden)
     site = patch["site"]
     assert torch.equal(one.hidden[:, :site + 1], env.cap.hidden[:, :site + 1])    # pre-patch at the patched site; nothing before it moves
@@ -199,10 +192,6 @@ def test_other_tails_and_refusals(env):
 # ------------------------------------------------------------------------------------------------------------------
 # against transformers
 # ------------------------------------------------------------------------------------------------------------------
-def _rel(a, b):
-    return float((a - b).norm() / b.norm()) if float(b.norm()) > 0 else float((a - b).norm())
-
-
 def _ratio(mine, own):
     return mine / own if own > 0 else (0.0 if mine == 0 else float("inf"))
 
@@ -210,7 +199,7 @@ def _ratio(mine, own):
 @lru_cache(maxsize=None)
 def _hf_plain(env):
     hf = env.hf()
-    return env.hf_run(hf, torch.float32, env.plain.tokens), env.hf_run(hf, torch.bfloat16, env.plain.tokens)
+    return ph.resid_run(env, hf, torch.float32, env.plain.tokens), ph.resid_run(env, hf, torch.bfloat16, env.plain.tokens)
 
 
 def test_hidden_and_the_logit_lens_against_transformers(env):
@@ -232,26 +221,13 @@ def test_patched_logits_against_transformers(env, name):
     res = env.gen(patch)
     got = res.step_logits.double().cpu()
     hf = env.hf()
-    want32, _, _ = env.hf_run(hf, torch.float32, res.tokens, patch)
-    want16, _, _ = env.hf_run(hf, torch.bfloat16, res.tokens, patch)
-    free32, _, _ = env.hf_run(hf, torch.float32, res.tokens)
-    tag = f"{name} kv={env.cfg.llama.n_kv_heads} qk_norm={env.cfg.llama.qk_norm}"
-    for t in range(NEW):
-        own, mine, effect = _rel(want16[t], want32[t]), _rel(got[t], want32[t]), _rel(free32[t], want32[t])
-        print(f"{tag} step {t}: rel-L2 vs HF fp32 {mine:.3e}; HF bf16 vs HF fp32 {own:.3e}; ratio {mine / own:.3f} (allowed "
-              f"{PARITY_RATIO}); the patch moves HF's logits by {effect:.3e}")
-        # (a prompt-only patch reaches the later steps through the cache alone; transformers on the CPU, on its own greedy tokens:
-        # 8 x the bf16 error or more at those steps, 55 x or more wherever the patch acts directly)
-        assert effect > 4 * own, "the patch does not reach transformers' residual stream: the reference would prove nothing"
-        assert mine <= PARITY_RATIO * own, f"step {t}"
-    top2 = want32.topk(2, dim=-1).values
-    margin = (top2[..., 0] - top2[..., 1]).t()                                   # [B, NEW]
-    noise = float((want16 - want32).abs().max())
-    decisive = margin > 2 * PARITY_RATIO * noise
-    print(f"{tag}: top-1 / top-2 margins of HF fp32: {int(decisive.sum())} of {decisive.numel()} above {2 * PARITY_RATIO * noise:.3f}; "
-          f"largest |logit difference| to HF fp32 {float((got - want32).abs().max()):.3e}")
-    assert int(decisive.sum()) >= decisive.numel() // 4        # (transformers alone, on the CPU: 7 to 16 of the 20)
-    assert torch.equal(res.tokens[decisive], want32.argmax(-1).t()[decisive])
+    want32, _, _ = ph.resid_run(env, hf, torch.float32, res.tokens, patch)
+    want16, _, _ = ph.resid_run(env, hf, torch.bfloat16, res.tokens, patch)
+    free32, _, _ = ph.resid_run(env, hf, torch.float32, res.tokens)
+    # (a prompt-only patch reaches the later steps through the cache alone; transformers on the CPU, on its own greedy tokens:
+    # 8 x the bf16 error or more at those steps, 55 x or more wherever the patch acts directly; 7 to 16 of the 20 margins decisive)
+    ph.parity_check(got, want32, want16, free32, res.tokens, f"{name} kv={env.cfg.llama.n_kv_heads} qk_norm={env.cfg.llama.qk_norm}",
+                    effect_floor=4, min_decisive=res.tokens.numel() // 4)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -303,29 +279,16 @@ def test_launch_trace():
 # the plugin
 # ------------------------------------------------------------------------------------------------------------------
 def test_plugin():
-    from icl_speech_text_llm_amd.models.model_factory import ModelFactory
-    model = ModelFactory.create_model("salmonn", device="cuda", arch="tiny", low_resource=True, llama_path="none", lora_alpha=32).eval()
-    on_gpu = lambda b: {k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
-    few = on_gpu(salmonn_batch(model, "speech", n=2, bs=2, num_examples=2))
-    zero = on_gpu(salmonn_batch(model, "speech", n=2, bs=2, num_examples=0))
+    model, few, zero = ph.tiny_plugin_batches(2, 0)
     c = model.cfg.llama
     tv = model.task_vectors(dict(few))
     assert set(tv) == {"hidden", "first_logits", "tokens", "texts"} and tv["hidden"].shape == (2, c.n_layers + 1, c.hidden)
     plain_few = model.generate_ids(dict(few), want_first_logits=True)
     assert torch.equal(tv["first_logits"], plain_few.first_logits) and torch.equal(tv["tokens"], plain_few.tokens)
     assert torch.equal(model.runtime.layer_logits(tv["hidden"])[:, c.n_layers], tv["first_logits"])
-    seen = {}
-    real = model.runtime.generate
-
-    def generate(segs, speech, **kw):
-        seen.update(segs=segs, speech=speech, kw=kw)
-        return real(segs, speech, **kw)
     site = c.n_layers // 2
-    model.runtime.generate = generate
-    try:
+    with ph.spy_generate(model) as seen:
         out = model.generate_patched(dict(zero), tv["hidden"][:, site], site)
-    finally:
-        del model.runtime.generate
     assert set(out) == {"texts", "tokens", "first_logits"} and len(out["texts"]) == 2 and out["first_logits"].shape == (2, c.vocab)
     assert seen["kw"]["patch"]["site"] == site and seen["kw"]["patch"]["mode"] == "replace" and seen["kw"]["patch"]["steps"] == "prompt"
     direct = model.runtime.generate(seen["segs"], seen["speech"], **seen["kw"])                 # the runtime-level call

@@ -1,6 +1,7 @@
 """`-m gpu`: ``prompt_attention(..., want_flow=True)`` of the runtime and ``prompt_attention(samples, flow=True)`` of the plugin.
 
-2-layer decoders (hidden 512, 4 heads of 128; no LoRA, so a transformers model holds the same tensors) over five ragged prompts:
+2-layer decoders of tests/probe_harness.py (hidden 512, 4 heads of 128; no LoRA, so a transformers model holds the same tensors)
+over five ragged prompts of text:
 multi-head — whose last layer a plain call trims to the last rows, and a flow call keeps at full height — and grouped 4 / 2 with
 QK-norm.  Bit for bit: with ``want_flow``, ``first_logits`` and ``mass`` are those of the call without it and ``first_logits`` are
 ``generate``'s; prefill chunks of two sequences give the bits of one chunk.  Within the two kernels' bounds: the last position has
@@ -12,49 +13,26 @@ zero padding.
 Measured on MI355X (printed by the tests, recorded in README.md): flow vs HF fp32, rel-L2, next to HF bf16 vs HF fp32 — multi-head
 1.69e-4 / 2.37e-4 (ratio 0.71), grouped QK-norm 7.12e-4 / 1.19e-3 (0.60); flow[last segment] vs mass at most 0.0014 of the bound.
 """
-from dataclasses import replace
-
 import pytest
 import torch
 
 import attn_segflow_ref as fr
-from decoder_support import row_prompts, salmonn_batch
+import probe_harness as ph
 from gpu_support import DEV, stop_after_a_device_fault  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
-PARITY_RATIO = 1.25
-PROMPT_LENS = [33, 90, 61, 12, 130]
+PROMPT_LENS = ph.PROMPT_LENS
 N_SEG = 5                  # four runs and the last position on its own
 S_CAP = 64.0               # scale * sum |q| |k| of bf16 unit-scale rows of these decoders stays below it (as tests/test_gpu_attn_segmass.py takes it)
 
 
-class _Env:
+class _Env(ph.Decoder):
     def __init__(self, kv, qk_norm):
-        from icl_speech_text_llm_amd.runtime import synth
-        from icl_speech_text_llm_amd.runtime.config import SalmonnCfg
-        from icl_speech_text_llm_amd.runtime.salmonn import SalmonnRuntime
-        tiny = SalmonnCfg.tiny(use_beats=False, lora=False)
-        self.cfg = replace(tiny, llama=replace(tiny.llama, hidden=512, n_layers=2, n_heads=4, n_kv_heads=kv, ffn=1024, qk_norm=qk_norm))
-        self.sd = synth.salmonn_state(self.cfg, seed=0, jitter=True, parts=("llama",))
-        self.rt = SalmonnRuntime(self.cfg, dict(self.sd), device=DEV, parts=("llama",))
-        self.prompts = row_prompts(self.cfg.llama.vocab, PROMPT_LENS, seed=29)
-        self.segments = []
-        for n in PROMPT_LENS:
-            sg = [min(j * 4 // n, 3) for j in range(n)]               # four runs ...
-            sg[n // 2] = 255                                           # ... one position ignored, as a query row and as a key ...
-            sg[n - 1] = N_SEG - 1                                      # ... and the last position on its own
-            self.segments.append(sg)
-
-    def hf(self):
-        import transformers as tf
-        c = self.cfg.llama
-        kw = dict(hidden_size=c.hidden, num_hidden_layers=c.n_layers, num_attention_heads=c.n_heads, num_key_value_heads=c.kv_heads,
-                  intermediate_size=c.ffn, vocab_size=c.vocab, rms_norm_eps=c.rms_eps, max_position_embeddings=c.max_pos,
-                  tie_word_embeddings=False, attention_bias=False, head_dim=c.head_dim, attn_implementation="eager")
-        m = (tf.Qwen3ForCausalLM(tf.Qwen3Config(**kw)) if c.qk_norm else tf.LlamaForCausalLM(tf.LlamaConfig(**kw))).eval()
-        m.load_state_dict({k[len("llama_model."):]: v for k, v in self.sd.items()}, strict=True)
-        return m
+        super().__init__(kv, qk_norm, n_layers=2, redraw=False, row_seed=29)
+        self.rt = self.runtime(DEV)
+        # four runs, one position ignored, as a query row and as a key, and the last position on its own
+        self.segments = [ph.four_runs(n, {n // 2: 255, n - 1: N_SEG - 1}) for n in PROMPT_LENS]
 
     def hf_flow(self, m, dtype):
         """[B, n_layers, n_heads, n_seg, n_seg] float64: transformers' eager attention matrix summed by (seg[i], seg[j])."""
@@ -89,11 +67,8 @@ def test_runtime(env):
     assert torch.equal(res.first_logits, plain.first_logits) and torch.equal(res.mass, plain.mass)
     gen = rt.generate(env.prompts, None, max_new_tokens=1, suppress_eos=True, want_first_logits=True)
     assert torch.equal(res.first_logits, gen.first_logits)
-    try:
-        rt.prefill_chunk = 2
+    with ph.prefill_chunks(rt, 2):
         chunked = rt.prompt_attention(env.prompts, None, env.segments, n_seg=N_SEG, want_flow=True)
-    finally:
-        del rt.prefill_chunk
     assert torch.equal(chunked.flow, res.flow) and torch.equal(chunked.mass, res.mass) and torch.equal(chunked.first_logits, res.first_logits)
     assert bool((res.flow >= 0).all())
     # the upper triangle of the runs is empty: a query of run a sees no key of a later run; so is everything the last segment sends
@@ -120,16 +95,14 @@ def test_runtime(env):
     hf = env.hf()
     want32 = env.hf_flow(hf, torch.float32)
     want16 = env.hf_flow(hf, torch.bfloat16)
-    rel = lambda a, b: float((a - b).norm() / b.norm())
-    own, got = rel(want16, want32), rel(res.flow.double(), want32)
+    own, got = ph.rel(want16, want32), ph.rel(res.flow.double(), want32)
     print(f"flow kv={c.n_kv_heads} qk_norm={c.qk_norm}: rel-L2 vs HF fp32 {got:.3e}; HF bf16 vs HF fp32 {own:.3e}; "
-          f"ratio {got / own:.3f} (allowed {PARITY_RATIO})")
-    assert got <= PARITY_RATIO * own
+          f"ratio {got / own:.3f} (allowed {ph.PARITY_RATIO})")
+    assert got <= ph.PARITY_RATIO * own
 
 
 def test_runtime_refusals(env):
     """``check_readout``'s refusals hold with ``want_flow`` and come before anything is sized or launched."""
-    from icl_speech_text_llm_amd.runtime.salmonn import SalmonnRuntime
     rt, c = env.rt, env.cfg.llama
     before = rt.ws.nbytes()
     with pytest.raises(ValueError, match="positions"):
@@ -142,16 +115,13 @@ def test_runtime_refusals(env):
         rt.prompt_attention([[[5] * (c.max_pos + 1)]], None, [[0] * (c.max_pos + 1)], want_flow=True)
     assert rt.ws.nbytes() == before
     if c.group == 1 and not c.qk_norm:
-        r8 = SalmonnRuntime(env.cfg, dict(env.sd), device=DEV, parts=("llama",), llm_kv_dtype="fp8")
+        r8 = env.runtime(DEV, llm_kv_dtype="fp8")
         with pytest.raises(ValueError, match="bf16 KV cache"):
             r8.prompt_attention(env.prompts, None, env.segments, want_flow=True)
 
 
 def test_plugin():
-    from icl_speech_text_llm_amd.models.model_factory import ModelFactory
-    model = ModelFactory.create_model("salmonn", device="cuda", arch="tiny", low_resource=True, llama_path="none", lora_alpha=32).eval()
-    b = salmonn_batch(model, "speech", n=2, bs=2, num_examples=2)
-    b = {k: (v.to("cuda") if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
+    model, b = ph.tiny_plugin_batches(2)
     plain = model.prompt_attention(dict(b))
     out = model.prompt_attention(dict(b), flow=True)
     assert set(plain) == {"mass", "pieces", "first_logits"} and set(out) == {"mass", "pieces", "first_logits", "flow", "rows"}

@@ -17,14 +17,14 @@ IDS = [f"h{h}-n{n}" for h, n in SHAPES]
 
 
 def test_fma32_is_one_rounding_of_the_exact_value():
-    """``_fma32`` against exact rational arithmetic, on values chosen to sit near rounding ties and on the cancellation probe."""
+    """``fma32`` against exact rational arithmetic, on values chosen to sit near rounding ties and on the cancellation probe."""
     g = np.random.default_rng(5)
     a = g.standard_normal(4000).astype(np.float32)
     v = g.standard_normal(4000).astype(np.float32)
     h = g.standard_normal(4000).astype(np.float32) * np.float32(2.0) ** g.integers(-30, 30, 4000).astype(np.float32)
     h[:1000] = -(a[:1000].astype(np.float64) * v[:1000].astype(np.float64)).astype(np.float32)         # cancellation
     h[1000:1500] = np.float32(2.0 ** 24) * np.sign(h[1000:1500])                                       # sums next to a tie
-    got = rr._fma32(a, v, h)
+    got = rr.fma32(a, v, h)
     for i in range(len(a)):
         x = Fraction(float(a[i])) * Fraction(float(v[i])) + Fraction(float(h[i]))
         # the two f32 neighbours of x around fl32(float(x)); float(x) is correctly rounded to f64, which orders them correctly
